@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json metric "1080p30 frames/sec encode+decode per GPU" on MI355X.
 
-Parity: the GPU's NAL bytes and decoded pictures are checked against the oracle (oracle/, the CPU
+Parity (--full): the GPU's NAL bytes and decoded pictures are checked against the oracle (oracle/, the CPU
 restatement of the reference path) on the bench's own geometry and bitrate: the first frames of every
 stream (captured in the warmup) and the last timed frame of every stream (captured after the timed
 region); parity with OpenH264 itself is partial. A failed check prints value null and exits 1.
@@ -23,7 +23,21 @@ Other BASELINE.json configs (one JSON line each, N = 1):
   --config 4  1920x1080 decode only: 8 concurrent decoders of one 1080p stream (the app.js fan-out)
   --config 5  1920x1080 IPPP encode+decode, 4 streams per GPU (32 over 8 GPUs), NAL gather at N > 1
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--streams S] [--group G]
+A plain run (no --full) does what the headline figure needs and nothing else: it sets up, warms up, times
+the K steps, writes its outputs when --dump-outputs is given and prints the line; the decoders' status is
+read, nothing is compared. --full adds the rest: the CPU leg (the oracle's baseline and the parity check
+against its hashes), the decoder == reconstruction self-check, and the rocprofv3 --pmc passes behind
+roofline.traffic and kernels.dec_parse_kernel.sq (--no-cpu-baseline / --no-traffic leave one of them out).
+
+--dump-outputs DIR: after the timed steps, what the timed path produced in its last step as DIR/<name>.npy
+(float32 / float64, under 64 MB; `_rank<r>` is appended to <name> at N > 1): nal_sizes and nal_bytes (every
+stream's access unit of the last frame, back to back in stream order), picture_row_sums (every stream's
+decoded I420 picture of the last frame, summed over each row of W bytes: any changed sample shows),
+picture_sample (the samples of every picture at the positions in picture_sample_index, a fixed seeded draw).
+The inputs are a pure function of the arguments, so two builds can be compared output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--streams S] [--group G] [--full]
+                  [--dump-outputs DIR]
   --gpus N > 1 without a torch.distributed launcher: bench.py starts `torch.distributed.run` with N
   ranks itself (a child process, before this process touches the GPU) and exits with its code.
 """
@@ -96,12 +110,20 @@ def parse():
     ap.add_argument('--gom-exact', action='store_true',
                     help='P-frame QPs by OpenH264\'s exact GOM rate control (H264MI_GOM_EXACT=1 for the encoders and the '
                          'oracle); default: this project\'s MB-row plan (DESIGN.md §3.6)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the CPU baseline and the parity check against '
+                         'the oracle, the decoder == reconstruction self-check, the rocprofv3 --pmc passes')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s outputs (NAL units, decoded pictures) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU leg out')
     ap.add_argument('--cpu-frames', type=int, default=7)
     ap.add_argument('--parity-frames', type=int, default=4, help='frames of stream 0 checked against the oracle before timing')
-    ap.add_argument('--no-traffic', action='store_true', help='skip the rocprofv3 --pmc passes that measure roofline.traffic')
+    ap.add_argument('--no-traffic', action='store_true',
+                    help='with --full: skip the rocprofv3 --pmc passes that measure roofline.traffic')
     ap.add_argument('--traffic-probe', action='store_true', help=argparse.SUPPRESS)  # child of measure_traffic()
     a = ap.parse_args()
+    if not a.full:  # a plain run: no CPU leg, no PMC passes
+        a.no_cpu_baseline = a.no_traffic = True
     if a.gom_exact:  # before any child process starts and before the library is loaded
         os.environ['H264MI_GOM_EXACT'] = '1'
     if a.config == 2:
@@ -451,7 +473,7 @@ def main():
     elif world > 1 and not a.no_cpu_baseline:
         shashes, last = oracle_hashes(a, mode, rank * a.streams)
     a.traffic_kernel = 'dec_recon_kernel' if a.config == 4 else 'enc_mb_kernel'
-    a.traffic_measured = (None, 'not measured (--no-traffic or N > 1)')
+    a.traffic_measured = (None, 'not measured (--no-traffic or N > 1)' if a.full else 'not measured (a plain run; --full measures it)')
     a.parse_mix = None
     if rank == 0 and world == 1 and not a.no_traffic:
         a.traffic_measured = measure_traffic(a)
@@ -480,7 +502,7 @@ def main():
         # the warmup, which starts at frame 0) against the oracle's hashes of the same streams
         cap = a.parity_frames if shashes is not None and a.warmup >= a.parity_frames else 0
         res = bench_encode(a, torch, np, h264mi, SyntheticStream, NalGather, stream_ids, dev, sync, dist, world, rank, cap)
-    parity_ok, parity_msg = True, 'skipped (--no-cpu-baseline)'
+    parity_ok, parity_msg = True, 'skipped (--no-cpu-baseline)' if a.full else 'skipped (a plain run; --full checks it)'
     if a.config == 4 and hashes is not None:
         # decode-only: the bench's stream 0 (its decoders all decode that stream) from a fresh encoder +
         # decoder after the timed region
@@ -493,6 +515,8 @@ def main():
         if world > 1:
             parity_msg = f'rank {rank}: ' + parity_msg
     res.pop('captured', None)
+    if res.get('last_frame') is None:  # a plain run hashes nothing
+        res.pop('last_frame', None)
     parity_ok = parity_ok and res.pop('selfcheck_ok')
     elapsed = res.pop('elapsed')
     if dist:
@@ -563,6 +587,53 @@ def roofline(kernel, alg_bytes, ms_total, launches, a, note=None):
     return r
 
 
+def load_clip(clip, sids, W, H, torch, SyntheticStream, dev):
+    """clip[t, i * F:(i + 1) * F] = SyntheticStream(sids[i], W, H).frame(t) for every t: the streams' textures are
+    made on the host (a thread per stream, up to 16 at a time: numpy releases the GIL), go to the GPU once, and each
+    frame's window is cut there -- the same bytes as frame(t), without 60 host copies of every stream's frame"""
+    from concurrent.futures import ThreadPoolExecutor
+    F = W * H * 3 // 2
+    with ThreadPoolExecutor(max(1, min(16, os.cpu_count() or 1))) as pool:
+        gens = pool.map(lambda sid: SyntheticStream(sid, W, H), sids)
+        for i, g in enumerate(gens):
+            ty, tu, tv = (torch.from_numpy(x).to(dev) for x in (g.ty, g.tu, g.tv))
+            for t in range(clip.shape[0]):
+                ox, oy = g.offset(t)
+                f = clip[t, i * F:(i + 1) * F]
+                f[:W * H].view(H, W).copy_(ty[oy:oy + H, ox:ox + W])
+                f[W * H:W * H * 5 // 4].view(H // 2, W // 2).copy_(tu[oy // 2:oy // 2 + H // 2, ox // 2:ox // 2 + W // 2])
+                f[W * H * 5 // 4:].view(H // 2, W // 2).copy_(tv[oy // 2:oy // 2 + H // 2, ox // 2:ox // 2 + W // 2])
+
+
+DUMP_SAMPLE_BYTES = 32 << 20  # picture_sample.npy, and
+DUMP_NAL_BYTES = 16 << 20     # nal_bytes.npy: with the small arrays the dump stays under 64 MB
+
+
+def dump_outputs(a, np, rank, world, sizes, nals, pics):
+    """--dump-outputs: the last timed step's outputs as float .npy files (see the module docstring). sizes: NAL bytes
+    per stream and nals: every stream's unit (None: the config encodes nothing); if they exceed nal_bytes.npy's
+    share, every unit is cut to the same length (nal_sizes keeps the whole sizes). pics: every stream's decoded
+    tight I420 picture as bytes (None: the config decodes nothing)"""
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    sfx = f'_rank{rank}' if world > 1 else ''
+
+    def save(name, x):
+        np.save(os.path.join(a.dump_outputs, name + sfx + '.npy'), x)
+
+    if sizes is not None:
+        save('nal_sizes', np.asarray(sizes, np.float64))
+        if sum(sizes) * 4 > DUMP_NAL_BYTES:
+            nals = [x[:DUMP_NAL_BYTES // 4 // len(nals)] for x in nals]
+        save('nal_bytes', np.frombuffer(b''.join(nals), np.uint8).astype(np.float32))
+    if pics:
+        F = a.width * a.height * 3 // 2
+        p = np.stack([np.frombuffer(x, np.uint8) for x in pics])
+        save('picture_row_sums', p.reshape(len(pics), F // a.width, a.width).sum(axis=2, dtype=np.float64))
+        idx = np.sort(np.random.default_rng(0).choice(F, min(F, DUMP_SAMPLE_BYTES // 4 // len(pics)), replace=False))
+        save('picture_sample_index', idx.astype(np.float64))
+        save('picture_sample', p[:, idx].astype(np.float32))
+
+
 def bench_encode(a, torch, np, h264mi, SyntheticStream, NalGather, stream_ids, dev, sync, dist, world, rank, capture=0):
     """configs 0 (metric), 2 (I-only encode), 3 (one stream), 5 (4 streams): encode (+ decode). capture = K:
     the warmup keeps every stream's NAL units and decoded pictures of frames 0..K-1 (parity check)"""
@@ -571,9 +642,7 @@ def bench_encode(a, torch, np, h264mi, SyntheticStream, NalGather, stream_ids, d
     i_only = a.config == 2
     decode = not i_only and not a.no_decode
     clip = torch.empty((a.clip, S * F), dtype=torch.uint8, device=dev)
-    for i, sid in enumerate(stream_ids(rank, S)):
-        g = SyntheticStream(sid, W, H)
-        clip[:, i * F:(i + 1) * F].copy_(torch.from_numpy(np.stack([g.frame(t) for t in range(a.clip)])))
+    load_clip(clip, stream_ids(rank, S), W, H, torch, SyntheticStream, dev)
     sync()
     # The encoder codes frame t of all S streams on `es` (P frames chain through its reconstruction,
     # so it is sequential in time) and copies each frame's NAL units to a staging slot; the decoder,
@@ -715,17 +784,22 @@ def bench_encode(a, torch, np, h264mi, SyntheticStream, NalGather, stream_ids, d
         del pics
         cap_nal.clear()
         cap_pic = None
-    selfcheck_ok = True
-    if decode:
+    def selfcheck():
+        """every decoder's status; --full: every stream's decoded picture == the encoder's reconstruction"""
+        ok = True
         for dec in decs:
             rc, got = dec.status()
-            selfcheck_ok = selfcheck_ok and rc == 0 and all(got)
-        nb = decs[0].cw * decs[0].ch * 3 // 2
-        for s in range(S):
-            x, y = np.empty(nb, np.uint8), np.empty(nb, np.uint8)
-            h264mi._hip_memcpy_d2h(x.ctypes.data, encs[s // Sg].recon_ptr(s % Sg), nb)
-            h264mi._hip_memcpy_d2h(y.ctypes.data, decs[s // Sd].picture_ptr(s % Sd), nb)
-            selfcheck_ok = selfcheck_ok and bool(np.array_equal(x, y))
+            ok = ok and rc == 0 and all(got)
+        if decode and a.full:
+            nb = decs[0].cw * decs[0].ch * 3 // 2
+            for s in range(S):
+                x, y = np.empty(nb, np.uint8), np.empty(nb, np.uint8)
+                h264mi._hip_memcpy_d2h(x.ctypes.data, encs[s // Sg].recon_ptr(s % Sg), nb)
+                h264mi._hip_memcpy_d2h(y.ctypes.data, decs[s // Sd].picture_ptr(s % Sd), nb)
+                ok = ok and bool(np.array_equal(x, y))
+        return ok
+
+    selfcheck_ok = selfcheck()
     for enc in encs:
         enc.set_timing(True)
     for dec in decs:
@@ -736,22 +810,21 @@ def bench_encode(a, torch, np, h264mi, SyntheticStream, NalGather, stream_ids, d
     # after the timed region: every stream's last timed frame (NAL units in the last staging slot, the decoders'
     # current pictures) for the oracle check, and the decoder == reconstruction self-check again
     sync()
-    lb, lj = state['last']
-    szl = stage_sz[lb][lj].cpu().tolist()
-    hostl = stage[lb][lj].cpu().numpy()
-    last_frame = [{'nal': hashlib.sha256(hostl[s * slot:s * slot + szl[s]].tobytes()).hexdigest(),
-                   'pic': hashlib.sha256(decs[s // Sd].picture_i420(s % Sd)).hexdigest() if decode else None} for s in range(S)]
-    del hostl
-    if decode:
-        for dec in decs:
-            rc, got = dec.status()
-            selfcheck_ok = selfcheck_ok and rc == 0 and all(got)
-        nb = decs[0].cw * decs[0].ch * 3 // 2
-        for s in range(S):
-            x, y = np.empty(nb, np.uint8), np.empty(nb, np.uint8)
-            h264mi._hip_memcpy_d2h(x.ctypes.data, encs[s // Sg].recon_ptr(s % Sg), nb)
-            h264mi._hip_memcpy_d2h(y.ctypes.data, decs[s // Sd].picture_ptr(s % Sd), nb)
-            selfcheck_ok = selfcheck_ok and bool(np.array_equal(x, y))
+    last_frame = None
+    if a.full or a.dump_outputs:
+        lb, lj = state['last']
+        szl = stage_sz[lb][lj].cpu().tolist()
+        hostl = stage[lb][lj].cpu().numpy()
+        nals = [hostl[s * slot:s * slot + szl[s]].tobytes() for s in range(S)]
+        pics = [decs[s // Sd].picture_i420(s % Sd) for s in range(S)] if decode else None
+        del hostl
+        if a.full:
+            last_frame = [{'nal': hashlib.sha256(nals[s]).hexdigest(),
+                           'pic': hashlib.sha256(pics[s]).hexdigest() if decode else None} for s in range(S)]
+        if a.dump_outputs:
+            dump_outputs(a, np, rank, world, szl, nals, pics)
+        del nals, pics
+    selfcheck_ok = selfcheck() and selfcheck_ok
     gather_check = None
     if gather is not None:  # the last group's units as rank 0 received them == what every rank staged
         sync()
@@ -812,8 +885,9 @@ def bench_encode(a, torch, np, h264mi, SyntheticStream, NalGather, stream_ids, d
             'roofline': roofline('enc_mb_kernel', alg, ems, en, a), 'kernels': kern,
             'nal_gather': gather_check,
             'selfcheck_ok': selfcheck_ok,
-            'selfcheck': ('decoder output == encoder reconstruction for every stream, after the warmup and after the timed '
-                          'region: ' + ('pass' if selfcheck_ok else 'FAIL'))
+            'selfcheck': (('decoder output == encoder reconstruction for every stream' if a.full else
+                           'every decoder\'s status (a plain run; --full compares the pictures with the encoder\'s reconstruction)')
+                          + ', after the warmup and after the timed region: ' + ('pass' if selfcheck_ok else 'FAIL'))
             if decode else 'n/a (encode only)',
             'last_nal_bytes': sizes}
 
@@ -862,12 +936,15 @@ def bench_decode_only(a, torch, np, h264mi, SyntheticStream, dev, sync):
     sync()
     rc, got = dec.status()
     ok = rc == 0 and all(got)
-    pics = [dec.picture_i420(s) for s in range(S)]
-    ok = ok and all(p == pics[0] for p in pics)
+    if a.full:
+        pics = [dec.picture_i420(s) for s in range(S)]
+        ok = ok and all(p == pics[0] for p in pics)
     dec.set_timing(True)
     elapsed = timed(run_steps, a.steps, 0, None, sync)
     rms, rn = dec.kernel_time(0)
     pms, pn = dec.kernel_time(1)
+    if a.dump_outputs:
+        dump_outputs(a, np, 0, 1, None, None, [dec.picture_i420(s) for s in range(S)])
     dec.close()
     enc.close()
     if a.parse_cus > 0:
@@ -883,7 +960,9 @@ def bench_decode_only(a, torch, np, h264mi, SyntheticStream, dev, sync):
                                       'chain (latency-bound, no meaningful HBM roofline)'),
             'kernels': {'dec_recon_kernel': {'avg_ms': rms / max(rn, 1), 'launches': rn},
                         'dec_parse_kernel': {'avg_ms': pms / max(pn, 1), 'launches': pn, 'slices_per_launch': S * G}},
-            'selfcheck_ok': ok, 'selfcheck': 'all decoders produce the same picture: ' + ('pass' if ok else 'FAIL')}
+            'selfcheck_ok': ok,
+            'selfcheck': ('all decoders produce the same picture: ' if a.full else 'the decoder\'s status (a plain run; --full '
+                          'compares the decoders\' pictures): ') + ('pass' if ok else 'FAIL')}
 
 
 if __name__ == '__main__':

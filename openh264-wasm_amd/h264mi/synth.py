@@ -44,9 +44,13 @@ class SyntheticStream:
         self.tu = texture(seed ^ 0x55555555, w // 2 + 32, h // 2 + 32)
         self.tv = texture(seed ^ 0x2AAAAAAA, w // 2 + 32, h // 2 + 32)
 
+    def offset(self, t):
+        """frame t's window in the textures: (x, y) in luma pixels (half of each for the chroma planes)"""
+        return (3 * t) % 64, (2 * t) % 64
+
     def frame(self, t):
         w, h = self.w, self.h
-        ox, oy = (3 * t) % 64, (2 * t) % 64
+        ox, oy = self.offset(t)
         y = self.ty[oy:oy + h, ox:ox + w]
         u = self.tu[oy // 2:oy // 2 + h // 2, ox // 2:ox // 2 + w // 2]
         v = self.tv[oy // 2:oy // 2 + h // 2, ox // 2:ox // 2 + w // 2]
