@@ -90,6 +90,16 @@ int h264mi_enc_frames_skipped(h264mi_encoder *e, int stream);
    31 MBs wide) takes its QP from the bits of every MB before it, so a stream keeps one GOM in flight; off (the
    default unless H264MI_GOM_EXACT=1 at creation): this project's MB-row QP plan inside the frame's window */
 int h264mi_enc_set_gom_exact(h264mi_encoder *e, int enable);
+/* Slices: every picture coded as n slices of whole macroblock rows, 1 <= n <= min(MB rows, 32); slice k starts at MB
+   row (k * rows) / n (h264mi_slice_first_row) and ends where slice k + 1 starts. The slices of a picture depend on
+   each other only through the deblocking filter, so a decoder can parse them in parallel
+   (h264mi_dec_set_slice_waves). Default 1, or H264MI_ENC_SLICES=n at creation (a bad value is ignored); takes effect
+   from the next h264mi_enc_encode. Returns 0, or -1 on a bad n. Exact GOM rate control is a single-slice mode:
+   set_slices(n > 1) fails while it is on, and set_gom_exact(1) fails while n > 1. */
+int h264mi_enc_set_slices(h264mi_encoder *e, int n);
+int h264mi_enc_slices(h264mi_encoder *e);
+/* host only: the first MB row of slice k of a picture of mbh MB rows in n slices; mbh for k == n; -1 on bad arguments */
+int h264mi_slice_first_row(int mbh, int n, int k);
 /* test hook: the next coded frame of stream fails as if its kernels had reported error code (> 0): it
    publishes 0 NAL bytes and the frame after it is an IDR. Code 3 fails it through enc_pack_kernel's
    RBSP-overflow branch itself (the early exit before the slice is assembled) */

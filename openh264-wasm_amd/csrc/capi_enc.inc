@@ -145,8 +145,22 @@ int h264mi_enc_set_frame_skip(h264mi_encoder *e, int enable) {
 // OpenH264's exact GOM rate control (DESIGN.md §3.6): each GOM's QP from the bits of every MB before it
 int h264mi_enc_set_gom_exact(h264mi_encoder *e, int enable) {
     if (!e) return -1;
+    if (enable && e->c->slices > 1) return -1;  // the rule restates OpenH264's single-slice budget (DESIGN.md §3.7)
     e->c->gom_exact = enable != 0;
     return 0;
+}
+// n slices of whole MB rows per picture from the next encode on (DESIGN.md §3.7). One host value for all streams:
+// each frame step hands it to its begin kernel, which latches it per stream (enc_begin_stream) for the frame's other
+// kernels, and picks the pack kernel by it -- frames already issued keep the count they were issued with
+int h264mi_enc_set_slices(h264mi_encoder *e, int n) {
+    if (!e || !slices_valid(e->c->mbh, n) || (n > 1 && e->c->gom_exact)) return -1;
+    e->c->slices = n;
+    return 0;
+}
+int h264mi_enc_slices(h264mi_encoder *e) { return e ? e->c->slices : -1; }
+int h264mi_slice_first_row(int mbh, int n, int k) {
+    if (mbh < 1 || !slices_valid(mbh, n) || k < 0 || k > n) return -1;
+    return slice_first_row(mbh, n, k);
 }
 int h264mi_enc_inject_error(h264mi_encoder *e, int stream, int code) {
     if (!e || stream < 0 || stream >= e->c->S || code <= 0) return -1;

@@ -227,6 +227,10 @@ struct DbkSrcGranules {
     uint32_t epoch;
     GLOBAL const uint64_t *rowq;  // QPY entering each MB row (row_entry_qp), for records flagged 0x80
     int slice_qp;
+    // row mby / mby - 1 is its slice's first row: entered at the slice QP (row_entry_qp). Only the encoder's records
+    // are ever flagged 0x80 (a decoder's QP byte is at most 51), so the decoder, which leaves rowq null, never gets
+    // there; the default keeps even such a record off rowq
+    bool first_c = true, first_t = true;
     uint64_t xl, xc, xi;       // the granules of the MB get() is asked for next, loaded one MB ahead
     // loads of MB mx's granules (tile dword `lane`, chroma, records of MB mx and the MB above); their
     // values are consumed by the next get(), so the load latency overlaps the current MB's filtering
@@ -283,8 +287,8 @@ DEV bool DbkSrcGranules::resolve_qp(uint32_t &i, int32_t *abort_word) const {
     const uint32_t q0 = (uint32_t)__builtin_amdgcn_readlane((int)i, 0), t0 = (uint32_t)__builtin_amdgcn_readlane((int)i, 32);
     const bool pc = (q0 >> 8) & 0x80u, pt = mby > 0 && ((t0 >> 8) & 0x80u);
     int ec = 0, et = 0;
-    if (pc && !row_entry_qp(rowq, mby, slice_qp, epoch, abort_word, &ec)) return false;
-    if (pt && !row_entry_qp(rowq, mby - 1, slice_qp, epoch, abort_word, &et)) return false;
+    if (pc && !row_entry_qp(rowq, mby, first_c, slice_qp, epoch, abort_word, &ec)) return false;
+    if (pt && !row_entry_qp(rowq, mby - 1, first_t, slice_qp, epoch, abort_word, &et)) return false;
     const bool mine = lane < 32 ? pc : pt;
     const int e = lane < 32 ? ec : et;
     if (mine && (lane & 31) == 0) i = (i & ~0xff00u) | ((uint32_t)e << 8);

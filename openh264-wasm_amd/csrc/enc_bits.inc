@@ -200,8 +200,8 @@ DEV int cavlc_lane_off(int lane) {
 }
 // ic / il / it: MbInfo dword `lane` (lanes 0..31) of the MB, its left and its top neighbour;
 // c[0..3]: the 32 bytes at the lane's block offset (whatever is stored there; used only if coded)
-// dqp: this MB's mb_qp_delta (written when it carries one)
-DEV void cavlc_code_mb(const CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDesc &D, int mbi, int mbx, int mby, int idr,
+// dqp: this MB's mb_qp_delta (written when it carries one); above: the MB above is in this MB's slice
+DEV void cavlc_code_mb(const CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDesc &D, int mbi, int mbx, bool above, int idr,
                        uint32_t ic, uint32_t il, uint32_t it, const uint64_t *c, int dqp, uint32_t bitg_epoch) {
     const int lane = threadIdx.x & 63;
     MbInfo &Cm = W.cur, &Lm = W.left, &Tm = W.top;
@@ -254,13 +254,13 @@ DEV void cavlc_code_mb(const CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDe
         const int ras = lane == 1 ? 0 : BLK2RAS[lane - 2], bx = ras & 3, by = ras >> 2;
         int na = -1, nb = -1;
         if (bx > 0) na = Cm.nnz[ras - 1]; else if (mbx > 0) na = Lm.nnz[ras + 3];
-        if (by > 0) nb = Cm.nnz[ras - 4]; else if (mby > 0) nb = Tm.nnz[ras + 12];
+        if (by > 0) nb = Cm.nnz[ras - 4]; else if (above) nb = Tm.nnz[ras + 12];
         nc = (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0));
     } else if (lane >= 20 && lane < 28) {
         const int pl = (lane - 20) >> 2, bb = (lane - 20) & 3, base = 16 + 4 * pl, bx = bb & 1, by = bb >> 1;
         int na = -1, nb = -1;
         if (bx > 0) na = Cm.nnz[base + bb - 1]; else if (mbx > 0) na = Lm.nnz[base + bb + 1];
-        if (by > 0) nb = Cm.nnz[base + bb - 2]; else if (mby > 0) nb = Tm.nnz[base + bb + 2];
+        if (by > 0) nb = Cm.nnz[base + bb - 2]; else if (above) nb = Tm.nnz[base + bb + 2];
         nc = (na >= 0 && nb >= 0) ? (na + nb + 1) >> 1 : (na >= 0 ? na : (nb >= 0 ? nb : 0));
     }
     int len = 0;
@@ -275,7 +275,7 @@ DEV void cavlc_code_mb(const CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDe
                 for (int blk = 0; blk < 16; blk++) {
                     const int ras = BLK2RAS[blk], bx = ras & 3, by = ras >> 2;
                     const int ma = bx > 0 ? Cm.i4mode[ras - 1] : (mbx > 0 ? Lm.i4mode[ras + 3] : -1);
-                    const int mb = by > 0 ? Cm.i4mode[ras - 4] : (mby > 0 ? Tm.i4mode[ras + 12] : -1);
+                    const int mb = by > 0 ? Cm.i4mode[ras - 4] : (above ? Tm.i4mode[ras + 12] : -1);
                     const int pm = (ma < 0 || mb < 0) ? 2 : min(ma, mb);
                     const int m = Cm.i4mode[ras];
                     if (m == pm) lb_put(b, 1, 1);
@@ -337,9 +337,16 @@ DEV void cavlc_code_mb(const CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDe
 // MB-row encoder publishes (96..127 of its 128; granule 127 follows its coefficient stores, which are
 // write-through (sc1), so sc1 loads of them after the granule see them -- MI355X_MICROARCH.md
 // inter-workgroup visibility, valid forms); the neighbours' records are granules too.
-DEV void cavlc_row(CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDesc &D, int mbw, int mby, int x0, int dx,
+DEV void cavlc_row(CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDesc &D, int mbw, int mbh, int mby, int x0, int dx,
                    uint32_t epoch, int32_t *abort_word, bool bitg) {
     const int lane = threadIdx.x & 63;
+    // a slice's first row (DESIGN.md §3.7): no nC / Intra4x4 mode context from the row above, which is not waited
+    // for, and the slice QP as the row's entry QP
+    const int nsl = uni(D.st->cur_slices), sl_row0 = slice_first_row(mbh, nsl, slice_of_row(mbh, nsl, mby));
+    const bool above = mby > sl_row0;
+    // the slice word of the row's MB records (MbInfo dword 31, MB_SLICE_FIRST: the slice's first MB; the loop-filter
+    // bits stay 0) is written here, off the MB rows' critical path
+    GLOBAL uint32_t *info32 = gbl((uint32_t *)D.info);
     {   // this wave's copy of the VLC tables (the other CAVLC wave writes identical values)
         const u32x4 *src = (const u32x4 *)&c_CAVLC_TABS;
         u32x4 *dst = (u32x4 *)&T;
@@ -353,8 +360,9 @@ DEV void cavlc_row(CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDesc &D, int
         const int mbi = mby * mbw + mbx;
         uint32_t ic = 0, il = 0, it = 0;
         if (!gran_wait(egr + (size_t)mbi * 128 + 96, 32, epoch, &ic, abort_word)) return;
+        if (lane == 0) info32[(size_t)mbi * 32 + 31] = (uint32_t)(sl_row0 * mbw);
         if (mbx > 0 && !gran_wait(egr + (size_t)(mbi - 1) * 128 + 96, 32, epoch, &il, abort_word)) return;
-        if (mby > 0 && !gran_wait(egr + (size_t)(mbi - mbw) * 128 + 96, 32, epoch, &it, abort_word)) return;
+        if (above && !gran_wait(egr + (size_t)(mbi - mbw) * 128 + 96, 32, epoch, &it, abort_word)) return;
         uint64_t c[4] = {0, 0, 0, 0};
         if (off >= 0) {
             const uint64_t *cp = (const uint64_t *)(coefb + (size_t)mbi * sizeof(MbCoef) + off);
@@ -369,11 +377,11 @@ DEV void cavlc_row(CavlcTabs &T, CavlcWaveLds &W, CONSTANT const EncDesc &D, int
         int dqp = 0;
         if (ty == MI_I16 || (ty != MI_PSKIP && cbp != 0)) {
             int pred = (int)((l0 >> 8) & 0x7f);
-            if ((mbx == 0 || ((l0 >> 8) & 0x80u)) && !row_entry_qp(gbl((const uint64_t *)D.rowq), mby, uni(D.st->cur_qp), epoch, abort_word, &pred))
+            if ((mbx == 0 || ((l0 >> 8) & 0x80u)) && !row_entry_qp(gbl((const uint64_t *)D.rowq), mby, !above, uni(D.st->cur_qp), epoch, abort_word, &pred))
                 return;
             dqp = (((int)((c0 >> 8) & 0x7f) - pred + 26 + 52) % 52) - 26;
         }
-        cavlc_code_mb(T, W, D, mbi, mbx, mby, idr, ic, il, it, c, dqp, bitg ? epoch : 0u);
+        cavlc_code_mb(T, W, D, mbi, mbx, above, idr, ic, il, it, c, dqp, bitg ? epoch : 0u);
     }
 }
 
@@ -388,6 +396,7 @@ struct BeginLaunch {
     size_t src_stride;
     int src_vec;                 // 16-byte source loads (w % 16 == 0, aligned frames)
     uint32_t *done;              // per stream: workgroups finished (the last one runs the picture init, then zeroes it)
+    int slices;                  // slices per picture of this frame (h264mi_enc_set_slices), latched into EncState::cur_slices
 };
 DEV int rc_qstep2qp(int32_t qstep) {  // RcConvertQStep2Qp (thresholds c_RC_QP_THR, h264mi_dev.h)
     if (qstep < 64) return 0;
@@ -413,13 +422,16 @@ DEV void rc_init_vgop(RcState &r) {  // RcInitVGop with bFixRCOverShoot
     r.remaining_weights = r.gop_num * 2000;  // WEIGHT_MULTIPLY
 }
 // the begin logic of one stream (one thread), once its frame complexity is known
-DEV void enc_begin_stream(EncState *st, uint32_t *gomc) {
+DEV void enc_begin_stream(EncState *st, uint32_t *gomc, int slices) {
     RcState &r = st->rc;
     // a frame whose kernels reported an error (wavefront timeout, overflow) produced no output, so
     // the decoder never saw the picture the encoder now holds as its reference: restart with an IDR
     const int idr = st->first || st->force_idr || st->err != 0;
     st->epoch = st->epoch + 1;
     st->err = 0;
+    // the frame's slice count (the host's value when the frame step was issued, validated by h264mi_enc_set_slices):
+    // latched here, so that every kernel of the frame reads one value whatever the setter does meanwhile
+    st->cur_slices = slices < 1 ? 1 : slices;
     // frame skip (func 589's check + CheckFrameSkipBasedMaxbr, func 1258): the update's flag, else the buffer
     // above its size with the run of skipped frames at most (round(fullness / bits per frame) + 1) >> 1
     int skip = 0;
@@ -559,7 +571,7 @@ __global__ __launch_bounds__(256) void enc_begin_kernel(BeginLaunch a) {
     if (tid == 0) {
         const uint32_t n = __hip_atomic_fetch_add(a.done + s, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         if (n + 1 == (uint32_t)a.K) {
-            enc_begin_stream(st, D.gomc);
+            enc_begin_stream(st, D.gomc, a.slices);
             __hip_atomic_store(a.done + s, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -1001,6 +1013,325 @@ DEV void enc_pack_block(const PackLaunch &a, int stream) {
         }
     }
 }
+// The same for a picture of more than one slice (DESIGN.md §3.7): the picture's slices one after the other, each
+// through (1)-(3) into its own NAL unit. A function and a kernel of its own: the loop around the per-thread arrays
+// costs registers (151 VGPRs against 117), which the single-slice pack above -- the default, kept as it was --
+// must not pay (it has to fit beside the decoder's resident waves, see PACK_THREADS).
+DEV void enc_pack_block_slices(const PackLaunch &a, int stream) {
+    __shared__ uint32_t s_hdr[8];
+    __shared__ int s_hdrlen;
+    __shared__ int s_w[PACK_WAVES];
+    __shared__ int s_rb[256];     // macroblock_layer() bits per MB row (GOM rate control)
+    __shared__ int s_rc[2];       // a frame was coded, mean row bits
+    const int tid = threadIdx.x;
+    const EncDesc &D = a.desc[stream];
+    EncState *st = D.st;
+    const bool inject_overflow = st->inject_err == 3;  // read by every thread before thread 0 clears it
+    if (st->cur_skip) {  // frame skipped by the rate control (enc_begin_kernel): no output
+        if (tid == 0) st->nal_bytes = 0;
+        return;
+    }
+    const int nmb = a.mbw * a.mbh;
+    // (uniform values in SGPRs: the slice loop's control flow is then scalar, which keeps its registers down)
+    const int idr = uni(st->cur_idr), qp = uni(st->cur_qp), nsl = uni(st->cur_slices);
+    uint32_t *rb = D.rbsp;
+    for (int r = tid; r < a.mbh; r += PACK_THREADS) s_rb[r] = 0;
+    // the access unit: [SPS PPS] then the picture's nsl slice NAL units back to back (DESIGN.md §3.7), each with its
+    // own header, mb_skip_run chain, stop bit, emulation prevention and start code; ooff: where the next one starts
+    uint8_t *out = D.nal;
+    int hdr = 0;
+    if (idr) {
+        for (int i = tid; i < st->sps_bytes; i += PACK_THREADS) out[i] = st->sps[i];
+        for (int i = tid; i < st->pps_bytes; i += PACK_THREADS) out[st->sps_bytes + i] = st->pps[i];
+        hdr = st->sps_bytes + st->pps_bytes;
+    }
+    int ooff = hdr;
+    constexpr int PACK_MBT = 32;
+#pragma unroll 1
+    for (int sk = 0; sk < nsl; sk++) {
+        // the slice's macroblocks [m0, m1): whole MB rows
+        const int m0 = slice_first_row(a.mbh, nsl, sk) * a.mbw, m1 = slice_first_row(a.mbh, nsl, sk + 1) * a.mbw;
+        // ---- slice header (7.3.3) into s_hdr
+        if (tid == 0) {
+            LBits b;
+            lb_init(b, s_hdr);
+            // OpenH264's slice header (WelsSliceHeaderWrite, h264.wasm func 1148; oracle h264o_enc_encode):
+            // slice_type 2 / 0, 15-bit frame_num, no POC (type 2); P: num_ref_idx override to 1 active,
+            // explicit reordering {idc 0, abs_diff_pic_num_minus1 0, idc 3}, marking flag 0; IDR: {0, 0}
+            lb_ue(b, (uint32_t)m0);  // first_mb_in_slice
+            lb_ue(b, idr ? 2 : 0);
+            lb_ue(b, 0);
+            lb_put(b, (uint32_t)st->frame_num, 15);
+            if (idr) {
+                lb_ue(b, (uint32_t)st->idr_pic_id);
+                lb_put(b, 0, 2);
+            } else {
+                lb_put(b, 0x3, 2);      // num_ref_idx_active_override_flag 1, num_ref_idx_l0_active_minus1 ue(0)
+                lb_put(b, 0x1C8, 9);    // ref_pic_list_modification_flag_l0 1, ue(0), ue(0), ue(3) = 00100,
+                                        // adaptive_ref_pic_marking_mode_flag 0
+            }
+            lb_se(b, qp - 26);
+            lb_ue(b, 0); lb_se(b, 0); lb_se(b, 0);
+            lb_flush(b);
+            s_hdrlen = b.total;
+        }
+        // ---- (1) contiguous MB range per thread (a multiple of 4 MBs): up to PACK_MBT lengths per thread
+        // in registers from 16-byte loads (one round trip); larger pictures re-read the tail of the range.
+        // The ranges are cut on a grid of 4 MBs from ib (the loads' alignment): thread 0's starts at m0, which
+        // need not lie on it, so Lr[j] is MB ib + j and the entries outside [i0, i1) stay 0
+        const int mg = m0 & ~3, per = ((m1 - mg + PACK_THREADS - 1) / PACK_THREADS + 3) & ~3;
+        const int ib = mg + tid * per, i0 = min(m1, max(m0, ib)), i1 = max(i0, min(m1, ib + per));
+        uint32_t Lr[PACK_MBT];
+#pragma unroll
+        for (int j = 0; j < PACK_MBT; j += 4) {
+            u32x4 v = {0, 0, 0, 0};
+            if (ib + j + 3 < i1) v = *(const u32x4 *)(D.mblen + ib + j);
+            else if (ib + j < i1) {
+                v.x = D.mblen[ib + j];
+                if (ib + j + 1 < i1) v.y = D.mblen[ib + j + 1];
+                if (ib + j + 2 < i1) v.z = D.mblen[ib + j + 2];
+            }
+            Lr[j] = v.x; Lr[j + 1] = v.y; Lr[j + 2] = v.z; Lr[j + 3] = v.w;
+        }
+        if (ib < i0) {  // the slice before this one ends inside the first group (i0 - ib <= 3)
+            Lr[0] = 0;
+            if (ib + 1 < i0) Lr[1] = 0;
+            if (ib + 2 < i0) Lr[2] = 0;
+        }
+        int my_last = -1;
+#pragma unroll
+        for (int j = 0; j < PACK_MBT; j++) if (Lr[j]) my_last = ib + j;
+        for (int i = ib + PACK_MBT; i < i1; i++) if (D.mblen[i]) my_last = i;
+        __syncthreads();  // s_rb cleared, s_hdrlen of this slice written
+        {   // row sums of the MB bit counts (mb_skip_run codes excluded), flushed at row changes
+            int r = i0 < m1 ? i0 / a.mbw : 0, xe = (r + 1) * a.mbw, acc = 0;
+            auto add = [&](int i, uint32_t l) {
+                if (i >= xe) { if (acc) atomicAdd(&s_rb[r], acc); acc = 0; r++; xe += a.mbw; }
+                acc += (int)l;
+            };
+#pragma unroll
+            for (int j = 0; j < PACK_MBT; j++)  // constant indices into Lr: a variable one would put it in scratch
+                if (ib + j < i1) add(ib + j, Lr[j]);  // (an entry before i0 is 0: it adds nothing)
+            for (int i = ib + PACK_MBT; i < i1; i++) add(i, D.mblen[i]);
+            if (acc) atomicAdd(&s_rb[r], acc);
+        }
+        // a skip run never crosses a slice edge: the slice's first run counts from m0, its trailing run ends at m1 - 1
+        int last_coded;
+        const int prev = max(m0 - 1, block_excl_scan<true>(my_last, s_w, &last_coded));  // last coded MB of the slice before i0
+        last_coded = max(m0 - 1, last_coded);
+        int mybits = 0;
+        {
+            int p = prev;
+#pragma unroll
+            for (int j = 0; j < PACK_MBT; j++) {
+                if (!Lr[j]) continue;
+                mybits += (int)Lr[j] + (idr ? 0 : ue_len((uint32_t)(ib + j - p - 1)));
+                p = ib + j;
+            }
+            for (int i = ib + PACK_MBT; i < i1; i++) {
+                const uint32_t l = D.mblen[i];
+                if (!l) continue;
+                mybits += (int)l + (idr ? 0 : ue_len((uint32_t)(i - p - 1)));
+                p = i;
+            }
+        }
+        int body;
+        const int base = s_hdrlen + block_excl_scan<false>(mybits, s_w, &body);
+        const int body_end = s_hdrlen + body;
+        const int trail = idr ? 0 : m1 - 1 - last_coded;
+        const int total_bits = uni(body_end + (trail > 0 ? ue_len((uint32_t)trail) : 0) + 1);
+        const int rbsp_bytes = (total_bits + 7) >> 3;
+        const int nd = (rbsp_bytes + 3) >> 2;
+        // RBSP overflow, a NAL unit that may not fit the stream's NAL buffer behind the ones before it (at most one
+        // emulation prevention byte per two RBSP bytes), or the test hook's code 3, in any slice: the whole frame fails
+        // and publishes nothing -- the size word every consumer reads (enc_fetch, copy_nals, ring_publish_kernel) becomes 0
+        if (nd + 2 > D.rbsp_cap || ooff + 5 + rbsp_bytes + (rbsp_bytes >> 1) + 1 > D.nal_cap || inject_overflow) {
+            if (tid == 0) { st->err = 2; st->nal_bytes = 0; st->inject_err = 0; }
+            return;
+        }
+        for (int i = tid; i < nd + 2; i += PACK_THREADS) rb[i] = 0;
+        __syncthreads();
+        // ---- (2) RBSP bits: the first four dwords of 4 MBs of the range loaded together per batch (a P MB
+        // rarely needs more than 128 bits); further dwords of longer MBs are loaded as they are reached
+        {
+            auto put_mb = [&](int i, uint32_t l, int pos, u32x4 a0) {
+                const uint32_t *src = D.mbbits + (size_t)i * H264MI_MB_SLOT_DWORDS;
+                const int n = (int)((l + 31) >> 5);
+                for (int k = 0; k < n; k++) {
+                    const int nb = (k == n - 1 && (l & 31)) ? (int)(l & 31) : 32;
+                    const uint32_t v = k == 0 ? a0.x : k == 1 ? a0.y : k == 2 ? a0.z : k == 3 ? a0.w : src[k];
+                    bits_or(rb, pos + 32 * k, v >> (32 - nb), nb);
+                }
+            };
+            int p = prev, pos = base;
+#pragma unroll
+            for (int j0 = 0; j0 < PACK_MBT; j0 += 4) {
+                u32x4 w0[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    w0[j] = Lr[j0 + j] ? *(const u32x4 *)(D.mbbits + (size_t)(ib + j0 + j) * H264MI_MB_SLOT_DWORDS) : u32x4{0, 0, 0, 0};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t l = Lr[j0 + j];
+                    if (!l) continue;
+                    const int i = ib + j0 + j;
+                    if (!idr) { const uint32_t run = (uint32_t)(i - p - 1); bits_ue(rb, pos, run); pos += ue_len(run); }
+                    put_mb(i, l, pos, w0[j]);
+                    pos += (int)l;
+                    p = i;
+                }
+            }
+            for (int i = ib + PACK_MBT; i < i1; i++) {
+                const uint32_t l = D.mblen[i];
+                if (!l) continue;
+                if (!idr) { const uint32_t run = (uint32_t)(i - p - 1); bits_ue(rb, pos, run); pos += ue_len(run); }
+                put_mb(i, l, pos, *(const u32x4 *)(D.mbbits + (size_t)i * H264MI_MB_SLOT_DWORDS));
+                pos += (int)l;
+                p = i;
+            }
+        }
+        if (tid == 0) {
+            const int nh = (s_hdrlen + 31) >> 5;
+            for (int k = 0; k < nh; k++) {
+                const int nb = (k == nh - 1 && (s_hdrlen & 31)) ? (s_hdrlen & 31) : 32;
+                bits_or(rb, 32 * k, s_hdr[k] >> (32 - nb), nb);
+            }
+            int pos = body_end;
+            if (trail > 0) { bits_ue(rb, pos, (uint32_t)trail); pos += ue_len((uint32_t)trail); }
+            bits_or(rb, pos, 1, 1);  // rbsp_stop_one_bit
+        }
+        __syncthreads();
+        // ---- (3) NAL assembly at ooff: start code + header + EP(RBSP)
+        if (tid == 0) {
+            out[ooff] = 0; out[ooff + 1] = 0; out[ooff + 2] = 0; out[ooff + 3] = 1;
+            out[ooff + 4] = (uint8_t)((3 << 5) | (idr ? 5 : 1));
+        }
+        const int obase = ooff + 5;
+        int carry_nz = -1, carry_ins = 0;  // over earlier chunks: last non-zero RBSP byte, insertions
+        constexpr int EPB = 64;            // bytes per thread per chunk
+        for (int c0 = 0; c0 < rbsp_bytes; c0 += EPB * PACK_THREADS) {
+            const int b0 = c0 + EPB * tid;
+            uint32_t wv[EPB / 4];
+#pragma unroll
+            for (int k = 0; k < EPB / 4; k++) {
+                const int wi = (b0 >> 2) + k;
+                wv[k] = b0 + 4 * k < rbsp_bytes ? __hip_atomic_load(&rb[wi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+            }
+            const int nb = max(0, min(EPB, rbsp_bytes - b0));
+            int my_nz = -1;
+#pragma unroll
+            for (int k = 0; k < EPB; k++)
+                if (k < nb && ((wv[k >> 2] >> (24 - 8 * (k & 3))) & 255)) my_nz = b0 + k;
+            int chunk_nz, chunk_ins;
+            const int pnz = max(carry_nz, block_excl_scan<true>(my_nz, s_w, &chunk_nz));
+            // zeros immediately before b0 (the NAL header byte before the RBSP is non-zero)
+            int z = pnz >= 0 ? b0 - 1 - pnz : b0;
+            uint64_t insm = 0;  // bit k: insert 0x03 before byte k
+            int z2 = z;
+#pragma unroll
+            for (int k = 0; k < EPB; k++) {
+                const int byte = (int)((wv[k >> 2] >> (24 - 8 * (k & 3))) & 255);
+                if (k < nb && byte <= 3 && z2 >= 2 && !(z2 & 1)) insm |= 1ull << k;
+                z2 = byte == 0 ? z2 + 1 : 0;
+            }
+            const int my_ins = __popcll(insm);
+            const int before = carry_ins + block_excl_scan<false>(my_ins, s_w, &chunk_ins);
+            int o = obase + b0 + before;
+            for (int k = 0; k < nb; k++) {
+                if ((insm >> k) & 1) out[o++] = 3;
+                out[o++] = (uint8_t)((wv[k >> 2] >> (24 - 8 * (k & 3))) & 255);
+            }
+            carry_nz = max(carry_nz, chunk_nz);
+            carry_ins += chunk_ins;
+        }
+        // the next slice's NAL unit follows this one; its RBSP reuses rb (every thread has loaded its bytes of this one
+        // before the scans above, and zeroes rb only behind the next slice's)
+        ooff = uni(obase + rbsp_bytes + carry_ins);
+    }
+    // the average QPY of the coded macroblocks (RcUpdatePictureQpBits: iTotalQpSlice / iTotalMbSlice, func 1218):
+    // a record flagged 0x80 is a non-carrier before its row's first carrier -- its QPY is the row's entry QP,
+    // the slice QP in a slice's first row
+    int sq_qp = 0, n_mb = 0;
+    if (!idr) {
+        const int per = ((nmb + PACK_THREADS - 1) / PACK_THREADS + 3) & ~3, i0 = min(nmb, tid * per), i1 = min(nmb, i0 + per);
+        int myq = 0, myn = 0;
+        for (int i = i0; i < i1; i++) {
+            if (!D.mblen[i]) continue;
+            const uint32_t qb = (((const uint32_t *)D.info)[(size_t)i * 32] >> 8) & 0xffu;
+            const int row = i / a.mbw;
+            myq += (qb & 0x80u) ? ((row == 0 || (nsl > 1 && slice_row_first(a.mbh, nsl, row))) ? qp : (int)(uint32_t)D.rowq[row]) : (int)qb;
+            myn++;
+        }
+        (void)block_excl_scan<false>(myq, s_w, &sq_qp);
+        (void)block_excl_scan<false>(myn, s_w, &n_mb);
+    }
+    __syncthreads();  // every thread is past reading st (the scans above), s_rb complete
+    if (tid == 0) {
+        if (st->inject_err) { st->err = st->inject_err; st->inject_err = 0; }  // test hook: as an RBSP overflow
+        const int nbytes = ooff;  // parameter sets + every slice NAL unit
+        // a failed frame publishes nothing: every consumer of the size word (enc_fetch, copy_nals,
+        // ring_publish_kernel) sees 0 bytes, and the next frame is an IDR (enc_begin_kernel)
+        st->nal_bytes = st->err ? 0 : nbytes;
+        s_rc[0] = -1;
+        if (!st->err) {  // a failed frame: no output (enc_fetch), no frame_num / POC / RC advance
+            // WelsRcPictureInfoUpdateGom (func 1218; oracle rc_picture_update) on the slice NAL's bytes (the
+            // parameter sets are another layer): the average QP, the R-Q model, the VGOP budget, the VBV skip check
+            RcState &r = st->rc;
+            const int bits = (nbytes - hdr) << 3;
+            const int avg = (!idr && n_mb > 0) ? (n_mb * 50 + sq_qp * 100) / (n_mb * 100) : qp;
+            r.last_qscale = avg;
+            r.avg_qp = avg;
+            if (!idr) {  // RcUpdateFrameComplexity (func 676)
+                const int q = c_RC_QSTEP[avg];
+                if (r.pframe_num == 0) {
+                    r.frame_cmplx_mean = (int64_t)(int32_t)(uint32_t)(uint64_t)r.frame_cmplx;
+                    r.linear_cmplx = (int64_t)bits * q;
+                } else {
+                    r.frame_cmplx_mean = (r.frame_cmplx * 20 + r.frame_cmplx_mean * 80 + 50) / 100;
+                    r.linear_cmplx = (r.linear_cmplx * 80 + (int64_t)q * bits * 20 + 50) / 100;
+                }
+                r.pframe_num = (r.pframe_num >= 254 ? 254 : r.pframe_num) + 1;
+            } else {     // RcUpdateIntraComplexity
+                const int64_t ic = (int64_t)c_RC_QSTEP[avg] * bits;
+                if (r.idr_num == 0) { r.intra_cmplx_mean = r.frame_cmplx; r.intra_cmplx = ic; }
+                else {
+                    r.intra_cmplx = (ic * 20 + r.intra_cmplx * 80 + 50) / 100;
+                    r.intra_cmplx_mean = (r.frame_cmplx * 20 + r.intra_cmplx_mean * 80 + 50) / 100;
+                }
+                r.intra_mb_count = r.nmb;
+                r.idr_num = (r.idr_num >= 254 ? 254 : r.idr_num) + 1;
+            }
+            r.remaining -= bits;
+            if (r.skip_en) {  // RcVBufferCalculationSkip
+#pragma clang fp contract(off)
+                r.fullness += bits - r.bpf;
+                int64_t pred = 0;
+                if (r.frame_coded_in_vgop <= 6) pred = (int64_t)(7 - r.frame_coded_in_vgop) * r.min_bits_tl;
+                const double inc = ((double)(pred - r.remaining) * 100.0) / (double)(r.bpf << 3) + -5.0;
+                if ((r.fullness > r.buffer_size_skip && avg > r.skip_qp) || inc > 10.0) r.skip_flag = 1;
+            }
+            r.frame_coded_in_vgop++;
+            st->frame_num = (st->frame_num + 1) & 0x7fff;
+            st->poc += 2;
+            int64_t sum = 0;
+            for (int rr = 0; rr < a.mbh; rr++) sum += s_rb[rr];
+            s_rc[0] = 1;
+            s_rc[1] = (int)(sum / a.mbh);
+        }
+    }
+    __syncthreads();
+    // the next frame's MB-row QP plan (oracle rc_plan_rows / h264o_rc_row_delta)
+    if (s_rc[0] >= 0) {
+        const int mean = s_rc[1];
+        for (int r = tid; r < a.mbh; r += PACK_THREADS) {
+            const int b = s_rb[r];
+            const int dr = mean <= 0 ? 0 : (b > 2 * mean ? 2 : (4 * (int64_t)b > 5 * (int64_t)mean ? 1 : (2 * b < mean ? -1 : 0)));
+            D.rowbits[r] = b;
+            D.rowqp[r] = dr;  // the row's offset; enc_mb_kernel clips frame QP + offset to the frame's window
+        }
+    }
+}
 __global__ __launch_bounds__(PACK_THREADS) void enc_pack_kernel(PackLaunch a) { enc_pack_block(a, blockIdx.x); }
+__global__ __launch_bounds__(PACK_THREADS) void enc_pack_slices_kernel(PackLaunch a) { enc_pack_block_slices(a, blockIdx.x); }
 
 }  // namespace h264mi

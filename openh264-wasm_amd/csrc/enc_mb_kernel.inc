@@ -731,11 +731,14 @@ void enc_mb_kernel(EncLaunch a) {
             CONSTANT const DbkDesc &DD = cst(a.dbk)[dsi];
             const DbkLaunch dl{a.mbw, a.mbh, a.S, a.dbk, nullptr, a.dprof};
             CONSTANT const EncDesc &DE = cst(a.desc)[dsi];
+            // the filter crosses slice edges (disable_deblocking_filter_idc 0); only the QPY entering a row knows them
+            const int nsl = uni(DE.st->cur_slices);
             deblock_row(SH.k.d, dl, DD, dby, DbkSrcGranules{gbl((const uint64_t *)DD.src_gran), a.mbw, dby, (uint32_t)uni((int)*DD.epoch),
-                                                            gbl((const uint64_t *)DE.rowq), uni(DE.st->cur_qp)});
+                                                            gbl((const uint64_t *)DE.rowq), uni(DE.st->cur_qp),
+                                                            slice_row_first(a.mbh, nsl, dby), dby > 0 && slice_row_first(a.mbh, nsl, dby - 1)});
         } else {
             CONSTANT const EncDesc &D = cst(a.desc)[dsi];
-            cavlc_row(SH.k.T, SH.k.w[wv - 1], D, a.mbw, dby, wv - 1, 2, (uint32_t)uni((int)D.st->epoch), &D.st->err, a.gomr > 0);
+            cavlc_row(SH.k.T, SH.k.w[wv - 1], D, a.mbw, a.mbh, dby, wv - 1, 2, (uint32_t)uni((int)D.st->epoch), &D.st->err, a.gomr > 0);
         }
         tl_end();
         return;
@@ -775,6 +778,10 @@ void enc_mb_kernel(EncLaunch a) {
     // entering the row for the MBs before the row's first carrier (record flag 0x80, resolved by the
     // deblocking row and the CAVLC from rowq), the row QP after it
     const int idr = uni(st->cur_idr), slice_qp = uni(st->cur_qp);
+    // slices of whole MB rows (DESIGN.md §3.7): nothing above a slice's first row is available (7.4.3) -- no wait on
+    // the row above, no neighbour from it -- and that row is entered at the slice QP. Uniform, decided once per row;
+    // the picture's row 0 is the single-slice case of it.
+    const int sl_row0 = slice_first_row(a.mbh, uni(st->cur_slices), slice_of_row(a.mbh, uni(st->cur_slices), mby));
     // an IDR is coded at the frame QP (OpenH264 turns the GOM QP off for I slices in RC_BITRATE_MODE, h264.wasm
     // func 1226 766730-766775); a P row at the frame QP + its planned offset inside the frame's window
     int32_t *abort_word = &st->err;
@@ -806,7 +813,12 @@ void enc_mb_kernel(EncLaunch a) {
     const int Y0 = mby * 16 - 24, Y = mby * 16;
     // global-address-space views of everything the wavefront touches (no flat ops: see h264mi_dev.h)
     GLOBAL const uint8_t *srcY = gbl(a.src_base) + (size_t)sidx * a.src_stride, *srcU = srcY + (size_t)w * h, *srcV = srcU + (size_t)(w / 2) * (h / 2);
-    GLOBAL uint64_t *grow_prev = gbl(D.gran) + (size_t)(mby > 0 ? mby - 1 : 0) * mbw * H264MI_GRANULES_PER_MB;
+    // The predicate `above` rides on a value that is live across the MB loop anyway -- the row above's granules, null
+    // when there is no such row -- so it costs no register of its own in a kernel that spills at its occupancy target
+    // (see XF above). WARNING: grow_prev is null in a slice's first row: every use of it must stay behind `above`
+    // (an unguarded grow_prev + ... there is a GPU fault, not a harmless read of row 0 as it once was).
+    GLOBAL uint64_t *const grow_prev = mby > sl_row0 ? gbl(D.gran) + (size_t)(mby - 1) * mbw * H264MI_GRANULES_PER_MB : nullptr;
+#define above (grow_prev != nullptr)
     GLOBAL uint64_t *grow = gbl(D.gran) + (size_t)mby * mbw * H264MI_GRANULES_PER_MB;
     GLOBAL uint64_t *egr = gbl(D.egran);
     GLOBAL uint32_t *info32 = gbl((uint32_t *)D.info);
@@ -974,8 +986,8 @@ void enc_mb_kernel(EncLaunch a) {
                 stamp(20 + wv, t_prev);
             }
         };
-        if (wv != 0 || mby == 0) commit_here();
-        if (mby > 0) {  // wave 0 polls, the workgroup follows through LDS
+        if (wv != 0 || !above) commit_here();
+        if (above) {  // wave 0 polls, the workgroup follows through LDS
             if (wv == 0) {
                 bool ok = true;
                 if (idr) {
@@ -1021,7 +1033,7 @@ void enc_mb_kernel(EncLaunch a) {
         if (mbx + 1 < mbw && (idr || !H264MI_ENC_LATE_PF)) issue_prefetch(mbx + 1);
         if (!vsrc && mbx > 0) load_src_bytes(mbx);
         // ---- 3. neighbour pixel context from the granule ring and the left MB
-        const bool has_top = mby > 0, has_left = mbx > 0, has_tr = mby > 0 && mbx + 1 < mbw, has_tl = has_top && has_left;
+        const bool has_top = above, has_left = mbx > 0, has_tr = above && mbx + 1 < mbw, has_tl = has_top && has_left;
         const int nbf = (int)has_left | ((int)has_top << 1) | ((int)has_tl << 2) | ((int)has_tr << 3);  // OpenH264's MB flags
         const uint32_t *PB = S.gp[mbx % 3], *PC = S.gp[(mbx + 1) % 3], *PD = S.gp[(mbx + 2) % 3];
         // top row (+ top-left, top-right) luma and chroma samples from the granules. all_waves: every wave
@@ -1049,7 +1061,7 @@ void enc_mb_kernel(EncLaunch a) {
         // top-left samples of (mbx-1, mby-1) (granules 3, 5, 7), published with their outputs; tr = true: the top-right
         // samples, granules 0..3 of (mbx+1, mby-1) (an intra MB's Intra4x4 search). false: the frame is aborting.
         auto poll_above = [&](bool tr) -> bool {
-            if (mby == 0 || (tr && !has_tr)) return true;
+            if (!above || (tr && !has_tr)) return true;
             if (wv == 0 && (tr || !H264MI_ENC_ST2PF || st2_stale)) {  // (ST2PF: published ones were taken at step 1)
 #ifndef H264MI_DIAG_NO_G9  // timing diagnostic only: granule 9 not polled (wrong Intra4x4 mode prediction in P slices)
                 const bool need = tr ? lane < 4 : (lane < 8 || lane == 9 || (mbx > 0 && (lane == 19 || lane == 21 || lane == 23)));
@@ -1487,7 +1499,7 @@ void enc_mb_kernel(EncLaunch a) {
             commit_prefetch(mbx + 1);
             stamp(20 + wv, t_prev);
         }
-        if (!idr && wv == 0 && mby > 0 && mbx + 1 < mbw) {  // the next MB's row-above granules (checked, polled if stale, there)
+        if (!idr && wv == 0 && above && mbx + 1 < mbw) {  // the next MB's row-above granules (checked, polled if stale, there)
             const bool need = p_need1(lane, mbx + 2 < mbw);
 #if H264MI_ENC_ST2PF
             st2_pf = st2_load(mbx + 1);  // first: the next MB's stage-1 wait (on top_pf) then covers it
@@ -1520,7 +1532,7 @@ void enc_mb_kernel(EncLaunch a) {
             if (lane == 6) v = refw;
             if (lane >= 7 && lane < 13) v = skip ? 0u : ld;
             if (lane == 13) v = (uint32_t)(uint16_t)mvdx | ((uint32_t)(uint16_t)mvdy << 16);
-            info32[(size_t)mbi * 32 + lane] = v;
+            if (lane < 31) info32[(size_t)mbi * 32 + lane] = v;  // (31, the slice word: the row's CAVLC waves, cavlc_row)
             if (lane < 31) gran_store(egr + (size_t)mbi * 128 + 96 + lane, epoch, v);  // -> deblocking row, CAVLC (31: wave 2)
         }
         if (wv == H264MI_ENC_REC_WAVE) stamp(36, t_prev);
@@ -1601,12 +1613,13 @@ void enc_mb_kernel(EncLaunch a) {
     // a row without an mb_qp_delta carrier hands on the QP it entered with
     if (!row_carried && mby + 1 < a.mbh && wv == 0) {
         int eq;
-        if (row_entry_qp(rowq, mby, slice_qp, epoch, abort_word, &eq) && lane == 0) gran_store(rowq + mby + 1, epoch, (uint32_t)eq);
+        if (row_entry_qp(rowq, mby, !above, slice_qp, epoch, abort_word, &eq) && lane == 0) gran_store(rowq + mby + 1, epoch, (uint32_t)eq);
     }
     if (prof && tid < 40) atomicAdd((unsigned long long *)&a.prof[tid < 16 ? tid : tid + 16], (unsigned long long)s_prof[tid]);
     tl_end();
 #undef tid
 #undef lane
+#undef above
 #if H264MI_ENC_XF_LDS
 #undef XF
 #endif

@@ -149,11 +149,20 @@ __global__ __launch_bounds__(PT_Q) void enc_post_kernel(PostLaunch a) {
     const int r = b - a.pk.S, per = a.gx * a.gy, z = r / per, yx = r - z * per, y = yx / a.gx;
     ref_planes_block(a.pl, yx - y * a.gx, y, z, a.gx);
 }
-static int launch_enc_post(const PackLaunch &pk, int cw, int ch, const PlanesDesc *pd, hipStream_t st) {
+// the same with the multi-slice pack (enc_pack_block_slices): a kernel of its own, so that its registers do not
+// count against the default single-slice step
+__global__ __launch_bounds__(PT_Q) void enc_post_slices_kernel(PostLaunch a) {
+    const int b = (int)blockIdx.x;
+    if (b < a.pk.S) { enc_pack_block_slices(a.pk, b); return; }
+    const int r = b - a.pk.S, per = a.gx * a.gy, z = r / per, yx = r - z * per, y = yx / a.gx;
+    ref_planes_block(a.pl, yx - y * a.gx, y, z, a.gx);
+}
+static int launch_enc_post(const PackLaunch &pk, int cw, int ch, const PlanesDesc *pd, hipStream_t st, bool slices) {
     int gx, gy, ystrips;
     ref_planes_grid(cw, ch, gx, gy, ystrips);
     const PostLaunch pl{pk, PlanesLaunch{pk.S, cw, ch, pd, ystrips}, gx, gy};
-    hipLaunchKernelGGL(enc_post_kernel, dim3(pk.S + gx * gy * pk.S), dim3(PT_Q), 0, st, pl);
+    if (slices) hipLaunchKernelGGL(enc_post_slices_kernel, dim3(pk.S + gx * gy * pk.S), dim3(PT_Q), 0, st, pl);
+    else hipLaunchKernelGGL(enc_post_kernel, dim3(pk.S + gx * gy * pk.S), dim3(PT_Q), 0, st, pl);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -403,11 +403,23 @@ template <class P> DEV bool gran_poll(P g, bool need, uint32_t epoch, uint64_t &
     }
 }
 
-// QPY entering MB row r of an encoder frame: the slice QP for row 0, else the value
-// row r - 1 publishes in rowq[r] (its row QP as soon as it codes an MB carrying mb_qp_delta, or the
-// QPY it entered with if it codes none). Wave-uniform; false on abort/timeout.
-template <class P> DEV bool row_entry_qp(P rowq, int r, int slice_qp, uint32_t epoch, int32_t *abort_word, int *qp) {
-    if (r == 0) { *qp = slice_qp; return true; }
+// ---------------------------------------------------------------- encoder slices
+// A picture coded as n slices of whole MB rows (1 <= n <= min(mbh, H264MI_MAX_SLICES)): slice k starts at MB
+// row (k * mbh) / n and ends where slice k + 1 starts; slice_first_row(mbh, n, n) == mbh. The one rule the MB
+// rows, the CAVLC rows, the pack and the host (h264mi_slice_first_row) share.
+__host__ __device__ inline int slice_first_row(int mbh, int n, int k) { return (k * mbh) / n; }
+// the slice MB row `row` lies in: the largest k with slice_first_row(k) <= row
+__host__ __device__ inline int slice_of_row(int mbh, int n, int row) { return ((row + 1) * n - 1) / mbh; }
+// the row is its slice's first: nothing above it is available (7.4.3), and it is entered at the slice QP
+__host__ __device__ inline bool slice_row_first(int mbh, int n, int row) {
+    return slice_first_row(mbh, n, slice_of_row(mbh, n, row)) == row;
+}
+
+// QPY entering MB row r of an encoder frame: the slice QP for a slice's first row (first),
+// else the value row r - 1 publishes in rowq[r] (its row QP as soon as it codes an MB carrying mb_qp_delta, or
+// the QPY it entered with if it codes none). Wave-uniform; false on abort/timeout.
+template <class P> DEV bool row_entry_qp(P rowq, int r, bool first, int slice_qp, uint32_t epoch, int32_t *abort_word, int *qp) {
+    if (first) { *qp = slice_qp; return true; }
     uint32_t v = 0;
     if (!gran_wait(rowq + r, 1, epoch, &v, abort_word)) return false;
     *qp = __builtin_amdgcn_readfirstlane((int)v);

@@ -35,7 +35,7 @@ struct MbInfo {
     int16_t mvd[2];      // encoder P16x16 mvd
     uint8_t sub[4];      // decoder P8x8 sub_mb_type
     int16_t mv[16][2];   // raster 4x4, quarter-pel
-    int32_t pad2;        // decoder: slice identity + loop-filter parameters (MB_SLICE_*); encoder 0
+    int32_t pad2;        // slice identity + loop-filter parameters (MB_SLICE_*); encoder: the slice's first MB
 };
 static_assert(sizeof(MbInfo) == 128, "MbInfo layout");
 
@@ -95,6 +95,8 @@ struct EncState {
     int32_t sps_bytes, pps_bytes;
     uint8_t sps[64], pps[32];
     RcState rc;
+    int32_t cur_slices;    // slices of the frame being coded (h264mi_enc_set_slices), latched from the frame step's
+                           // launch when the frame begins (enc_begin_stream): every kernel of the frame reads this one
 };
 
 // Per-stream encoder buffers for one frame step.
@@ -201,8 +203,9 @@ struct DecFrame {          // per (frame slot, stream): written by dec_scan_kern
 };
 #define H264MI_PROG_ABORT 0xFFFFFFFFu
 // MbInfo dword 31 (pad2) of a decoded MB: its slice's first MB (neighbour availability: a preceding MB
-// is in the same slice iff its address >= first) and loop-filter parameters (deblock.inc). 0 for the
-// encoder's single-slice pictures.
+// is in the same slice iff its address >= first) and loop-filter parameters (deblock.inc). The encoder's
+// records carry their slice's first MB (h264mi_enc_set_slices; 0 in a single-slice picture) and leave the
+// other fields 0: disable_deblocking_filter_idc 0, no filter offsets, in every slice.
 #define MB_SLICE_FIRST(w) ((int)((w) & 0xFFFFFu))
 #define MB_SLICE_IDC(w) ((int)(((w) >> 20) & 3u))
 #define MB_SLICE_OFFA(w) (2 * (((int)((w) << 6)) >> 28))   // bits 22..25, signed, x2

@@ -166,6 +166,7 @@ struct EncCtx {
     int gom_rows = 1;            // MB rows per GOM (RcInitSequenceParameter)
     int sgrp = 0;                // enc_mb_kernel: streams per ticket group of a queue (EncLaunch::sgrp; 0: all)
     bool gom_exact = false;      // OpenH264's GOM QP rule (h264mi_enc_set_gom_exact; enc_bits.inc gom_row_qp)
+    int slices = 1;              // slices per picture from the next frame step on (h264mi_enc_set_slices; BeginLaunch::slices)
     std::vector<EncDesc> h_desc[2];
     int parity = 0;
     // host-side output staging (C-ABI path)
@@ -204,6 +205,9 @@ static void enc_free(EncCtx *c) {
     delete c;
 }
 
+// a picture of mbh MB rows can be coded as n slices of whole MB rows (h264mi_dev.h slice_first_row)
+static bool slices_valid(int mbh, int n) { return n >= 1 && n <= mbh && n <= H264MI_MAX_SLICES; }
+
 static EncCtx *enc_create(int w, int h, int bitrate, int S, hipStream_t stream) {
     // h <= 4096: at most 256 MB rows (the pack kernel's row table)
     if (w <= 0 || h <= 0 || (w & 1) || (h & 1) || S <= 0 || S > H264MI_MAX_STREAMS || w > 16 * H264MI_ENC_MAX_MBW || h > 4096) return nullptr;
@@ -233,6 +237,12 @@ static EncCtx *enc_create(int w, int h, int bitrate, int S, hipStream_t stream) 
     size_t off_egr = off_plc + 2 * al(cps * cph);
     size_t off_rowqp = off_egr + al(8 * 128 * (size_t)c->nmb), off_rowbits = off_rowqp + al(4 * (size_t)c->mbh);
     size_t off_rowq = off_rowbits + al(4 * (size_t)c->mbh);
+    // defaults for new encoders: exact GOM mode, then the slice count (a bad value, or one with exact GOM, is ignored)
+    if (const char *e = getenv("H264MI_GOM_EXACT")) c->gom_exact = atoi(e) != 0;
+    if (const char *e = getenv("H264MI_ENC_SLICES")) {
+        const int n = atoi(e);
+        if (slices_valid(c->mbh, n) && !(c->gom_exact && n > 1)) c->slices = n;
+    }
     RcState rc0;
     rc_seq_init(rc0, w, h, bitrate);
     c->gom_count = rc0.gom_count;
@@ -302,6 +312,7 @@ static EncCtx *enc_create(int w, int h, int bitrate, int S, hipStream_t stream) 
         memset(&st, 0, sizeof(st));
         st.rc = rc0;
         st.first = 1; st.idr_pic_id = 0; st.bitrate = bitrate;  // first IDR: 1 (DESIGN.md §3.1)
+        st.cur_slices = c->slices;
         // the first frame's MB-row QP plan: no rows coded yet, every row at the frame QP (offset 0)
         std::vector<int32_t> rq((size_t)c->mbh, 0);
         (void)hipMemcpyAsync(b + off_rowqp, rq.data(), 4 * (size_t)c->mbh, hipMemcpyHostToDevice, c->stream);
@@ -321,7 +332,6 @@ static EncCtx *enc_create(int w, int h, int bitrate, int S, hipStream_t stream) 
     if (const char *e = getenv("H264MI_ENC_PROF_ROW")) c->prof_row = atoi(e);
     if (const char *e = getenv("H264MI_ENC_LEAN")) c->lean = atoi(e);  // diagnostics: force a build
     if (const char *e = getenv("H264MI_ENC_XQ")) c->xq = atoi(e);      // A/B: ticket queues
-    if (const char *e = getenv("H264MI_GOM_EXACT")) c->gom_exact = atoi(e) != 0;  // default for new encoders
     if (const char *e = getenv("H264MI_ENC_SGRP")) c->sgrp = atoi(e);               // A/B: streams per ticket group
     {
         int dev = 0, n = 0;
@@ -341,7 +351,7 @@ static int enc_frame(EncCtx *c, const uint8_t *d_frames) {
     const int src_vec = (c->w % 16) == 0 && (c->fbytes % 16) == 0 && ((uintptr_t)d_frames % 16) == 0;
     // frame complexity + skip decision + the rate control's picture init (enc_bits.inc)
     hipLaunchKernelGGL(enc_begin_kernel, dim3(c->begin_k, c->S), dim3(256), 0, c->stream,
-                       BeginLaunch{c->S, c->w, c->h, c->cw, c->ch, c->begin_k, c->d_desc[par], c->d_ticket, d_frames, c->fbytes, src_vec, c->d_done});
+                       BeginLaunch{c->S, c->w, c->h, c->cw, c->ch, c->begin_k, c->d_desc[par], c->d_ticket, d_frames, c->fbytes, src_vec, c->d_done, c->slices});
     EncLaunch el{c->w, c->h, c->mbw, c->mbh, c->S, c->d_desc[par], c->d_ticket, d_frames, c->fbytes, c->d_prof, src_vec,
                  c->d_dbk[par], c->d_prof ? c->d_prof + 16 : nullptr, c->dlag};
     if (c->timing) {
@@ -368,7 +378,8 @@ static int enc_frame(EncCtx *c, const uint8_t *d_frames) {
     // frame's deblocked picture, one launch (enc_post_kernel). (The planes on a side stream beside the
     // packing were measured slower twice: 1715 -> 1312 frames/s in round 1 with 4 hardware queues,
     // 1315 -> 1249 in round 2 with 8.)
-    if (launch_enc_post(PackLaunch{c->mbw, c->mbh, c->S, c->d_desc[par]}, c->cw, c->ch, c->d_pd[par], c->stream) != 0) return -1;
+    // (the pack of a multi-slice frame is a kernel of its own: c->slices is what this step's begin kernel latches)
+    if (launch_enc_post(PackLaunch{c->mbw, c->mbh, c->S, c->d_desc[par]}, c->cw, c->ch, c->d_pd[par], c->stream, c->slices > 1) != 0) return -1;
     HIPCHECK(hipGetLastError());
     c->parity ^= 1;
     return 0;

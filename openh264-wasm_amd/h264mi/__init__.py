@@ -48,6 +48,9 @@ def lib():
             'h264mi_enc_set_frame_skip': (i, [vp, i]),
             'h264mi_enc_frames_skipped': (i, [vp, i]),
             'h264mi_enc_set_gom_exact': (i, [vp, i]),
+            'h264mi_enc_set_slices': (i, [vp, i]),
+            'h264mi_enc_slices': (i, [vp]),
+            'h264mi_slice_first_row': (i, [i, i, i]),
             'h264mi_enc_inject_error': (i, [vp, i, i]),
             'h264mi_enc_sync': (i, [vp]),
             'h264mi_enc_nal_bytes': (i, [vp, vp]),
@@ -246,6 +249,12 @@ class Module:
         cb()
 
 
+def slice_first_row(mbh, n, k):
+    """first MB row of slice k of a picture of mbh MB rows coded as n slices (h264mi_slice_first_row; host only):
+    (k * mbh) // n, mbh for k == n, -1 on bad arguments"""
+    return lib().h264mi_slice_first_row(int(mbh), int(n), int(k))
+
+
 class BatchEncoder:
     """S independent encoder streams of one geometry, frames and NAL units resident in HBM."""
 
@@ -283,6 +292,16 @@ class BatchEncoder:
         """OpenH264's exact GOM rate control (h264mi_enc_set_gom_exact)"""
         if self._L.h264mi_enc_set_gom_exact(self._e, 1 if on else 0) != 0:
             raise RuntimeError('h264mi_enc_set_gom_exact failed')
+
+    def set_slices(self, n):
+        """every picture as n slices of whole MB rows from the next encode on (h264mi_enc_set_slices); ValueError on
+        an n outside 1..min(MB rows, 32), or n > 1 with exact GOM rate control on"""
+        if self._L.h264mi_enc_set_slices(self._e, int(n)) != 0:
+            raise ValueError(f'h264mi_enc_set_slices({n}) refused')
+
+    def slices(self):
+        """slices per picture in force for the next encode (h264mi_enc_slices)"""
+        return self._L.h264mi_enc_slices(self._e)
 
     def gom_state(self, s=0):
         """exact GOM mode: the last P frame's per-GOM [QP, slice bits before it, target bits, last coded MB + 1]
