@@ -110,6 +110,12 @@ const void *h264mi_enc_nal_ptr(h264mi_encoder *e, int stream);     /* Annex-B by
 const void *h264mi_enc_recon_ptr(h264mi_encoder *e, int stream);   /* deblocked reconstruction, coded size (device) */
 const void *h264mi_enc_input_buffer(h264mi_encoder *e);            /* internal device input area (nstreams frames) */
 size_t h264mi_enc_frame_bytes(h264mi_encoder *e);
+/* async, as h264mi_enc_encode, from nstreams tight RGBA8 frames back to back (device, 4-byte aligned,
+   h264mi_enc_rgba_frame_bytes = 4 * width * height each): one batched conversion (the reference's rgba_to_yuv:
+   BT.601 limited range, chroma from the top-left pixel of each 2x2, alpha ignored) into the encoder's input
+   area on its stream, then the same frame step -- rate control, slices, exact GOM and inject_error as there */
+int h264mi_enc_encode_rgba(h264mi_encoder *e, const void *d_rgba_frames);
+size_t h264mi_enc_rgba_frame_bytes(h264mi_encoder *e);
 int h264mi_enc_last_qp(h264mi_encoder *e, int stream);
 /* the rate control's state after the last frame step (RC_BITRATE_MODE restated from h264.wasm),
    16 int32 in the oracle's h264o_enc_rc_state order: {skipped, QP, average QP, target bits, remaining bits,
@@ -206,6 +212,15 @@ int h264mi_dec_decode_frames_after_n(h264mi_decoder *d, int nframes, const void 
 int h264mi_dec_decode_frames_out(h264mi_decoder *d, int nframes, const void *const *d_nal, const int *nal_bytes,
                                  const int *const *d_sizes, void *const *ready_events, int nevents, void *const *d_out,
                                  int *const *d_got);
+/* what h264mi_dec_decode_frames_out writes to d_out: H264MI_FMT_I420 (the default), or H264MI_FMT_RGBA: frame
+   f's cropped picture as tight RGBA8 (width x height x 4 bytes, 4-byte aligned buffers, A = 255; the reference's
+   yuv_to_rgba_optimized), converted straight from the deblocked picture. Timing and d_got are the same for both.
+   Applies to the calls enqueued after it (each call captures its format). Returns 0, -1 on a bad argument.
+   h264mi_dec_output_format: the format in effect. */
+#define H264MI_FMT_I420 0
+#define H264MI_FMT_RGBA 1
+int h264mi_dec_set_output_format(h264mi_decoder *d, int fmt);
+int h264mi_dec_output_format(h264mi_decoder *d);
 int h264mi_dec_sync(h264mi_decoder *d);
 /* HIP-event timing of the decoder's kernels (bench.py): which 0 = dec_recon_kernel, 1 = dec_parse_kernel */
 int h264mi_dec_set_timing(h264mi_decoder *d, int enable);
@@ -265,6 +280,13 @@ int h264mi_nal_unpack(void *dst, const void *src, size_t slot, const int32_t *si
 /* edge colour conversions on the GPU, host buffers (openh264_wrapper.cpp:22-40 and :150-195) */
 int h264mi_rgba_to_i420_host(const unsigned char *rgba, int width, int height, unsigned char *out_i420);
 int h264mi_i420_to_rgba_host(const unsigned char *i420, int width, int height, unsigned char *out_rgba);
+/* the same conversions on device buffers, async on hip_stream: n frames of one geometry in one launch, tight
+   RGBA8 frames (4 * w * h bytes, 4-byte aligned) and tight I420 frames (w * h * 3 / 2 bytes) back to back.
+   A frame whose buffers are aligned for it (w % 8 == 0, RGBA 16 bytes, I420 8 bytes) takes the wide-access
+   path; any other takes a 2-pixel path with the same bytes. Returns 0, or -1 on a bad argument (a null
+   pointer, w or h odd or <= 0, n <= 0), which is checked before the device is touched. */
+int h264mi_rgba_to_i420_dev(void *d_i420, const void *d_rgba, int w, int h, int n, void *hip_stream);
+int h264mi_i420_to_rgba_dev(void *d_rgba, const void *d_i420, int w, int h, int n, void *hip_stream);
 
 /* library self-description */
 const char *h264mi_version(void);

@@ -107,9 +107,9 @@ void h264mi_i_decode_frame_optimized_cap(h264mi_instance *I, int decoder_index, 
         if (hipMalloc(&c->d_rgba, n) != hipSuccess) return;
         c->rgba_cap = n;
     }
-    if (launch_i420_to_rgba(d.pic[par][0] + (size_t)y0 * c->cw + x0, d.pic[par][1] + (size_t)(y0 / 2) * (c->cw / 2) + x0 / 2,
-                            d.pic[par][2] + (size_t)(y0 / 2) * (c->cw / 2) + x0 / 2, W, H, c->cw, c->cw / 2, c->d_rgba, c->stream) != 0)
-        return;
+    const I420Pics pics{d.pic[par][0] + (size_t)y0 * c->cw + x0, d.pic[par][1] + (size_t)(y0 / 2) * (c->cw / 2) + x0 / 2,
+                        d.pic[par][2] + (size_t)(y0 / 2) * (c->cw / 2) + x0 / 2, 0, c->cw, c->cw / 2};
+    if (W <= 0 || H <= 0 || launch_i420_to_rgba(pics, W, H, 1, c->d_rgba, c->stream) != 0) return;
     if (hipMemcpyAsync(out_rgba_buffer, c->d_rgba, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return;
     *out_width = W; *out_height = H;
@@ -177,10 +177,11 @@ int h264mi_dec_decode_frames_out(h264mi_decoder *d, int nframes, const void *con
         (nevents > 0 && !ready_events)) return -1;
     std::vector<DecInput> in((size_t)nframes * d->c->S);
     for (size_t i = 0; i < in.size(); i++) {
+        if (d_out && d->c->out_fmt == H264MI_FMT_RGBA && ((uintptr_t)d_out[i] & 3)) return -1;  // RGBA pixels are stored as dwords
         in[i].nal = (const uint8_t *)d_nal[i];
         in[i].size = nal_bytes ? nal_bytes[i] : 0;
         in[i].size_dev = d_sizes ? (const int32_t *)d_sizes[i] : nullptr;
-        in[i].pad = 0;
+        in[i].fmt = d->c->out_fmt;
         in[i].out = d_out ? (uint8_t *)d_out[i] : nullptr;
         in[i].got = d_got ? (int32_t *)d_got[i] : nullptr;
     }
@@ -215,6 +216,14 @@ int h264mi_dec_set_streamed(h264mi_decoder *d, int mode) {
     return dec_set_streamed(d->c, mode);
 }
 int h264mi_dec_streamed(h264mi_decoder *d) { return d ? d->c->streamed : 0; }
+// what h264mi_dec_decode_frames_out writes to its d_out buffers; each call captures the format when it is
+// enqueued (DecInput::fmt), so a change needs no synchronisation
+int h264mi_dec_set_output_format(h264mi_decoder *d, int fmt) {
+    if (!d || (fmt != H264MI_FMT_I420 && fmt != H264MI_FMT_RGBA)) return -1;
+    d->c->out_fmt = fmt;
+    return 0;
+}
+int h264mi_dec_output_format(h264mi_decoder *d) { return d ? d->c->out_fmt : -1; }
 int h264mi_dec_set_recon_gate(h264mi_decoder *d, const uint32_t *d_counter, uint32_t target, uint32_t step, int count, int limit_us) {
     if (!d || count < 0 || limit_us < 0 || limit_us > 1000000) return -1;
     DecCtx *c = d->c;
@@ -313,7 +322,7 @@ extern "C" int h264mi_rgba_to_i420_host(const unsigned char *rgba, int w, int h,
     uint8_t *d = nullptr;
     if (hipMalloc(&d, n_in + n_out) != hipSuccess) return -1;
     int rc = -1;
-    if (hipMemcpy(d, rgba, n_in, hipMemcpyHostToDevice) == hipSuccess && launch_rgba_to_i420(d, w, h, d + n_in, nullptr) == 0 &&
+    if (hipMemcpy(d, rgba, n_in, hipMemcpyHostToDevice) == hipSuccess && launch_rgba_to_i420(d, w, h, 1, d + n_in, nullptr) == 0 &&
         hipMemcpy(out_i420, d + n_in, n_out, hipMemcpyDeviceToHost) == hipSuccess)
         rc = 0;
     (void)hipFree(d);
@@ -325,11 +334,20 @@ extern "C" int h264mi_i420_to_rgba_host(const unsigned char *i420, int w, int h,
     uint8_t *d = nullptr;
     if (hipMalloc(&d, n_in + n_out) != hipSuccess) return -1;
     int rc = -1;
-    const uint8_t *Y = d, *U = d + (size_t)w * h, *V = U + (size_t)(w / 2) * (h / 2);
     if (hipMemcpy(d, i420, n_in, hipMemcpyHostToDevice) == hipSuccess &&
-        launch_i420_to_rgba(Y, U, V, w, h, w, w / 2, d + n_in, nullptr) == 0 &&
+        launch_i420_to_rgba(tight_i420(d, w, h), w, h, 1, d + n_in, nullptr) == 0 &&
         hipMemcpy(out_rgba, d + n_in, n_out, hipMemcpyDeviceToHost) == hipSuccess)
         rc = 0;
     (void)hipFree(d);
     return rc;
+}
+// Device-buffer forms: n tight frames back to back on both sides, one launch, asynchronous on the stream.
+// The argument checks come before any HIP call.
+extern "C" int h264mi_rgba_to_i420_dev(void *d_i420, const void *d_rgba, int w, int h, int n, void *hip_stream) {
+    if (!d_i420 || !d_rgba || !color_args_ok(w, h, n) || ((uintptr_t)d_rgba & 3)) return -1;
+    return launch_rgba_to_i420((const uint8_t *)d_rgba, w, h, n, (uint8_t *)d_i420, (hipStream_t)hip_stream);
+}
+extern "C" int h264mi_i420_to_rgba_dev(void *d_rgba, const void *d_i420, int w, int h, int n, void *hip_stream) {
+    if (!d_rgba || !d_i420 || !color_args_ok(w, h, n) || ((uintptr_t)d_rgba & 3)) return -1;
+    return launch_i420_to_rgba(tight_i420((const uint8_t *)d_i420, w, h), w, h, n, (uint8_t *)d_rgba, (hipStream_t)hip_stream);
 }

@@ -93,7 +93,7 @@ void h264mi_i_encode_frame(h264mi_instance *I, unsigned char *rgba, int width, i
         I->rgba_dev_size = n;
     }
     if (hipMemcpyAsync(I->rgba_dev, rgba, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return;
-    if (launch_rgba_to_i420(I->rgba_dev, width, height, c->d_src, c->stream) != 0) return;
+    if (launch_rgba_to_i420(I->rgba_dev, width, height, 1, c->d_src, c->stream) != 0) return;
     if (enc_frame(c, c->d_src) != 0) return;
     enc_fetch(I, c, 0, out_data, out_size);
 }
@@ -177,8 +177,17 @@ int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
     if (!e || !d_frames) return -1;
     return enc_frame(e->c, (const uint8_t *)d_frames);
 }
+// nstreams tight RGBA8 frames back to back: one batched conversion into the encoder's own input area on its
+// stream, then the frame step as h264mi_enc_encode runs it
+int h264mi_enc_encode_rgba(h264mi_encoder *e, const void *d_rgba_frames) {
+    if (!e || !d_rgba_frames || ((uintptr_t)d_rgba_frames & 3)) return -1;
+    EncCtx *c = e->c;
+    if (launch_rgba_to_i420((const uint8_t *)d_rgba_frames, c->w, c->h, c->S, c->d_src, c->stream) != 0) return -1;
+    return enc_frame(c, c->d_src);
+}
 const void *h264mi_enc_input_buffer(h264mi_encoder *e) { return e ? e->c->d_src : nullptr; }
 size_t h264mi_enc_frame_bytes(h264mi_encoder *e) { return e ? e->c->fbytes : 0; }
+size_t h264mi_enc_rgba_frame_bytes(h264mi_encoder *e) { return e ? (size_t)e->c->w * e->c->h * 4 : 0; }
 int h264mi_enc_sync(h264mi_encoder *e) { return e && hipStreamSynchronize(e->c->stream) == hipSuccess ? 0 : -1; }
 int h264mi_enc_nal_bytes(h264mi_encoder *e, int *out) {
     if (!e) return -1;

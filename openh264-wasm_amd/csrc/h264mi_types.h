@@ -211,8 +211,9 @@ struct DecFrame {          // per (frame slot, stream): written by dec_scan_kern
 #define MB_SLICE_OFFA(w) (2 * (((int)((w) << 6)) >> 28))   // bits 22..25, signed, x2
 #define MB_SLICE_OFFB(w) (2 * (((int)((w) << 2)) >> 28))   // bits 26..29, signed, x2
 // one access unit; out / got (optional, device): where dec_output_kernel puts this frame's cropped tight
-// I420 picture and its got-picture flag once the frame is reconstructed (every frame of a batched call)
-struct DecInput { const uint8_t *nal; const int32_t *size_dev; int32_t size, pad; uint8_t *out; int32_t *got; };
+// I420 picture and its got-picture flag once the frame is reconstructed (every frame of a batched call).
+// fmt (H264MI_FMT_*, one value per call): RGBA has dec_output_rgba_kernel write tight RGBA8 instead
+struct DecInput { const uint8_t *nal; const int32_t *size_dev; int32_t size, fmt; uint8_t *out; int32_t *got; };
 
 struct DecDesc {
     uint8_t *cur[3];        // unfiltered reconstruction (coded size)

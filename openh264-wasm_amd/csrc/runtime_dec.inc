@@ -44,6 +44,7 @@ struct DecCtx {
     const uint32_t *rg_counter = nullptr;
     uint32_t rg_target = 0, rg_step = 0, rg_limit = 0;
     int rg_count = 0;
+    int out_fmt = 0;                    // H264MI_FMT_*: what the next calls write to their d_out buffers
     // C-ABI staging
     uint8_t *d_nal = nullptr;
     size_t nal_cap = 0;
@@ -294,7 +295,11 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
         if (dec_time_mark(c, 0, c->stream)) return -1;
         if (streamed && f == 0) HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_parsed[g], 0));
         hipLaunchKernelGGL(dec_end_kernel, dim3((S + 63) / 64), dim3(64), 0, c->stream, DecEndLaunch{S, df, streamed});
-        if (outputs)  // every frame's picture to the caller (DecInput::out / got)
+        if (outputs && in[0].fmt == H264MI_FMT_RGBA) {  // every frame's picture to the caller (DecInput::out / got)
+            const dim3 cg = color_grid(c->cw, c->ch, S);
+            hipLaunchKernelGGL(dec_output_rgba_kernel, dim3(cg.x, S), dim3(256), 0, c->stream,
+                               DecOutLaunch{S, c->cw, c->ch, df, c->d_in + (size_t)(slot0 + f) * S});
+        } else if (outputs)
             hipLaunchKernelGGL(dec_output_kernel, dim3((2 * c->ch + 3) / 4, S), dim3(256), 0, c->stream,
                                DecOutLaunch{S, c->cw, c->ch, df, c->d_in + (size_t)(slot0 + f) * S});
         if (launch_ref_planes(S, c->cw, c->ch, c->d_pd, c->stream) != 0) return -1;  // the next frame's reference planes
@@ -360,7 +365,7 @@ static int dec_frame(DecCtx *c, const uint8_t *const *d_nal, const int *nbytes, 
                      uint8_t *const *d_out = nullptr) {
     std::vector<DecInput> in(c->S);
     for (int s = 0; s < c->S; s++) {
-        in[s].nal = d_nal[s]; in[s].size = nbytes ? nbytes[s] : 0; in[s].size_dev = nbytes_dev ? nbytes_dev[s] : nullptr; in[s].pad = 0;
+        in[s].nal = d_nal[s]; in[s].size = nbytes ? nbytes[s] : 0; in[s].size_dev = nbytes_dev ? nbytes_dev[s] : nullptr; in[s].fmt = H264MI_FMT_I420;
         in[s].out = d_out ? d_out[s] : nullptr; in[s].got = nullptr;
     }
     return dec_frames(c, 1, in.data());

@@ -108,6 +108,12 @@ def lib():
             'h264mi_dec_stream': (vp, [vp]),
             'h264mi_rgba_to_i420_host': (i, [vp, i, i, vp]),
             'h264mi_i420_to_rgba_host': (i, [vp, i, i, vp]),
+            'h264mi_rgba_to_i420_dev': (i, [vp, vp, i, i, i, vp]),
+            'h264mi_i420_to_rgba_dev': (i, [vp, vp, i, i, i, vp]),
+            'h264mi_enc_encode_rgba': (i, [vp, vp]),
+            'h264mi_enc_rgba_frame_bytes': (ctypes.c_size_t, [vp]),
+            'h264mi_dec_set_output_format': (i, [vp, i]),
+            'h264mi_dec_output_format': (i, [vp]),
             'h264mi_ring_create': (vp, [i, i]),
             'h264mi_ring_destroy': (None, [vp]),
             'h264mi_ring_publish': (ctypes.c_longlong, [vp, vp, i, i]),
@@ -262,6 +268,7 @@ class BatchEncoder:
         import torch
         self.w, self.h, self.S = width, height, nstreams
         self.frame_bytes = width * height * 3 // 2
+        self.rgba_frame_bytes = width * height * 4
         self._L = lib()
         hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
         self._e = self._L.h264mi_enc_create(width, height, bitrate, nstreams, ctypes.c_void_p(hs))
@@ -274,6 +281,13 @@ class BatchEncoder:
         assert frames.is_cuda and frames.numel() >= self.S * self.frame_bytes
         if self._L.h264mi_enc_encode(self._e, ctypes.c_void_p(frames.data_ptr())) != 0:
             raise RuntimeError('h264mi_enc_encode failed')
+
+    def encode_rgba(self, frames):
+        """frames: uint8 CUDA tensor holding S tight RGBA8 frames (4 * w * h bytes each) back to back (async):
+        one batched conversion on the encoder's stream, then the frame step of encode()"""
+        assert frames.is_cuda and frames.numel() >= self.S * self.rgba_frame_bytes
+        if self._L.h264mi_enc_encode_rgba(self._e, ctypes.c_void_p(frames.data_ptr())) != 0:
+            raise RuntimeError('h264mi_enc_encode_rgba failed')
 
     def force_idr(self, stream=-1):
         self._L.h264mi_enc_force_idr(self._e, stream)
@@ -446,7 +460,9 @@ class BatchDecoder:
         (nal_sizes) or device int32 addresses (size_ptrs). n <= max_frames. Inputs are ordered after
         the decoder's stream, or, if ready_event (a torch.cuda.Event recorded by the producer, or a
         list of them, one per producer stream) is given, after those events only. out_ptrs / got_ptrs
-        (device addresses, same indexing): every frame's cropped tight I420 picture and got flag."""
+        (device addresses, same indexing): every frame's cropped picture and got flag. An out buffer holds
+        w * h * 3 // 2 bytes (tight I420) with the output format 'i420', w * h * 4 bytes (tight RGBA8, 4-byte
+        aligned) with 'rgba' (set_output_format); it is left untouched when got is 0."""
         m = len(nal_ptrs)
         assert m % self.S == 0 and m // self.S <= self.B
         ptrs = (ctypes.c_void_p * m)(*nal_ptrs)
@@ -458,6 +474,16 @@ class BatchDecoder:
         gp = (ctypes.c_void_p * m)(*got_ptrs) if got_ptrs is not None else None
         if self._L.h264mi_dec_decode_frames_out(self._d, m // self.S, ptrs, sizes, sp, ev, len(evs), op, gp) != 0:
             raise RuntimeError('h264mi_dec_decode_frames failed')
+
+    OUTPUT_FORMATS = {'i420': 0, 'rgba': 1}  # H264MI_FMT_*
+
+    def set_output_format(self, fmt):
+        """what decode_frames writes to out_ptrs from the next call on: 'i420' (default) or 'rgba'"""
+        if fmt not in self.OUTPUT_FORMATS or self._L.h264mi_dec_set_output_format(self._d, self.OUTPUT_FORMATS[fmt]) != 0:
+            raise ValueError(f'h264mi_dec_set_output_format({fmt!r}) refused')
+
+    def output_format(self):
+        return {v: k for k, v in self.OUTPUT_FORMATS.items()}[self._L.h264mi_dec_output_format(self._d)]
 
     def set_parse_cus(self, lo, hi):
         """entropy decoding on CU mask bits [lo, hi) (see h264mi_dec_set_parse_cus)"""
@@ -613,6 +639,27 @@ def _hiprt():
         _hip.hipStreamSynchronize.restype = ctypes.c_int
         _hip.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
     return _hip
+
+
+def _convert_dev(fn, dst, src, dst_bytes, src_bytes, w, h, n, stream):
+    import torch
+    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
+    assert dst.is_contiguous() and src.is_contiguous()
+    assert n <= 0 or (dst.numel() >= n * dst_bytes and src.numel() >= n * src_bytes)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if fn(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {w}x{h}, {n} frames')
+
+
+def rgba_to_i420(dst, src, w, h, n, stream=None):
+    """n tight RGBA8 frames (uint8 CUDA tensor src) to n tight I420 frames (dst), one launch, async on stream
+    (default: the current one); h264mi_rgba_to_i420_dev"""
+    _convert_dev(lib().h264mi_rgba_to_i420_dev, dst, src, w * h * 3 // 2, w * h * 4, w, h, n, stream)
+
+
+def i420_to_rgba(dst, src, w, h, n, stream=None):
+    """n tight I420 frames (uint8 CUDA tensor src) to n tight RGBA8 frames (dst, A = 255); h264mi_i420_to_rgba_dev"""
+    _convert_dev(lib().h264mi_i420_to_rgba_dev, dst, src, w * h * 4, w * h * 3 // 2, w, h, n, stream)
 
 
 def version():
