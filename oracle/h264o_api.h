@@ -71,6 +71,28 @@ int h264o_dec_decode(H264ODec *d, const uint8_t *data, int size, uint8_t *out_i4
 void h264o_dec_mbinfo(const H264ODec *d, int32_t *out);
 void h264o_dec_nnz(const H264ODec *d, uint8_t *out);  /* 24 TotalCoeff bytes per MB of the last picture */
 
+/* Loop-filter test hooks (tests/dbkref.py): everything clause 8.7 reads, as the decoder holds it when it
+ * calls its own filter. They change nothing of what the decoder decodes.
+ * h264o_dec_set_capture(d, 1): from the next picture on, keep a copy of the picture as it stands immediately
+ *   before the loop filter. h264o_dec_prefilter copies it to out as tight I420 at *coded* size (the filter's
+ *   taps cross the crop line; h264o_dec_coded_size gives cw, ch) and returns its byte count cw * ch * 3 / 2,
+ *   -1 when no picture was captured.
+ * h264o_dec_records: H264O_REC_INTS int32 for every macroblock of the last picture, in raster order; returns
+ *   the macroblock count (-1: no picture geometry yet). Layout of one record:
+ *     [0]      mb type (MBT_*: 0 I_NxN, 1 I_16x16, 2 P_L0_16x16, 3 P_Skip, 4 P_16x8, 5 P_8x16, 6 P_8x8, 7 I_PCM)
+ *     [1]      QPY as parsed (an I_PCM macroblock holds the running QPY; 8.7.2.2's "QPY 0" rule is the reader's)
+ *     [2..17]  TotalCoeff of the 16 luma 4x4 blocks, raster order (I_PCM: 16 each)
+ *     [18..21] ref_idx_l0 of the four 8x8 quadrants (-1: intra)
+ *     [22..53] mv of the 16 luma 4x4 blocks, raster order, x then y, quarter samples
+ *     [54]     first_mb_in_slice of the macroblock's slice
+ *     [55]     disable_deblocking_filter_idc   [56] FilterOffsetA   [57] FilterOffsetB  (of that slice)
+ *     [58]     chroma_qp_index_offset of the picture's PPS   [59] 0 (reserved) */
+#define H264O_REC_INTS 60
+void h264o_dec_set_capture(H264ODec *d, int on);
+int h264o_dec_coded_size(const H264ODec *d, int *cw, int *ch);
+int h264o_dec_prefilter(const H264ODec *d, uint8_t *out);
+int h264o_dec_records(const H264ODec *d, int32_t *out);
+
 /* test-stream helpers (tests/streamgen.py): CAVLC bits of one residual block (0/1 per byte; returns
  * the bit count, -1 if cap is too small) and the coded_block_pattern codeNum of cbp (Table 9-4) */
 int h264o_cavlc_bits(const int16_t *coef, int maxnum, int nc, uint8_t *bits, int cap);

@@ -26,6 +26,8 @@ struct H264ODec {
     MBInfo *mbs;
     uint8_t *done;            /* per MB: decoded in the picture being assembled */
     int pic_open, pic_idr, pic_ref;  /* the access unit's picture: started, IDR, nal_ref_idc != 0 */
+    int capture;              /* test hook: keep a copy of each picture as it stands before the loop filter */
+    uint8_t *pre;             /* that copy: tight I420 at coded size (cw x ch), NULL until a picture was captured */
 };
 
 H264ODec *h264o_dec_create(void) { return (H264ODec *)calloc(1, sizeof(H264ODec)); }
@@ -34,7 +36,7 @@ static void free_frames(H264ODec *d) {
     free(d->mbs); d->mbs = NULL;
     free(d->done); d->done = NULL;
 }
-void h264o_dec_destroy(H264ODec *d) { if (d) { free_frames(d); free(d); } }
+void h264o_dec_destroy(H264ODec *d) { if (d) { free_frames(d); free(d->pre); free(d); } }
 
 static int parse_sps(H264ODec *d, BR *r) {
     int profile = br_get(r, 8);
@@ -486,6 +488,14 @@ int h264o_dec_decode(H264ODec *d, const uint8_t *data, int size, uint8_t *out, i
             emit_picture(d, d->ref, out, w, h);
             return 2;
         }
+    if (d->capture) {  /* test hook: the loop filter's input, read-only for the decoding process */
+        const size_t ny = (size_t)d->cw * d->ch;
+        uint8_t *pre = (uint8_t *)realloc(d->pre, ny * 3 / 2);
+        if (pre) {
+            d->pre = pre;
+            memcpy(pre, d->cur[0], ny); memcpy(pre + ny, d->cur[1], ny / 4); memcpy(pre + ny + ny / 4, d->cur[2], ny / 4);
+        }
+    }
     /* the loop filter over the whole picture, each MB with its slice's parameters (8.7) */
     deblock_frame(d->cur[0], d->cur[1], d->cur[2], d->cw, d->cw / 2, d->mbs, d->mbw, d->mbh, d->cqp_off);
     emit_picture(d, d->cur, out, w, h);
@@ -507,6 +517,35 @@ void h264o_dec_mbinfo(const H264ODec *d, int32_t *out) {
         r[0] = m->type; r[1] = m->qp; r[2] = m->cbp; r[3] = m->mv[0][0]; r[4] = m->mv[0][1];
         r[5] = m->i16mode; r[6] = m->cmode; r[7] = s;
     }
+}
+
+/* ---------------- loop-filter test hooks (h264o_api.h): what clause 8.7 consumes ---------------- */
+void h264o_dec_set_capture(H264ODec *d, int on) { if (d) d->capture = on != 0; }
+int h264o_dec_coded_size(const H264ODec *d, int *cw, int *ch) {
+    if (!d || !d->mbs) return -1;
+    *cw = d->cw; *ch = d->ch;
+    return 0;
+}
+int h264o_dec_prefilter(const H264ODec *d, uint8_t *out) {
+    if (!d || !d->pre || !d->mbs) return -1;
+    const int n = d->cw * d->ch * 3 / 2;
+    memcpy(out, d->pre, (size_t)n);
+    return n;
+}
+int h264o_dec_records(const H264ODec *d, int32_t *out) {
+    if (!d || !d->mbs) return -1;
+    const int n = d->mbw * d->mbh;
+    for (int i = 0; i < n; i++) {
+        const MBInfo *m = &d->mbs[i];
+        int32_t *r = out + (size_t)H264O_REC_INTS * i;
+        r[0] = m->type; r[1] = m->qp;
+        for (int k = 0; k < 16; k++) r[2 + k] = m->nnz[k];
+        for (int k = 0; k < 4; k++) r[18 + k] = m->ref[k];
+        for (int k = 0; k < 16; k++) { r[22 + 2 * k] = m->mv[k][0]; r[23 + 2 * k] = m->mv[k][1]; }
+        r[54] = m->slice_first; r[55] = m->dbk_idc; r[56] = m->dbk_a; r[57] = m->dbk_b;
+        r[58] = d->cqp_off; r[59] = 0;
+    }
+    return n;
 }
 
 /* ---------------- wrapper colour conversion (openh264_wrapper.cpp:22-40, :150-195) ---------------- */

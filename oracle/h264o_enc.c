@@ -497,6 +497,9 @@ int h264o_table(const char *name, double *out) {
     else if (!strcmp(name, "level_limits")) { for (int i = 0; i < 17 * 6; i++) out[n++] = OH_LEVEL_LIMITS[i / 6][i % 6]; }
     else if (!strcmp(name, "single_ctr_run")) { for (int i = 0; i < 16; i++) out[n++] = OH_SINGLE_CTR[i]; }
     else if (!strcmp(name, "chroma_qp")) { for (int i = 0; i < 52; i++) out[n++] = CHROMA_QP[i]; }
+    else if (!strcmp(name, "dbk_alpha")) { for (int i = 0; i < 52; i++) out[n++] = DBK_ALPHA[i]; }
+    else if (!strcmp(name, "dbk_beta")) { for (int i = 0; i < 52; i++) out[n++] = DBK_BETA[i]; }
+    else if (!strcmp(name, "dbk_tc0")) { for (int i = 0; i < 52 * 3; i++) out[n++] = DBK_TC0[i / 3][i % 3]; }
     else return -1;
     return n;
 }

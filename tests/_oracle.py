@@ -34,6 +34,11 @@ class Oracle:
         L.h264o_dec_destroy.argtypes = [vp]
         L.h264o_dec_decode.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
         L.h264o_dec_mbinfo.argtypes = [vp, vp]
+        L.h264o_dec_set_capture.argtypes = [vp, ctypes.c_int]
+        L.h264o_dec_coded_size.argtypes = [vp, vp, vp]
+        L.h264o_dec_prefilter.argtypes = [vp, vp]
+        L.h264o_dec_records.argtypes = [vp, vp]
+        L.h264o_table.argtypes = [ctypes.c_char_p, vp]
         L.h264o_rgba_to_i420.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
         L.h264o_i420_to_rgba.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
         self.L = L
@@ -124,6 +129,33 @@ class ODec:
         if rc in (1, 2):  # 2: damaged access unit concealed by a copy of the last picture
             return rc, self.out[:w.value * h.value * 3 // 2].copy(), w.value, h.value
         return rc, None, w.value, h.value
+
+    REC_INTS = 60  # H264O_REC_INTS
+
+    def set_capture(self, on=True):
+        """keep each picture as it stands before the loop filter (h264o_dec_set_capture)"""
+        self.L.h264o_dec_set_capture(self.d, 1 if on else 0)
+
+    def coded_size(self):
+        cw, ch = ctypes.c_int(0), ctypes.c_int(0)
+        assert self.L.h264o_dec_coded_size(self.d, ctypes.byref(cw), ctypes.byref(ch)) == 0
+        return cw.value, ch.value
+
+    def prefilter(self):
+        """-> (Y, U, V) of the last picture before its loop filter, at coded size"""
+        cw, ch = self.coded_size()
+        buf = np.zeros(cw * ch * 3 // 2, np.uint8)
+        assert self.L.h264o_dec_prefilter(self.d, buf.ctypes.data) == buf.size
+        n = cw * ch
+        return (buf[:n].reshape(ch, cw), buf[n:n + n // 4].reshape(ch // 2, cw // 2),
+                buf[n + n // 4:].reshape(ch // 2, cw // 2))
+
+    def records(self):
+        """-> int32 [macroblocks, REC_INTS]: what clause 8.7 reads of every macroblock (layout: h264o_api.h)"""
+        cw, ch = self.coded_size()
+        out = np.zeros((cw // 16) * (ch // 16) * self.REC_INTS, np.int32)
+        assert self.L.h264o_dec_records(self.d, out.ctypes.data) == out.size // self.REC_INTS
+        return out.reshape(-1, self.REC_INTS)
 
     def __del__(self):
         try:

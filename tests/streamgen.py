@@ -148,6 +148,7 @@ class SyntaxGen:
         self.cqp, self.init_qp = cqp, init_qp
         self.poc_type, self.dpoaz = poc_type, dpoaz  # POC type 0 / 1 (delta_pic_order_always_zero_flag) / 2
         self.tc_choice = None  # TotalCoeff distribution of generated blocks (None: the default mix)
+        self._spec = None      # the scripted macroblock being written (_slice's script=), else None
         self.frame_num = 0
         self.poc = 0
         self.idr_id = 0
@@ -271,9 +272,23 @@ class SyntaxGen:
         if kind == 'pcm':
             w.ue(off + 25)
             w.align_zero()
+            if self._spec is not None and 'samples' in self._spec:   # scripted: the 384 pcm_sample bytes (Y, Cb, Cr)
+                for v in self._spec['samples']:
+                    w.u(int(v), 8)
+                return qp, [16] * 24, None
             for _ in range(384):
                 w.u(int(rng.integers(1, 256)), 8)
             return qp, [16] * 24, None
+        if kind == 'i16' and self._spec is not None and 'mode' in self._spec:
+            # scripted I_16x16 with no coefficient at all: prediction mode 'mode' (its neighbours must be available),
+            # chroma DC prediction, coded_block_pattern 0, mb_qp_delta 'dq' -- the block is its prediction
+            w.ue(off + 1 + int(self._spec['mode']))
+            w.ue(0)
+            dq = int(self._spec.get('dq', 0))
+            w.se(dq)
+            qp = (qp + dq + 52) % 52
+            self._block(w, np.zeros(16, np.int16), self._nc(nn, None, mx, my, cur, 0))
+            return qp, cur, None
         cm = int(rng.choice([m for m, nd in _CHROMA_NEEDS.items() if _ok(nd, top_mb, left_mb, tl_mb)]))
         if kind == 'i4':
             w.ue(off + 0)
@@ -356,10 +371,12 @@ class SyntaxGen:
         return self.init_qp + qp_delta
 
     def _slice(self, idr, mix, qp_delta=0, dbk=(0, 0, 0), override=False, reorder=False, max_mvd=24, ref_idc=2, cbp_fixed=None,
-               slices=None):
+               slices=None, script=None):
         """one picture; slices = [{'first': first_mb_in_slice, 'qp_delta', 'dbk', 'intra'}, ...] (first 0 first,
         increasing; a key left out takes the picture-wide argument) -> the RBSP of each slice in
-        raster order (the single-slice default returns one)"""
+        raster order (the single-slice default returns one). script = {macroblock address: spec} writes those
+        macroblocks as told instead of drawing them: {'kind': 'pcm', 'samples': 384 values}, {'kind': 'i16', 'mode': m,
+        'dq': d} (no coefficients), {'kind': 'skip'}, or any {'kind': k} of the mix with random content"""
         rng = self.rng
         mbw, mbh = self.mbw, self.mbh
         slices = slices or [{'first': 0}]
@@ -389,6 +406,9 @@ class SyntaxGen:
                     w, run = FastBits(), 0
                     qp = self._header(w, addr, idr, islice, sd.get('qp_delta', qp_delta), sd.get('dbk', dbk), override, reorder, ref_idc)
                 kind = names[int(rng.choice(len(names), p=probs))]
+                self._spec = script.get(addr) if script else None
+                if self._spec is not None:
+                    kind = self._spec['kind']
                 if islice and kind in ('skip', 'p16', 'p16x8', 'p8x16', 'p8x8'):
                     kind = 'i4'
                 if kind == 'skip':
