@@ -100,6 +100,48 @@ int h264mi_enc_set_slices(h264mi_encoder *e, int n);
 int h264mi_enc_slices(h264mi_encoder *e);
 /* host only: the first MB row of slice k of a picture of mbh MB rows in n slices; mbh for k == n; -1 on bad arguments */
 int h264mi_slice_first_row(int mbh, int n, int k);
+/* Per-frame distortion on the device. Of a pair of w x h 4:2:0 pictures (a, b), per plane
+   (Y w x h; Cb, Cr w/2 x h/2):
+     sse       the sum of squared differences over every sample of the plane;
+     ssim_fix  the sum over the plane's windows of llrint(ssim_window * 2^32). A window is 8x8 samples at stride 4
+               in both directions: x = 0, 4, .. <= pw - 8, y = 0, 4, .. <= ph - 8 (samples right of / below the last
+               window count in sse only). With s1 = sum a, s2 = sum b, ss = sum a^2 + sum b^2, s12 = sum ab over its
+               64 sample pairs, c1 = 416, c2 = 235963, all in int64: vars = 64 ss - s1^2 - s2^2, covar = 64 s12 - s1 s2,
+               ssim_window = (double)((2 s1 s2 + c1)(2 covar + c2)) / (double)((s1^2 + s2^2 + c1)(vars + c2)).
+   Every step is exact integer arithmetic or one correctly rounded IEEE-754 double operation and the sums are
+   integer, so the record is bit-identical from run to run and to a restatement on any host.
+   Mean SSIM of a plane = ssim_fix / (windows * 2^32); PSNR = h264mi_psnr(sse, samples of the plane). */
+typedef struct h264mi_quality {
+    uint64_t sse[3];       /* Y, Cb, Cr */
+    int64_t  ssim_fix[3];  /* Y, Cb, Cr */
+    uint32_t windows[2];   /* windows per luma plane, per chroma plane */
+    uint32_t coded;        /* encoder: 1 = the stats of a coded frame; 0 = the step coded nothing, every other field 0 */
+    uint32_t reserved;     /* 0 */
+} h264mi_quality;          /* 64 bytes */
+/* async on hip_stream: n pairs of tight I420 frames (d_a, d_b: n frames of w * h * 3 / 2 bytes back to back, any
+   alignment) into d_out[n] (device, 8-byte aligned), coded = 1. One launch behind a clearing of d_out on the same
+   stream. Returns 0, or -1 on a bad argument (a null pointer, n <= 0, w or h odd or below 16), which is checked
+   before the device is touched. */
+int h264mi_i420_quality_dev(h264mi_quality *d_out, const void *d_a, const void *d_b, int w, int h, int n, void *hip_stream);
+/* host only: 10 log10(255^2 samples / sse) in dB; 100.0 when sse == 0 */
+double h264mi_psnr(uint64_t sse, uint64_t samples);
+/* The encoder's own records: while on, every frame step appends one launch on the encoder's stream that compares
+   each stream's source frame with the display area of the deblocked reconstruction of that step (what a decoder
+   shows) and writes nstreams records in the encoder's memory. A stream whose step published 0 NAL bytes (a
+   rate-control skip, a failed frame) gets coded = 0 and zeros. Off by default, or H264MI_ENC_QUALITY=1 at
+   creation; takes effect from the next h264mi_enc_encode; off: no launch, the step is unchanged. The NAL bytes,
+   the reconstruction and the rate control do not depend on it. While it is on, the source frames passed to
+   h264mi_enc_encode are read until the end of that step's work on the stream (its last launch): overwrite them
+   in stream order, as before. Returns 0; -1 on a null encoder or one below 16x16.
+   h264mi_enc_quality_enabled: 1 / 0, -1 on a null encoder. */
+int h264mi_enc_set_quality(h264mi_encoder *e, int enable);
+int h264mi_enc_quality_enabled(h264mi_encoder *e);
+/* sync; the last frame step's record of one stream (coded 0 and zeros before the first step after turning it on).
+   Returns 0; -1 when the option is off or on a bad argument */
+int h264mi_enc_quality(h264mi_encoder *e, int stream, h264mi_quality *out);
+/* the nstreams records on the device, rewritten by every frame step in stream order, for consumers that do not
+   synchronise the host; NULL when the option is off */
+const h264mi_quality *h264mi_enc_quality_dev(h264mi_encoder *e);
 /* test hook: the next coded frame of stream fails as if its kernels had reported error code (> 0): it
    publishes 0 NAL bytes and the frame after it is an IDR. Code 3 fails it through enc_pack_kernel's
    RBSP-overflow branch itself (the early exit before the slice is assembled) */

@@ -162,6 +162,23 @@ int h264mi_slice_first_row(int mbh, int n, int k) {
     if (mbh < 1 || !slices_valid(mbh, n) || k < 0 || k > n) return -1;
     return slice_first_row(mbh, n, k);
 }
+// Per-frame distortion records (DESIGN.md §5.2; runtime_enc.inc enc_set_quality)
+int h264mi_enc_set_quality(h264mi_encoder *e, int enable) { return e ? enc_set_quality(e->c, enable != 0) : -1; }
+int h264mi_enc_quality_enabled(h264mi_encoder *e) { return e ? (e->c->quality ? 1 : 0) : -1; }
+int h264mi_enc_quality(h264mi_encoder *e, int stream, h264mi_quality *out) {
+    if (!e || !out || !e->c->quality || stream < 0 || stream >= e->c->S) return -1;
+    if (hipMemcpyAsync(out, e->c->d_qual + stream, sizeof(h264mi_quality), hipMemcpyDeviceToHost, e->c->stream) != hipSuccess) return -1;
+    return hipStreamSynchronize(e->c->stream) == hipSuccess ? 0 : -1;
+}
+const h264mi_quality *h264mi_enc_quality_dev(h264mi_encoder *e) { return e && e->c->quality ? e->c->d_qual : nullptr; }
+int h264mi_i420_quality_dev(h264mi_quality *d_out, const void *d_a, const void *d_b, int w, int h, int n, void *hip_stream) {
+    if (!d_out || !d_a || !d_b || !quality_args_ok(w, h, n)) return -1;
+    return launch_quality_i420(d_out, (const uint8_t *)d_a, (const uint8_t *)d_b, w, h, n, (hipStream_t)hip_stream);
+}
+double h264mi_psnr(uint64_t sse, uint64_t samples) {
+    if (sse == 0) return 100.0;
+    return 10.0 * log10(65025.0 * (double)samples / (double)sse);
+}
 int h264mi_enc_inject_error(h264mi_encoder *e, int stream, int code) {
     if (!e || stream < 0 || stream >= e->c->S || code <= 0) return -1;
     if (hipMemcpyAsync(&e->c->d_st[stream].inject_err, &code, sizeof(int), hipMemcpyHostToDevice, e->c->stream) != hipSuccess) return -1;

@@ -167,6 +167,9 @@ struct EncCtx {
     int sgrp = 0;                // enc_mb_kernel: streams per ticket group of a queue (EncLaunch::sgrp; 0: all)
     bool gom_exact = false;      // OpenH264's GOM QP rule (h264mi_enc_set_gom_exact; enc_bits.inc gom_row_qp)
     int slices = 1;              // slices per picture from the next frame step on (h264mi_enc_set_slices; BeginLaunch::slices)
+    bool quality = false;        // per-frame distortion records from the next frame step on (h264mi_enc_set_quality)
+    h264mi_quality *d_qual = nullptr;  // S records (quality.hip), allocated when the option is first turned on: an
+                                       // encoder that never uses it holds exactly the memory it held before
     std::vector<EncDesc> h_desc[2];
     int parity = 0;
     // host-side output staging (C-ABI path)
@@ -199,10 +202,24 @@ static void enc_free(EncCtx *c) {
 
     for (auto e : c->ev) (void)hipEventDestroy(e);
     (void)hipFree(c->d_pool);
+    (void)hipFree(c->d_qual);
     (void)hipFree(c->d_prof);
     (void)hipFree(c->d_tl);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
+}
+
+// Per-frame distortion records (DESIGN.md §5.2): one host flag; a frame step issued while it is set appends
+// quality_kernel on the encoder's stream. Turning it on clears the records (in stream order), so that what is read
+// before the next step says "nothing coded" instead of showing an earlier frame's figures
+static int enc_set_quality(EncCtx *c, bool on) {
+    if (c->w < 16 || c->h < 16) return -1;
+    if (on && !c->quality) {
+        if (!c->d_qual && hipMalloc(&c->d_qual, sizeof(h264mi_quality) * (size_t)c->S) != hipSuccess) { c->d_qual = nullptr; return -1; }
+        if (hipMemsetAsync(c->d_qual, 0, sizeof(h264mi_quality) * (size_t)c->S, c->stream) != hipSuccess) return -1;
+    }
+    c->quality = on;
+    return 0;
 }
 
 // a picture of mbh MB rows can be coded as n slices of whole MB rows (h264mi_dev.h slice_first_row)
@@ -338,12 +355,19 @@ static EncCtx *enc_create(int w, int h, int bitrate, int S, hipStream_t stream) 
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
             c->ncu = n;
     }
+    if (const char *e = getenv("H264MI_ENC_QUALITY")) (void)enc_set_quality(c, atoi(e) != 0);  // refused below 16x16
     if (getenv("H264MI_ENC_TL") && hipMalloc(&c->d_tl, 4 * (size_t)S * c->mbh * sizeof(uint64_t)) == hipSuccess)
         (void)hipMemset(c->d_tl, 0, 4 * (size_t)S * c->mbh * sizeof(uint64_t));
     if (getenv("H264MI_ENC_PROF") && hipMalloc(&c->d_prof, 64 * sizeof(uint64_t)) == hipSuccess)
         (void)hipMemset(c->d_prof, 0, 64 * sizeof(uint64_t));  // 0..15 + 32..51 enc_mb_kernel, 16..21 deblocking rows
     return c;
 }
+
+// quality.hip (a translation unit of its own)
+int launch_quality_enc(h264mi_quality *d_out, const uint8_t *d_frames, size_t fbytes, int w, int h, int cw, const EncDesc *desc, int S,
+                       hipStream_t s);
+int launch_quality_i420(h264mi_quality *d_out, const uint8_t *a, const uint8_t *b, int w, int h, int n, hipStream_t s);
+bool quality_args_ok(int w, int h, int n);
 
 // One frame step for all S streams. src: S tight I420 frames, contiguous, in device memory.
 static int enc_frame(EncCtx *c, const uint8_t *d_frames) {
@@ -381,6 +405,9 @@ static int enc_frame(EncCtx *c, const uint8_t *d_frames) {
     // (the pack of a multi-slice frame is a kernel of its own: c->slices is what this step's begin kernel latches)
     if (launch_enc_post(PackLaunch{c->mbw, c->mbh, c->S, c->d_desc[par]}, c->cw, c->ch, c->d_pd[par], c->stream, c->slices > 1) != 0) return -1;
     HIPCHECK(hipGetLastError());
+    // the frame's distortion, behind the pack (its NAL byte counts) and the deblocking rows: the source against the
+    // display area of this parity's deblocked pictures (quality.hip)
+    if (c->quality && launch_quality_enc(c->d_qual, d_frames, c->fbytes, c->w, c->h, c->cw, c->d_desc[par], c->S, c->stream) != 0) return -1;
     c->parity ^= 1;
     return 0;
 }

@@ -124,6 +124,12 @@ def lib():
             'h264mi_version': (cp, []),
             'h264mi_enc_rows_counter': (vp, [vp]),
             'h264mi_dec_set_recon_gate': (i, [vp, vp, ctypes.c_uint32, ctypes.c_uint32, i, i]),
+            'h264mi_i420_quality_dev': (i, [vp, vp, vp, i, i, i, vp]),
+            'h264mi_psnr': (ctypes.c_double, [ctypes.c_uint64, ctypes.c_uint64]),
+            'h264mi_enc_set_quality': (i, [vp, i]),
+            'h264mi_enc_quality_enabled': (i, [vp]),
+            'h264mi_enc_quality': (i, [vp, i, vp]),
+            'h264mi_enc_quality_dev': (vp, [vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -261,6 +267,28 @@ def slice_first_row(mbh, n, k):
     return lib().h264mi_slice_first_row(int(mbh), int(n), int(k))
 
 
+class Quality(ctypes.Structure):
+    """h264mi_quality (include/h264mi.h): one picture pair's distortion record, 64 bytes"""
+    _fields_ = [('sse', ctypes.c_uint64 * 3), ('ssim_fix', ctypes.c_int64 * 3), ('windows', ctypes.c_uint32 * 2),
+                ('coded', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+    def as_dict(self, w, h):
+        """the record of a w x h pair as {'coded', 'sse', 'ssim_fix', 'windows', 'psnr', 'ssim'}; psnr (dB,
+        h264mi_psnr) and ssim (the mean over the windows) per plane Y, Cb, Cr, None where nothing was coded"""
+        coded = int(self.coded)
+        samples = (w * h, (w // 2) * (h // 2), (w // 2) * (h // 2))
+        win = (self.windows[0], self.windows[1], self.windows[1])
+        sse, fix = [int(v) for v in self.sse], [int(v) for v in self.ssim_fix]
+        return {'coded': coded, 'sse': sse, 'ssim_fix': fix, 'windows': [int(v) for v in self.windows],
+                'psnr': [psnr(sse[p], samples[p]) for p in range(3)] if coded else None,
+                'ssim': [fix[p] / (win[p] * 4294967296.0) for p in range(3)] if coded else None}
+
+
+def psnr(sse, samples):
+    """10 log10(255^2 samples / sse) in dB, 100.0 when sse == 0 (h264mi_psnr; host only)"""
+    return lib().h264mi_psnr(int(sse), int(samples))
+
+
 class BatchEncoder:
     """S independent encoder streams of one geometry, frames and NAL units resident in HBM."""
 
@@ -316,6 +344,28 @@ class BatchEncoder:
     def slices(self):
         """slices per picture in force for the next encode (h264mi_enc_slices)"""
         return self._L.h264mi_enc_slices(self._e)
+
+    def set_quality(self, on):
+        """per-frame SSE / SSIM records of every stream from the next encode on (h264mi_enc_set_quality): one more
+        launch per frame step, nothing else changes; ValueError for an encoder below 16x16"""
+        if self._L.h264mi_enc_set_quality(self._e, 1 if on else 0) != 0:
+            raise ValueError('h264mi_enc_set_quality refused')
+
+    def quality_enabled(self):
+        return self._L.h264mi_enc_quality_enabled(self._e) == 1
+
+    def quality(self, s=0):
+        """stream s's record of the last frame step (synchronises; h264mi_enc_quality) as a dict: 'sse' and
+        'ssim_fix' (the exact integers), 'windows', 'coded' (0: the step coded nothing, all zeros), and per plane
+        'psnr' (dB) and 'ssim' (mean), None when nothing was coded. RuntimeError while the option is off."""
+        q = Quality()
+        if self._L.h264mi_enc_quality(self._e, s, ctypes.byref(q)) != 0:
+            raise RuntimeError('h264mi_enc_quality failed (set_quality(True) first)')
+        return q.as_dict(self.w, self.h)
+
+    def quality_ptr(self):
+        """device address of the S records (h264mi_enc_quality_dev; 64 bytes each), None while the option is off"""
+        return self._L.h264mi_enc_quality_dev(self._e)
 
     def gom_state(self, s=0):
         """exact GOM mode: the last P frame's per-GOM [QP, slice bits before it, target bits, last coded MB + 1]
@@ -660,6 +710,28 @@ def rgba_to_i420(dst, src, w, h, n, stream=None):
 def i420_to_rgba(dst, src, w, h, n, stream=None):
     """n tight I420 frames (uint8 CUDA tensor src) to n tight RGBA8 frames (dst, A = 255); h264mi_i420_to_rgba_dev"""
     _convert_dev(lib().h264mi_i420_to_rgba_dev, dst, src, w * h * 4, w * h * 3 // 2, w, h, n, stream)
+
+
+def i420_quality(out, a, b, w, h, n, stream=None):
+    """distortion records of n pairs of tight I420 frames (uint8 CUDA tensors a, b, any alignment) into out (a CUDA
+    tensor of at least 64 * n bytes, 8-byte aligned: n h264mi_quality records), one launch, async on stream
+    (default: the current one); h264mi_i420_quality_dev. Read them with quality_records()."""
+    import torch
+    assert out.is_cuda and a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8
+    assert out.is_contiguous() and a.is_contiguous() and b.is_contiguous()
+    fb = w * h + 2 * (w // 2) * (h // 2)
+    assert n <= 0 or (out.numel() * out.element_size() >= 64 * n and a.numel() >= n * fb and b.numel() >= n * fb)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_i420_quality_dev(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()),
+                                     w, h, n, ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {w}x{h}, {n} pairs')
+
+
+def quality_records(out, n):
+    """the first n records of a tensor written by i420_quality, copied to the host as Quality structures
+    (synchronises through the copy)"""
+    raw = out.view(-1).cpu().numpy().tobytes()
+    return [Quality.from_buffer_copy(raw[64 * k:64 * k + 64]) for k in range(n)]
 
 
 def version():

@@ -1,4 +1,5 @@
 // block_excl_scan (enc_bits.inc) against a host scan: max and sum, random inputs with -1s
+// (link with openh264-wasm_amd/csrc/quality.hip, the library's second translation unit)
 #include "../../openh264-wasm_amd/csrc/h264mi_kernels.hip"
 #include <cstdio>
 #include <vector>
