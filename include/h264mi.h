@@ -158,6 +158,16 @@ size_t h264mi_enc_frame_bytes(h264mi_encoder *e);
    area on its stream, then the same frame step -- rate control, slices, exact GOM and inject_error as there */
 int h264mi_enc_encode_rgba(h264mi_encoder *e, const void *d_rgba_frames);
 size_t h264mi_enc_rgba_frame_bytes(h264mi_encoder *e);
+/* async, as h264mi_enc_encode, from nstreams tight I420 frames of src_w x src_h back to back (device, any
+   alignment) that are larger than the encoder's pictures: one batched area-average downscale
+   (h264mi_i420_scale_dev) into the encoder's input area on its stream, then the same frame step -- rate control,
+   slices, exact GOM, inject_error and the quality records as there; the records compare the scaled source with
+   the reconstruction. The source frames are read by the scale launch only. src_w x src_h equal to the encoder's
+   size copies the frames. Returns -1 and enqueues nothing -- the encoder's next step is as if the call had not
+   happened -- on a null pointer, a source smaller than the encoder in either direction, an odd source (or
+   encoder) size, a source size above 4096, or frames that overlap the encoder's input area. One ladder: a
+   1080p encoder fed by h264mi_enc_encode and 720p / 540p / 360p encoders fed from the same buffer by this. */
+int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w, int src_h);
 int h264mi_enc_last_qp(h264mi_encoder *e, int stream);
 /* the rate control's state after the last frame step (RC_BITRATE_MODE restated from h264.wasm),
    16 int32 in the oracle's h264o_enc_rc_state order: {skipped, QP, average QP, target bits, remaining bits,
@@ -329,6 +339,18 @@ int h264mi_i420_to_rgba_host(const unsigned char *i420, int width, int height, u
    pointer, w or h odd or <= 0, n <= 0), which is checked before the device is touched. */
 int h264mi_rgba_to_i420_dev(void *d_i420, const void *d_rgba, int w, int h, int n, void *hip_stream);
 int h264mi_i420_to_rgba_dev(void *d_rgba, const void *d_i420, int w, int h, int n, void *hip_stream);
+/* Area-average downscaling on the device, async on hip_stream: n tight sw x sh I420 frames back to
+   back at d_src (any alignment) to n tight dw x dh frames at d_dst, one launch. Every plane is scaled on its own
+   (Y sw x sh -> dw x dh; Cb, Cr sw/2 x sh/2 -> dw/2 x dh/2). For a plane of pw x ph samples scaled to qw x qh:
+     wx(i, ox) = max(0, min((i+1) qw, (ox+1) pw) - max(i qw, ox pw))   source column i in output column ox
+     wy(j, oy) = max(0, min((j+1) qh, (oy+1) ph) - max(j qh, oy ph))   source row j in output row oy
+     out(ox, oy) = (sum_j sum_i wy wx p(i, j) + ((pw ph) >> 1)) / (pw ph)   floor division: rounds half up
+   Exact integers (the numerator is below 2^32 for pw, ph <= 4096), so the bytes are the same from run to run and
+   equal a restatement on any host; equal sizes return the source bytes, 2:1 both ways gives (a + b + c + d + 2) >> 2.
+   Returns 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer, n <= 0, an
+   odd size, dw outside 2..sw, dh outside 2..sh, sw or sh above 4096, or source and destination byte ranges that
+   overlap. Upscaling and other filters are not provided. */
+int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, void *hip_stream);
 
 /* library self-description */
 const char *h264mi_version(void);

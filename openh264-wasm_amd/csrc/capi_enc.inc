@@ -202,6 +202,21 @@ int h264mi_enc_encode_rgba(h264mi_encoder *e, const void *d_rgba_frames) {
     if (launch_rgba_to_i420((const uint8_t *)d_rgba_frames, c->w, c->h, c->S, c->d_src, c->stream) != 0) return -1;
     return enc_frame(c, c->d_src);
 }
+// Area-average downscaling (DESIGN.md §5.3; scale.hip): n tight I420 frames of one geometry pair, one launch
+int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, void *hip_stream) {
+    if (!d_dst || !d_src || !scale_args_ok(dw, dh, sw, sh, n) || scale_ranges_overlap(d_dst, dw, dh, d_src, sw, sh, n)) return -1;
+    return launch_scale_i420((uint8_t *)d_dst, dw, dh, (const uint8_t *)d_src, sw, sh, n, (hipStream_t)hip_stream);
+}
+// nstreams tight src_w x src_h I420 frames back to back: one batched downscale into the encoder's own input area on
+// its stream, then the frame step as h264mi_enc_encode runs it (the quality records then see the scaled source).
+// Every refusal comes before the first launch
+int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w, int src_h) {
+    if (!e || !d_frames) return -1;
+    EncCtx *c = e->c;
+    if (!scale_args_ok(c->w, c->h, src_w, src_h, c->S) || scale_ranges_overlap(c->d_src, c->w, c->h, d_frames, src_w, src_h, c->S)) return -1;
+    if (launch_scale_i420(c->d_src, c->w, c->h, (const uint8_t *)d_frames, src_w, src_h, c->S, c->stream) != 0) return -1;
+    return enc_frame(c, c->d_src);
+}
 const void *h264mi_enc_input_buffer(h264mi_encoder *e) { return e ? e->c->d_src : nullptr; }
 size_t h264mi_enc_frame_bytes(h264mi_encoder *e) { return e ? e->c->fbytes : 0; }
 size_t h264mi_enc_rgba_frame_bytes(h264mi_encoder *e) { return e ? (size_t)e->c->w * e->c->h * 4 : 0; }

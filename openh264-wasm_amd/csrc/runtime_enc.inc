@@ -368,6 +368,10 @@ int launch_quality_enc(h264mi_quality *d_out, const uint8_t *d_frames, size_t fb
                        hipStream_t s);
 int launch_quality_i420(h264mi_quality *d_out, const uint8_t *a, const uint8_t *b, int w, int h, int n, hipStream_t s);
 bool quality_args_ok(int w, int h, int n);
+// scale.hip (likewise)
+int launch_scale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, hipStream_t s);
+bool scale_args_ok(int dw, int dh, int sw, int sh, int n);
+bool scale_ranges_overlap(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n);
 
 // One frame step for all S streams. src: S tight I420 frames, contiguous, in device memory.
 static int enc_frame(EncCtx *c, const uint8_t *d_frames) {

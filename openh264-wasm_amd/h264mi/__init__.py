@@ -130,6 +130,8 @@ def lib():
             'h264mi_enc_quality_enabled': (i, [vp]),
             'h264mi_enc_quality': (i, [vp, i, vp]),
             'h264mi_enc_quality_dev': (vp, [vp]),
+            'h264mi_i420_scale_dev': (i, [vp, i, i, vp, i, i, i, vp]),
+            'h264mi_enc_encode_scaled': (i, [vp, vp, i, i]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -316,6 +318,15 @@ class BatchEncoder:
         assert frames.is_cuda and frames.numel() >= self.S * self.rgba_frame_bytes
         if self._L.h264mi_enc_encode_rgba(self._e, ctypes.c_void_p(frames.data_ptr())) != 0:
             raise RuntimeError('h264mi_enc_encode_rgba failed')
+
+    def encode_scaled(self, frames, src_w, src_h):
+        """frames: uint8 CUDA tensor holding S tight I420 frames of src_w x src_h back to back, any alignment
+        (async): one batched area-average downscale (i420_scale) into the encoder's input area on its stream, then
+        the frame step of encode(); the quality records then compare the scaled source with the reconstruction.
+        ValueError, with nothing enqueued, for a source smaller than the encoder, an odd size or one above 4096."""
+        assert frames.is_cuda and frames.numel() >= self.S * (src_w * src_h + 2 * (src_w // 2) * (src_h // 2))
+        if self._L.h264mi_enc_encode_scaled(self._e, ctypes.c_void_p(frames.data_ptr()), int(src_w), int(src_h)) != 0:
+            raise ValueError(f'h264mi_enc_encode_scaled refused {src_w}x{src_h} -> {self.w}x{self.h}')
 
     def force_idr(self, stream=-1):
         self._L.h264mi_enc_force_idr(self._e, stream)
@@ -710,6 +721,22 @@ def rgba_to_i420(dst, src, w, h, n, stream=None):
 def i420_to_rgba(dst, src, w, h, n, stream=None):
     """n tight I420 frames (uint8 CUDA tensor src) to n tight RGBA8 frames (dst, A = 255); h264mi_i420_to_rgba_dev"""
     _convert_dev(lib().h264mi_i420_to_rgba_dev, dst, src, w * h * 4, w * h * 3 // 2, w, h, n, stream)
+
+
+def i420_scale(dst, src, sw, sh, dw, dh, n, stream=None):
+    """n tight sw x sh I420 frames (uint8 CUDA tensor src, any alignment) area-averaged down to n tight dw x dh
+    frames (dst), one launch, async on stream (default: the current one); h264mi_i420_scale_dev. Exact integers:
+    the bytes equal tests/scaleref.py's. ValueError on a bad argument (odd sizes, dw > sw, dh > sh, a source above
+    4096, n <= 0, overlapping buffers)."""
+    import torch
+    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
+    assert dst.is_contiguous() and src.is_contiguous()
+    sfb, dfb = sw * sh + 2 * (sw // 2) * (sh // 2), dw * dh + 2 * (dw // 2) * (dh // 2)
+    assert n <= 0 or min(sw, sh, dw, dh) <= 0 or (dst.numel() >= n * dfb and src.numel() >= n * sfb)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_i420_scale_dev(ctypes.c_void_p(dst.data_ptr()), dw, dh, ctypes.c_void_p(src.data_ptr()), sw, sh, n,
+                                   ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {sw}x{sh} -> {dw}x{dh}, {n} frames')
 
 
 def i420_quality(out, a, b, w, h, n, stream=None):
