@@ -352,6 +352,57 @@ int h264mi_i420_to_rgba_dev(void *d_rgba, const void *d_i420, int w, int h, int 
    overlap. Upscaling and other filters are not provided. */
 int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, void *hip_stream);
 
+/* Several pictures into one on the device: a gallery of decoded streams, one composed picture per
+   receiver, a letterboxed or cropped rendition. A cell takes a crop of one source frame to a rectangle of one canvas. */
+typedef struct h264mi_cell {
+    int32_t src;             /* source frame, 0 .. nsrc - 1 */
+    int32_t canvas;          /* canvas, 0 .. ncanvas - 1 */
+    int32_t sx, sy, sw, sh;  /* crop: a rectangle of the source frame */
+    int32_t dx, dy, dw, dh;  /* where it goes: a rectangle of the canvas */
+} h264mi_cell;               /* 40 bytes */
+/* async on hip_stream. Sources: nsrc tight src_w x src_h I420 frames back to back at d_src; canvases: ncanvas tight
+   cw x ch I420 frames back to back at d_canvas; both at any alignment. For every cell and every plane the destination
+   rectangle of the canvas plane receives the area average of the cropped source plane: exactly the formula of
+   h264mi_i420_scale_dev above, with pw x ph = the crop's size in that plane (sw x sh luma, sw/2 x sh/2 chroma, the
+   crop's origin halved for chroma) and qw x qh = the rectangle's size in that plane. dw == sw && dh == sh copies the
+   crop. Every canvas byte outside the cells' rectangles keeps its value. A source may feed any number of cells.
+   cells is a host array: it is read before the call returns and may be freed then; it travels to the device as
+   kernel arguments, 64 cells to a launch, further cells in further launches on the same stream.
+   Returns 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer; ncanvas, nsrc or
+   ncells <= 0, or ncells > 4096; any odd value among the sizes and the eight rectangle fields; src_w or src_h above
+   4096, or a canvas side above 8192; a crop not inside the source, or a rectangle not inside the canvas; dw outside
+   2..sw or dh outside 2..sh; src or canvas out of range; two cells of one canvas whose rectangles share a sample;
+   source and canvas byte ranges that overlap. A picture-in-picture is two calls in stream order, not overlapping
+   cells. Upscaling, blending and per-source geometries within one call are not provided. */
+int h264mi_i420_compose_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,
+                            const h264mi_cell *cells, int ncells, void *hip_stream);
+/* async on hip_stream: every Y sample of n tight w x h I420 frames at d_frames (any alignment) is set to y, every Cb
+   sample to cb, every Cr sample to cr. Returns -1 on a null pointer, n <= 0, an odd or non-positive size, a side above
+   8192, or a value outside 0..255. */
+int h264mi_i420_fill_dev(void *d_frames, int w, int h, int n, int y, int cb, int cr, void *hip_stream);
+/* host only: the gallery layout of n whole src_w x src_h sources on canvas 0 of cw x ch, into out[0 .. n - 1]. All
+   arithmetic is integers, all divisions floor divisions. cols = the smallest c with c * c >= n, rows = (n + cols - 1)
+   / cols; source k goes to slot column k % cols, slot row k / cols. The slot is [X0, X1) x [Y0, Y1) with
+   X0 = 2 * (col * cw / (2 * cols)), X1 = 2 * ((col + 1) * cw / (2 * cols)), Y0 and Y1 likewise from row, ch, rows. The
+   picture inside the slot keeps the source's shape and is never enlarged:
+     dw = min(src_w, X1 - X0, 2 * ((Y1 - Y0) * src_w / (2 * src_h)))
+     dh = min(src_h, Y1 - Y0, 2 * (dw * src_h / (2 * src_w)))
+   and is centred: dx = X0 + 2 * ((X1 - X0 - dw) / 4), dy = Y0 + 2 * ((Y1 - Y0 - dh) / 4). The crop is the whole source.
+   Returns n, or -1 on a bad argument (a null pointer, n <= 0 or above 4096, sizes that h264mi_i420_compose_dev
+   refuses), on cap < n, or when some dw or dh comes out below 2. 16 sources of 1920x1080 on a 1920x1080 canvas are
+   480x270 cells at multiples of (480, 270); one 64x36 source on 48x48 is a 48x26 cell at (0, 10). */
+int h264mi_mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch);
+/* async, as h264mi_enc_encode_scaled, but the canvases are the encoder's nstreams input frames (cw x ch = the
+   encoder's size, ncanvas = nstreams). With bg_y >= 0 one fill launch first sets the whole input area to the
+   background (bg_y, bg_cb, bg_cr); then the compose launch(es), then the normal frame step, everything on the
+   encoder's stream. With bg_y < 0 no fill runs and uncovered samples keep what the input area held. Rate control,
+   slices, exact GOM, inject_error and the quality records behave as in h264mi_enc_encode; the records compare the
+   composed picture with the reconstruction. Returns -1 and enqueues nothing -- the encoder's next step is as if the
+   call had not happened -- on everything h264mi_i420_compose_dev refuses, a background component above 255 (or, with
+   bg_y >= 0, a negative bg_cb or bg_cr), and sources that overlap the input area. */
+int h264mi_enc_encode_composed(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc,
+                               const h264mi_cell *cells, int ncells, int bg_y, int bg_cb, int bg_cr);
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -217,6 +217,36 @@ int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w,
     if (launch_scale_i420(c->d_src, c->w, c->h, (const uint8_t *)d_frames, src_w, src_h, c->S, c->stream) != 0) return -1;
     return enc_frame(c, c->d_src);
 }
+// Several pictures into one (DESIGN.md §5.4; compose.hip): every cell's crop of a source frame area-averaged into its
+// rectangle of a canvas, 64 cells to a launch
+int h264mi_i420_compose_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,
+                            const h264mi_cell *cells, int ncells, void *hip_stream) {
+    if (!d_canvas || !d_src || !compose_args_ok(cw, ch, ncanvas, src_w, src_h, nsrc, cells, ncells) ||
+        compose_ranges_overlap(d_canvas, cw, ch, ncanvas, d_src, src_w, src_h, nsrc))
+        return -1;
+    return launch_compose_i420((uint8_t *)d_canvas, cw, ch, (const uint8_t *)d_src, src_w, src_h, cells, ncells, (hipStream_t)hip_stream);
+}
+int h264mi_i420_fill_dev(void *d_frames, int w, int h, int n, int y, int cb, int cr, void *hip_stream) {
+    if (!d_frames || !fill_args_ok(w, h, n, y, cb, cr)) return -1;
+    return launch_fill_i420((uint8_t *)d_frames, w, h, n, y, cb, cr, (hipStream_t)hip_stream);
+}
+int h264mi_mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch) {
+    return mosaic_cells(out, cap, n, src_w, src_h, cw, ch);
+}
+// the encoder's nstreams input frames as the canvases: an optional fill, the compose launch(es), then the frame step
+// as h264mi_enc_encode runs it, all on the encoder's stream. Every refusal comes before the first launch
+int h264mi_enc_encode_composed(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
+                               int bg_y, int bg_cb, int bg_cr) {
+    if (!e || !d_src) return -1;
+    EncCtx *c = e->c;
+    if (!compose_args_ok(c->w, c->h, c->S, src_w, src_h, nsrc, cells, ncells) ||
+        compose_ranges_overlap(c->d_src, c->w, c->h, c->S, d_src, src_w, src_h, nsrc))
+        return -1;
+    if (bg_y > 255 || bg_cb > 255 || bg_cr > 255 || (bg_y >= 0 && !fill_args_ok(c->w, c->h, c->S, bg_y, bg_cb, bg_cr))) return -1;
+    if (bg_y >= 0 && launch_fill_i420(c->d_src, c->w, c->h, c->S, bg_y, bg_cb, bg_cr, c->stream) != 0) return -1;
+    if (launch_compose_i420(c->d_src, c->w, c->h, (const uint8_t *)d_src, src_w, src_h, cells, ncells, c->stream) != 0) return -1;
+    return enc_frame(c, c->d_src);
+}
 const void *h264mi_enc_input_buffer(h264mi_encoder *e) { return e ? e->c->d_src : nullptr; }
 size_t h264mi_enc_frame_bytes(h264mi_encoder *e) { return e ? e->c->fbytes : 0; }
 size_t h264mi_enc_rgba_frame_bytes(h264mi_encoder *e) { return e ? (size_t)e->c->w * e->c->h * 4 : 0; }

@@ -1,0 +1,314 @@
+// compose.hip -- several I420 pictures into one on the device (gfx950), as include/h264mi.h defines it
+// (h264mi_i420_compose_dev, h264mi_i420_fill_dev, h264mi_mosaic_cells). DESIGN.md §5.4.
+//   compose_kernel : up to H264MI_COMPOSE_CELLS cells per launch -- the standalone call, or sources composed into an
+//                    encoder's input area (h264mi_enc_encode_composed)
+//   fill_kernel    : n tight frames set to one colour
+// A cell takes a crop of one source frame to a rectangle of one canvas. Per plane that is §5.3's area average with
+// pw x ph = the crop's size in the plane and qw x qh = the rectangle's (scale.hip's header has the formula): exact
+// unsigned 32-bit integers for pw, ph <= 4096, the same bytes whatever the order of evaluation.
+// The walk is scale_kernel's: a wave owns a strip of 64 output columns and a segment of H264MI_COMPOSE_ROWS output rows
+// of one plane of one cell and walks the overlapping source rows downward, H264MI_COMPOSE_BATCH rows at a time, a lane
+// per output column. What differs:
+//  * geometry is per cell. The launch's arguments hold the cells and a prefix table of waves per cell; a wave finds its
+//    cell by a binary search of that table (all of it scalar), then plane, strip and segment as the scaler does.
+//  * rows are a pitch apart that is not the plane's width: source rows the source plane's width, destination rows the
+//    canvas plane's. A lane's taps are columns of the source plane row: the crop's first column added to the taps within
+//    the crop.
+//  * a source plane is read as dwords when its base address and its pitch are multiples of 4, whatever the crop's first
+//    column: the aligned dwords that hold the taps lie in the same plane row (the pitch is a multiple of 4 and every tap
+//    is below it), the samples of such a dword that are not taps are masked out or shifted away. Otherwise bytes.
+//  * an output row segment is stored as dwords when its first address is a multiple of 4 -- tested per row, since with a
+//    canvas pitch that is no multiple of 4 it changes from row to row -- and then only the groups of four samples that
+//    lie inside the rectangle; everything else as bytes. Nothing is written outside the rectangle, nothing is read
+//    outside the source frame.
+//
+// A translation unit and a code object of its own, as quality.hip and scale.hip are: the library's other kernels stay
+// byte for byte what they were. The host runtime (capi_enc.inc) reaches it through the functions at the end.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <stdint.h>
+#include "../../include/h264mi.h"
+
+namespace h264mi {
+#define CDEV __device__ __forceinline__
+
+#define H264MI_COMPOSE_ROWS 16          // output rows per wave
+#define H264MI_COMPOSE_BATCH 8          // source rows whose loads are in flight together
+#define H264MI_COMPOSE_CELLS 64         // cells per launch: the argument block is 1.9 KB
+#define H264MI_COMPOSE_MAX_CELLS 4096   // cells per call
+#define H264MI_COMPOSE_MAX_BLOCKS 2048  // 8 blocks of 256 on each of 256 CUs; the rest is a stride loop
+#define H264MI_COMPOSE_MAX_SRC 4096     // source side: 255 * 4096^2 + 4096^2 / 2 < 2^32
+#define H264MI_COMPOSE_MAX_CANVAS 8192  // canvas side: a rectangle field fits 16 bits
+
+struct ComposeCell {  // a cell as the kernel reads it, 24 bytes
+    int32_t src, canvas;
+    uint16_t sx, sy, sw, sh, dx, dy, dw, dh;
+};
+struct ComposeLaunch {
+    const uint8_t *src;
+    uint8_t *dst;
+    size_t sfb, dfb;                           // source frame f: src + f * sfb; canvas c: dst + c * dfb
+    int src_w, src_h, cw, ch;
+    int ncells;
+    int first[H264MI_COMPOSE_CELLS + 1];       // cell k's waves are first[k] .. first[k + 1] - 1
+    ComposeCell cell[H264MI_COMPOSE_CELLS];
+};
+static_assert(sizeof(ComposeLaunch) < 2048, "the argument block stays well below 4 KB");
+
+// the horizontal sums of one output column on H264MI_COMPOSE_BATCH source plane rows: wf p[i0] + qw (p[i0+1] + .. +
+// p[i1-1]) + wl p[i1] each (wl = 0 when i1 == i0), i0 and i1 columns of the plane row, from byte loads. The rows' loads
+// of one tap are independent of each other and issued together.
+CDEV void compose_hsum_bytes(uint32_t *h, const uint8_t *S, const uint32_t *row, int i0, int i1, uint32_t wf, uint32_t wl, uint32_t qw) {
+    uint32_t mid[H264MI_COMPOSE_BATCH];
+#pragma unroll
+    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) mid[r] = 0;
+    for (int i = i0 + 1; i < i1; i++) {
+#pragma unroll
+        for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) mid[r] += S[row[r] + i];
+    }
+#pragma unroll
+    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) h[r] = wf * S[row[r] + i0] + qw * mid[r] + wl * S[row[r] + i1];
+}
+// the same from the aligned dwords i0 / 4 .. i1 / 4 of plane rows that start at a multiple of 4 and are a multiple of
+// 4 long: the taps between the first and the last are summed by v_sad_u8 under a byte mask, which the rows share.
+// Bytes of those dwords below i0 or above i1 (outside the crop, inside the row) are under no mask and in no shift.
+CDEV void compose_hsum_dwords(uint32_t *h, const uint8_t *S, const uint32_t *row, int i0, int i1, uint32_t wf, uint32_t wl, uint32_t qw) {
+    const int d0 = i0 >> 2, d1 = i1 >> 2;
+    uint32_t mid[H264MI_COMPOSE_BATCH], first[H264MI_COMPOSE_BATCH], last[H264MI_COMPOSE_BATCH];
+#pragma unroll
+    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) mid[r] = first[r] = last[r] = 0;
+    for (int d = d0; d <= d1; d++) {
+        uint32_t v[H264MI_COMPOSE_BATCH];
+#pragma unroll
+        for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) v[r] = *(const uint32_t *)(S + row[r] + 4 * d);
+        const int lo = max(i0 + 1 - 4 * d, 0), hi = min(i1 - 1 - 4 * d, 3);  // the dword's bytes between the end taps
+        const uint32_t m = lo <= hi ? (0xffffffffu >> (8 * (3 - hi))) & (0xffffffffu << (8 * lo)) : 0u;
+#pragma unroll
+        for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) {
+            mid[r] = __builtin_amdgcn_sad_u8(v[r] & m, 0u, mid[r]);
+            if (d == d0) first[r] = (v[r] >> (8 * (i0 & 3))) & 255u;
+            if (d == d1) last[r] = (v[r] >> (8 * (i1 & 3))) & 255u;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) h[r] = wf * first[r] + qw * mid[r] + wl * last[r];
+}
+
+// waves across and down a qw x qh rectangle of one plane
+__host__ __device__ static inline int compose_nstrip(int qw) { return (qw + 63) / 64; }
+__host__ __device__ static inline int compose_nseg(int qh) { return (qh + H264MI_COMPOSE_ROWS - 1) / H264MI_COMPOSE_ROWS; }
+
+__global__ __launch_bounds__(256) void compose_kernel(ComposeLaunch a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // scalar: what follows from it is per wave
+    const int items = a.first[a.ncells];
+    for (int it = (int)blockIdx.x * 4 + wave; it < items; it += (int)gridDim.x * 4) {
+        int lo_c = 0, hi_c = a.ncells;  // first[lo_c] <= it < first[hi_c]
+        while (hi_c - lo_c > 1) {
+            const int mid_c = (lo_c + hi_c) >> 1;
+            if (a.first[mid_c] <= it) lo_c = mid_c; else hi_c = mid_c;
+        }
+        const ComposeCell c = a.cell[lo_c];
+        int k = it - a.first[lo_c];  // the wave's index within the cell
+        const int lw = compose_nstrip(c.dw) * compose_nseg(c.dh), cwv = compose_nstrip(c.dw >> 1) * compose_nseg(c.dh >> 1);
+        int p = 0;
+        if (k >= lw) { k -= lw; p = 1; if (k >= cwv) { k -= cwv; p = 2; } }
+        const int sh1 = p != 0;  // chroma: every size and origin halved
+        const int pw = c.sw >> sh1, ph = c.sh >> sh1, qw = c.dw >> sh1, qh = c.dh >> sh1;
+        const int spitch = a.src_w >> sh1, dpitch = a.cw >> sh1;
+        const size_t sy_b = (size_t)a.src_w * a.src_h, sc_b = (size_t)(a.src_w >> 1) * (a.src_h >> 1);
+        const size_t dy_b = (size_t)a.cw * a.ch, dc_b = (size_t)(a.cw >> 1) * (a.ch >> 1);
+        // the source plane, and its row that holds the crop's first row; the rectangle's first sample
+        const uint8_t *P = a.src + (size_t)c.src * a.sfb + (p == 0 ? 0 : p == 1 ? sy_b : sy_b + sc_b);
+        const uint8_t *S = P + (size_t)(c.sy >> sh1) * spitch;
+        uint8_t *D = a.dst + (size_t)c.canvas * a.dfb + (p == 0 ? 0 : p == 1 ? dy_b : dy_b + dc_b) + (size_t)(c.dy >> sh1) * dpitch +
+                     (c.dx >> sh1);
+        const int x0 = c.sx >> sh1;
+        const bool wide = ((((uintptr_t)P) | (uintptr_t)spitch) & 3) == 0;
+        const int nstrip = compose_nstrip(qw);
+        const int strip = k % nstrip, seg = k / nstrip;
+        const int ox = strip * 64 + lane;
+        const bool act = ox < qw;
+        // the lane's taps: columns i0..i1 of the plane row, weights wf, qw, .., qw, wl
+        int i0 = x0, i1 = x0;
+        uint32_t wf = 0, wl = 0;
+        if (act) {
+            const int lo = ox * pw, hi = lo + pw;  // the output column in units of 1 / (pw qw)
+            const int t0 = lo / qw, t1 = (hi + qw - 1) / qw - 1;
+            wf = (uint32_t)(min((t0 + 1) * qw, hi) - lo);
+            wl = t1 > t0 ? (uint32_t)(hi - t1 * qw) : 0u;
+            i0 = x0 + t0;
+            i1 = x0 + t1;
+        }
+        const uint32_t area = (uint32_t)pw * (uint32_t)ph, half = area >> 1;
+        const int oy0 = seg * H264MI_COMPOSE_ROWS, oy1 = min(oy0 + H264MI_COMPOSE_ROWS, qh);
+        const int y0 = (oy0 * ph) / qh, y1 = (oy1 * ph + qh - 1) / qh - 1;  // crop rows y0..y1
+        int oy = oy0;
+        uint32_t acc = 0;
+        for (int yb0 = y0; yb0 <= y1; yb0 += H264MI_COMPOSE_BATCH) {  // a batch of source rows: its loads, then the rows in order
+            uint32_t hs[H264MI_COMPOSE_BATCH];
+#pragma unroll
+            for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) hs[r] = 0;
+            if (act) {
+                uint32_t row[H264MI_COMPOSE_BATCH];  // byte offsets from S; rows beyond y1 read row y1 again and are not used
+#pragma unroll
+                for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) row[r] = (uint32_t)(min(yb0 + r, y1) * spitch);
+                if (wide) compose_hsum_dwords(hs, S, row, i0, i1, wf, wl, (uint32_t)qw);
+                else compose_hsum_bytes(hs, S, row, i0, i1, wf, wl, (uint32_t)qw);
+            }
+#pragma unroll
+            for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) {
+            const int y = yb0 + r;
+            if (y > y1) break;
+            const uint32_t h = hs[r];
+            const int top = oy * ph, bot = top + ph, ya = y * qh, yb = ya + qh;  // the same in every lane
+            acc += (uint32_t)(min(yb, bot) - max(ya, top)) * h;
+            if (yb >= bot) {  // output row oy is complete
+                const uint32_t v = (acc + half) / area;
+                uint8_t *o = D + (size_t)oy * dpitch + strip * 64;  // the strip's first sample of the row
+                if (((uintptr_t)o & 3) == 0) {
+                    uint32_t q = v | (__shfl_down(v, 1) << 8);
+                    q |= __shfl_down(q, 2) << 16;  // lanes 4j: the bytes of lanes 4j .. 4j + 3
+                    if (act) {
+                        const int base = ox & ~3;
+                        if (base + 3 < qw) { if ((lane & 3) == 0) *(uint32_t *)(o + lane) = q; }
+                        else o[lane] = (uint8_t)v;
+                    }
+                } else if (act) {
+                    o[lane] = (uint8_t)v;
+                }
+                oy++;
+                acc = (uint32_t)(yb - bot) * h;  // the rest of a straddling row opens the next one
+            }
+            }
+        }
+    }
+}
+
+// n tight w x h frames at dst set to (y, cb, cr). blockIdx.y is the frame; a thread owns aligned 16-byte pieces of the
+// frame's address range: one inside a plane and inside the frame is one store, any other goes byte by byte, each byte
+// tested against the frame's range (the piece's other bytes are a neighbouring frame's, or nobody's).
+struct FillLaunch {
+    uint8_t *dst;
+    size_t fb, yb, cb;  // bytes of a frame, of its luma plane, of one chroma plane
+    uint32_t v[3];      // the three values, each in all four bytes
+};
+__global__ __launch_bounds__(256) void fill_kernel(FillLaunch a) {
+    const uintptr_t lo = (uintptr_t)a.dst + (size_t)blockIdx.y * a.fb, hi = lo + a.fb;  // the frame's bytes
+    const uintptr_t first = lo & ~(uintptr_t)15;
+    const size_t pieces = (hi - first + 15) >> 4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pieces; i += (size_t)gridDim.x * blockDim.x) {
+        const uintptr_t p = first + (i << 4);
+        if (p >= lo && p + 16 <= hi) {
+            const size_t off = p - lo;  // plane of the piece's first and last byte
+            const int p0 = off < a.yb ? 0 : off < a.yb + a.cb ? 1 : 2, p1 = off + 15 < a.yb ? 0 : off + 15 < a.yb + a.cb ? 1 : 2;
+            if (p0 == p1) {
+                const uint32_t v = a.v[p0];
+                *(uint4 *)p = make_uint4(v, v, v, v);
+                continue;
+            }
+        }
+        for (int b = 0; b < 16; b++) {
+            const uintptr_t q = p + b;
+            if (q < lo || q >= hi) continue;
+            const size_t off = q - lo;
+            *(uint8_t *)q = (uint8_t)a.v[off < a.yb ? 0 : off < a.yb + a.cb ? 1 : 2];
+        }
+    }
+}
+
+static size_t i420_bytes(int w, int h) { return (size_t)w * h + 2 * (size_t)(w / 2) * (h / 2); }
+
+// arguments of a fill call
+bool fill_args_ok(int w, int h, int n, int y, int cb, int cr) {
+    return n > 0 && w > 0 && h > 0 && !((w | h) & 1) && w <= H264MI_COMPOSE_MAX_CANVAS && h <= H264MI_COMPOSE_MAX_CANVAS &&
+           y >= 0 && y <= 255 && cb >= 0 && cb <= 255 && cr >= 0 && cr <= 255;
+}
+int launch_fill_i420(uint8_t *dst, int w, int h, int n, int y, int cb, int cr, hipStream_t s) {
+    FillLaunch a{};
+    a.dst = dst; a.fb = i420_bytes(w, h); a.yb = (size_t)w * h; a.cb = (size_t)(w / 2) * (h / 2);
+    a.v[0] = 0x01010101u * (uint32_t)y; a.v[1] = 0x01010101u * (uint32_t)cb; a.v[2] = 0x01010101u * (uint32_t)cr;
+    const size_t blocks = (a.fb / 16 + 2 + 255) / 256;
+    const unsigned gx = (unsigned)std::min(blocks, (size_t)std::max(1, H264MI_COMPOSE_MAX_BLOCKS / n));
+    (void)hipGetLastError();
+    for (int f0 = 0; f0 < n; f0 += 65535) {  // gridDim.y is 16 bits
+        FillLaunch b = a;
+        b.dst = dst + (size_t)f0 * a.fb;
+        hipLaunchKernelGGL(fill_kernel, dim3(gx, (unsigned)std::min(n - f0, 65535)), dim3(256), 0, s, b);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// arguments of a compose call, everything but the pointers' values: counts, sizes, every cell's fields, and no two
+// cells of one canvas that share a sample
+bool compose_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells) {
+    if (!cells || ncanvas <= 0 || nsrc <= 0 || ncells <= 0 || ncells > H264MI_COMPOSE_MAX_CELLS) return false;
+    if (((cw | ch | src_w | src_h) & 1) || cw < 2 || ch < 2 || src_w < 2 || src_h < 2) return false;
+    if (src_w > H264MI_COMPOSE_MAX_SRC || src_h > H264MI_COMPOSE_MAX_SRC || cw > H264MI_COMPOSE_MAX_CANVAS || ch > H264MI_COMPOSE_MAX_CANVAS)
+        return false;
+    for (int k = 0; k < ncells; k++) {
+        const h264mi_cell &c = cells[k];
+        if (c.src < 0 || c.src >= nsrc || c.canvas < 0 || c.canvas >= ncanvas) return false;
+        if ((c.sx | c.sy | c.sw | c.sh | c.dx | c.dy | c.dw | c.dh) & 1) return false;
+        if (c.sx < 0 || c.sy < 0 || c.sw < 2 || c.sh < 2 || c.sw > src_w - c.sx || c.sh > src_h - c.sy) return false;  // sx <= src_w: no overflow
+        if (c.sx > src_w || c.sy > src_h) return false;
+        if (c.dw < 2 || c.dw > c.sw || c.dh < 2 || c.dh > c.sh) return false;
+        if (c.dx < 0 || c.dy < 0 || c.dx > cw || c.dy > ch || c.dw > cw - c.dx || c.dh > ch - c.dy) return false;
+    }
+    for (int k = 1; k < ncells; k++)
+        for (int j = 0; j < k; j++) {
+            const h264mi_cell &a = cells[k], &b = cells[j];
+            if (a.canvas == b.canvas && a.dx < b.dx + b.dw && b.dx < a.dx + a.dw && a.dy < b.dy + b.dh && b.dy < a.dy + a.dh) return false;
+        }
+    return true;
+}
+// whether the byte ranges of nsrc source frames at src and ncanvas canvases at canvas share a byte
+bool compose_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *src, int src_w, int src_h, int nsrc) {
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)canvas;
+    const uintptr_t sb = (uintptr_t)nsrc * i420_bytes(src_w, src_h), db = (uintptr_t)ncanvas * i420_bytes(cw, ch);
+    return s0 < d0 + db && d0 < s0 + sb;
+}
+// cells (as compose_args_ok accepts them) into the canvases at dst, H264MI_COMPOSE_CELLS to a launch
+int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
+                        hipStream_t s) {
+    ComposeLaunch a{};
+    a.src = src; a.dst = dst; a.sfb = i420_bytes(src_w, src_h); a.dfb = i420_bytes(cw, ch);
+    a.src_w = src_w; a.src_h = src_h; a.cw = cw; a.ch = ch;
+    (void)hipGetLastError();
+    for (int k0 = 0; k0 < ncells; k0 += H264MI_COMPOSE_CELLS) {
+        a.ncells = std::min(ncells - k0, H264MI_COMPOSE_CELLS);
+        a.first[0] = 0;
+        for (int k = 0; k < a.ncells; k++) {
+            const h264mi_cell &c = cells[k0 + k];
+            a.cell[k] = ComposeCell{c.src, c.canvas, (uint16_t)c.sx, (uint16_t)c.sy, (uint16_t)c.sw, (uint16_t)c.sh,
+                                    (uint16_t)c.dx, (uint16_t)c.dy, (uint16_t)c.dw, (uint16_t)c.dh};
+            // at most 128 * 512 + 2 * 64 * 256 waves a cell, 64 cells: far below 2^31
+            a.first[k + 1] = a.first[k] + compose_nstrip(c.dw) * compose_nseg(c.dh) + 2 * compose_nstrip(c.dw / 2) * compose_nseg(c.dh / 2);
+        }
+        const int blocks = (a.first[a.ncells] + 3) / 4;
+        hipLaunchKernelGGL(compose_kernel, dim3((unsigned)std::min(blocks, H264MI_COMPOSE_MAX_BLOCKS)), dim3(256), 0, s, a);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the gallery layout of include/h264mi.h (h264mi_mosaic_cells): host only, integers, floor divisions
+int mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch) {
+    if (!out || n <= 0 || n > H264MI_COMPOSE_MAX_CELLS || cap < n) return -1;
+    if (((cw | ch | src_w | src_h) & 1) || cw < 2 || ch < 2 || src_w < 2 || src_h < 2) return -1;
+    if (src_w > H264MI_COMPOSE_MAX_SRC || src_h > H264MI_COMPOSE_MAX_SRC || cw > H264MI_COMPOSE_MAX_CANVAS || ch > H264MI_COMPOSE_MAX_CANVAS)
+        return -1;
+    int cols = 1;
+    while (cols * cols < n) cols++;
+    const int rows = (n + cols - 1) / cols;
+    for (int k = 0; k < n; k++) {
+        const int col = k % cols, row = k / cols;
+        const int X0 = 2 * (col * cw / (2 * cols)), X1 = 2 * ((col + 1) * cw / (2 * cols));
+        const int Y0 = 2 * (row * ch / (2 * rows)), Y1 = 2 * ((row + 1) * ch / (2 * rows));
+        const int dw = std::min(std::min(src_w, X1 - X0), 2 * ((Y1 - Y0) * src_w / (2 * src_h)));
+        const int dh = std::min(std::min(src_h, Y1 - Y0), 2 * (dw * src_h / (2 * src_w)));
+        if (dw < 2 || dh < 2) return -1;
+        out[k] = h264mi_cell{k, 0, 0, 0, src_w, src_h, X0 + 2 * ((X1 - X0 - dw) / 4), Y0 + 2 * ((Y1 - Y0 - dh) / 4), dw, dh};
+    }
+    return n;
+}
+}  // namespace h264mi

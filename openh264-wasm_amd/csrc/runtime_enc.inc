@@ -372,6 +372,14 @@ bool quality_args_ok(int w, int h, int n);
 int launch_scale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, hipStream_t s);
 bool scale_args_ok(int dw, int dh, int sw, int sh, int n);
 bool scale_ranges_overlap(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n);
+// compose.hip (likewise)
+int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
+                        hipStream_t s);
+int launch_fill_i420(uint8_t *dst, int w, int h, int n, int y, int cb, int cr, hipStream_t s);
+bool compose_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells);
+bool compose_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *src, int src_w, int src_h, int nsrc);
+bool fill_args_ok(int w, int h, int n, int y, int cb, int cr);
+int mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch);
 
 // One frame step for all S streams. src: S tight I420 frames, contiguous, in device memory.
 static int enc_frame(EncCtx *c, const uint8_t *d_frames) {

@@ -132,6 +132,10 @@ def lib():
             'h264mi_enc_quality_dev': (vp, [vp]),
             'h264mi_i420_scale_dev': (i, [vp, i, i, vp, i, i, i, vp]),
             'h264mi_enc_encode_scaled': (i, [vp, vp, i, i]),
+            'h264mi_i420_compose_dev': (i, [vp, i, i, i, vp, i, i, i, vp, i, vp]),
+            'h264mi_i420_fill_dev': (i, [vp, i, i, i, i, i, i, vp]),
+            'h264mi_mosaic_cells': (i, [vp, i, i, i, i, i, i]),
+            'h264mi_enc_encode_composed': (i, [vp, vp, i, i, i, vp, i, i, i, i]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -327,6 +331,19 @@ class BatchEncoder:
         assert frames.is_cuda and frames.numel() >= self.S * (src_w * src_h + 2 * (src_w // 2) * (src_h // 2))
         if self._L.h264mi_enc_encode_scaled(self._e, ctypes.c_void_p(frames.data_ptr()), int(src_w), int(src_h)) != 0:
             raise ValueError(f'h264mi_enc_encode_scaled refused {src_w}x{src_h} -> {self.w}x{self.h}')
+
+    def encode_composed(self, src, src_w, src_h, nsrc, cells, bg=(16, 128, 128)):
+        """src: uint8 CUDA tensor holding nsrc tight I420 frames of src_w x src_h back to back, any alignment; cells: a
+        sequence of Cell whose canvases are this encoder's S input frames (async): with bg = (y, cb, cr) one fill of
+        the whole input area, with bg=None none (uncovered samples keep what the input area held); then every cell's
+        crop area-averaged into its rectangle (i420_compose), then the frame step of encode(), all on the encoder's
+        stream. ValueError, with nothing enqueued, for whatever i420_compose refuses or a background above 255."""
+        assert src.is_cuda and (nsrc <= 0 or min(src_w, src_h) <= 0 or src.numel() >= nsrc * (src_w * src_h + 2 * (src_w // 2) * (src_h // 2)))
+        arr = _cell_array(cells)
+        y, cb, cr = (-1, 0, 0) if bg is None else (int(v) for v in bg)
+        if self._L.h264mi_enc_encode_composed(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
+                                              y, cb, cr) != 0:
+            raise ValueError(f'h264mi_enc_encode_composed refused {len(arr)} cells of {nsrc} sources {src_w}x{src_h} -> {self.w}x{self.h}')
 
     def force_idr(self, stream=-1):
         self._L.h264mi_enc_force_idr(self._e, stream)
@@ -737,6 +754,60 @@ def i420_scale(dst, src, sw, sh, dw, dh, n, stream=None):
     if lib().h264mi_i420_scale_dev(ctypes.c_void_p(dst.data_ptr()), dw, dh, ctypes.c_void_p(src.data_ptr()), sw, sh, n,
                                    ctypes.c_void_p(hs)) != 0:
         raise ValueError(f'bad arguments: {sw}x{sh} -> {dw}x{dh}, {n} frames')
+
+
+class Cell(ctypes.Structure):
+    """h264mi_cell (include/h264mi.h): a crop (sx, sy, sw, sh) of source frame src to a rectangle (dx, dy, dw, dh) of
+    canvas `canvas`, 40 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('src', 'canvas', 'sx', 'sy', 'sw', 'sh', 'dx', 'dy', 'dw', 'dh')]
+
+    def __repr__(self):
+        return 'Cell(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
+
+
+def _cell_array(cells):
+    cells = list(cells)
+    return (Cell * len(cells))(*cells)
+
+
+def mosaic_cells(n, src_w, src_h, cw, ch):
+    """the gallery layout of n whole src_w x src_h sources on canvas 0 of cw x ch as a list of Cell
+    (h264mi_mosaic_cells; host only): the smallest square grid that holds n, every picture as large as its slot allows
+    at the source's shape, never enlarged, centred. ValueError on a bad argument or a cell below 2 samples."""
+    arr = (Cell * max(int(n), 1))()
+    if lib().h264mi_mosaic_cells(arr, len(arr), int(n), int(src_w), int(src_h), int(cw), int(ch)) != n:
+        raise ValueError(f'bad arguments: {n} sources {src_w}x{src_h} on {cw}x{ch}')
+    return list(arr)
+
+
+def i420_compose(canvas, cw, ch, ncanvas, src, src_w, src_h, nsrc, cells, stream=None):
+    """every cell's crop of one of nsrc tight src_w x src_h I420 frames (uint8 CUDA tensor src) area-averaged into its
+    rectangle of one of ncanvas tight cw x ch I420 frames (canvas), any alignment, async on stream (default: the
+    current one); h264mi_i420_compose_dev. Canvas bytes outside the rectangles keep their value. Exact integers: the
+    bytes equal tests/composeref.py's. ValueError on a bad argument (odd fields, a crop outside the source, a rectangle
+    outside the canvas or larger than its crop, overlapping cells of one canvas, overlapping buffers, more than 4096
+    cells)."""
+    import torch
+    assert canvas.is_cuda and src.is_cuda and canvas.dtype == torch.uint8 and src.dtype == torch.uint8
+    assert canvas.is_contiguous() and src.is_contiguous()
+    sfb, cfb = src_w * src_h + 2 * (src_w // 2) * (src_h // 2), cw * ch + 2 * (cw // 2) * (ch // 2)
+    assert min(ncanvas, nsrc, src_w, src_h, cw, ch) <= 0 or (canvas.numel() >= ncanvas * cfb and src.numel() >= nsrc * sfb)
+    arr = _cell_array(cells)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_i420_compose_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(src.data_ptr()), src_w, src_h,
+                                     nsrc, arr, len(arr), ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {len(arr)} cells of {nsrc} sources {src_w}x{src_h} on {ncanvas} canvases {cw}x{ch}')
+
+
+def i420_fill(frames, w, h, n, y, cb, cr, stream=None):
+    """n tight w x h I420 frames (uint8 CUDA tensor, any alignment) set to the colour (y, cb, cr), async on stream
+    (default: the current one); h264mi_i420_fill_dev. ValueError on a bad argument."""
+    import torch
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()
+    assert n <= 0 or min(w, h) <= 0 or frames.numel() >= n * (w * h + 2 * (w // 2) * (h // 2))
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_i420_fill_dev(ctypes.c_void_p(frames.data_ptr()), w, h, n, int(y), int(cb), int(cr), ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}, colour ({y}, {cb}, {cr})')
 
 
 def i420_quality(out, a, b, w, h, n, stream=None):
