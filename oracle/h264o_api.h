@@ -93,6 +93,30 @@ int h264o_dec_coded_size(const H264ODec *d, int *cw, int *ch);
 int h264o_dec_prefilter(const H264ODec *d, uint8_t *out);
 int h264o_dec_records(const H264ODec *d, int32_t *out);
 
+/* Reconstruction test hook (tests/reconref.py): the parsed syntax of every macroblock of the last picture, before
+ * any derivation -- what clauses 8.3, 8.4 and 8.5 start from. Kept only while h264o_dec_set_capture is on; it changes
+ * nothing of what the decoder decodes. Returns the macroblock count (-1: nothing captured). The entries are cleared when
+ * a picture opens, so a macroblock the picture's slices did not cover reads all zero, and they are released by the first
+ * picture decoded with the capture off (-1 from then on). H264O_SYN_INTS int32 per macroblock, raster order:
+ *     [0]        mb_type as parsed: the ue(v) value, in a P slice 0..4 inter and 5..30 intra (Table 7-13 after the
+ *                offset of 5); -1 for a macroblock of an mb_skip_run
+ *     [1]        slice_type % 5 of its slice (0 P, 2 I)
+ *     [2..5]     sub_mb_type of the four sub-macroblocks (P_8x8)
+ *     [6..37]    mvd_l0 of every partition / sub-macroblock partition in parse order, x then y
+ *     [38..53]   prev_intra4x4_pred_mode_flag by luma4x4BlkIdx   [54..69] rem_intra4x4_pred_mode by luma4x4BlkIdx
+ *     [70]       intra_chroma_pred_mode   [71] coded_block_pattern as mapped from [76], its codeNum (both 0 for
+ *                I_16x16, whose pattern is part of mb_type)   [72] mb_qp_delta (0 when absent)
+ *     [73]       SliceQPY   [74] first_mb_in_slice   [75] chroma_qp_index_offset of the PPS
+ *     [77]       disable_deblocking_filter_idc   [78] FilterOffsetA   [79] FilterOffsetB  (of the slice)
+ *     [80..95]   Intra16x16DCLevel, scan order
+ *     [96..351]  the 16 luma blocks by luma4x4BlkIdx, 16 ints each: Luma4x4 levels in scan order, or for I_16x16
+ *                the 15 Intra16x16ACLevel in entries 0..14
+ *     [352..359] chroma DC levels, Cb then Cr, 4 each in parse order
+ *     [360..487] chroma AC levels, Cb then Cr, 4 blocks of 16 ints each: the 15 levels in entries 0..14
+ *     [488..871] the 384 pcm_sample values (luma, Cb, Cr) */
+#define H264O_SYN_INTS 872
+int h264o_dec_syntax(const H264ODec *d, int32_t *out);
+
 /* test-stream helpers (tests/streamgen.py): CAVLC bits of one residual block (0/1 per byte; returns
  * the bit count, -1 if cap is too small) and the coded_block_pattern codeNum of cbp (Table 9-4) */
 int h264o_cavlc_bits(const int16_t *coef, int maxnum, int nc, uint8_t *bits, int cap);

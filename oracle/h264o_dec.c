@@ -28,6 +28,7 @@ struct H264ODec {
     int pic_open, pic_idr, pic_ref;  /* the access unit's picture: started, IDR, nal_ref_idc != 0 */
     int capture;              /* test hook: keep a copy of each picture as it stands before the loop filter */
     uint8_t *pre;             /* that copy: tight I420 at coded size (cw x ch), NULL until a picture was captured */
+    int32_t *syn;             /* test hook: H264O_SYN_INTS parsed syntax elements per MB (h264o_dec_syntax), NULL until captured */
 };
 
 H264ODec *h264o_dec_create(void) { return (H264ODec *)calloc(1, sizeof(H264ODec)); }
@@ -35,6 +36,7 @@ static void free_frames(H264ODec *d) {
     for (int p = 0; p < 3; p++) { free(d->cur[p]); free(d->ref[p]); d->cur[p] = d->ref[p] = NULL; }
     free(d->mbs); d->mbs = NULL;
     free(d->done); d->done = NULL;
+    free(d->syn); d->syn = NULL;
 }
 void h264o_dec_destroy(H264ODec *d) { if (d) { free_frames(d); free(d->pre); free(d); } }
 
@@ -261,6 +263,10 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
     if (!d->pic_open) {
         d->pic_open = 1; d->pic_idr = nal_type == 5; d->pic_ref = nal_ref_idc != 0;
         memset(d->done, 0, (size_t)total);
+        if (d->syn) {  /* test hook: no entry of an earlier picture survives; capture switched off releases it */
+            if (d->capture) memset(d->syn, 0, (size_t)total * H264O_SYN_INTS * sizeof(int32_t));
+            else { free(d->syn); d->syn = NULL; }
+        }
     } else if (d->pic_idr != (nal_type == 5) || d->pic_ref != (nal_ref_idc != 0)) {
         return -1;
     }
@@ -304,6 +310,13 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
     }
     if (r->err || qp < 0 || qp > 51 || d->cqp_off < -12 || d->cqp_off > 12) return -1;
     int addr = first_mb, more = 1;
+    if (d->capture && !d->syn) d->syn = (int32_t *)calloc((size_t)total * H264O_SYN_INTS, sizeof(int32_t));
+    /* test hook (h264o_dec_syntax): what the bitstream says of MB a, written beside the decoding and never read by it */
+#define H264O_SYN_OPEN(a, mbtype) do { sy = (d->capture && d->syn) ? d->syn + (size_t)(a) * H264O_SYN_INTS : NULL; \
+        if (sy) { memset(sy, 0, sizeof(int32_t) * H264O_SYN_INTS); sy[0] = (mbtype); sy[1] = st; sy[73] = slice_qp; \
+                  sy[74] = first_mb; sy[75] = d->cqp_off; sy[77] = dbk_idc; sy[78] = dbk_a; sy[79] = dbk_b; } } while (0)
+    int32_t *sy = NULL;
+    const int slice_qp = qp;
     /* every MB of the slice carries the slice's identity and loop-filter parameters */
 #define H264O_SLICE_MB(mb) do { (mb)->slice_first = first_mb; (mb)->dbk_idc = (int8_t)dbk_idc; (mb)->dbk_a = (int8_t)dbk_a; \
                                 (mb)->dbk_b = (int8_t)dbk_b; if (d->done[addr]) return -1; d->done[addr] = 1; } while (0)
@@ -316,6 +329,7 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
                 MBInfo *mb = &d->mbs[addr];
                 memset(mb, 0, sizeof(*mb));
                 H264O_SLICE_MB(mb);
+                H264O_SYN_OPEN(addr, -1);
                 mb->type = MBT_PSKIP; mb->qp = qp;
                 for (int k = 0; k < 16; k++) mb->i4mode[k] = 2;
                 for (int k = 0; k < 4; k++) mb->ref[k] = 0;
@@ -337,10 +351,12 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
         int itype = -1;
         if (st == 0) { if (mt >= 5) itype = (int)mt - 5; } else itype = (int)mt;
         if (itype > 25 || (st == 0 && mt > 30)) return -1;
+        H264O_SYN_OPEN(addr, (int)mt);
         if (itype == 25) {
             mb->type = MBT_IPCM; mb->qp = qp;
             r->pos = (r->pos + 7) & ~(size_t)7;
             for (int i = 0; i < 384; i++) mb->pcm[i] = (uint8_t)br_get(r, 8);
+            if (sy) for (int i = 0; i < 384; i++) sy[488 + i] = mb->pcm[i];
             memset(mb->nnz, 16, sizeof(mb->nnz));
         } else if (itype >= 0) {
             if (itype == 0) {
@@ -348,13 +364,14 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
                 for (int blk = 0; blk < 16; blk++) {
                     int ras = BLK2RAS[blk];
                     int pm = pred_mode4(d->mbs, mb, d->mbw, mbx, mby, ras);
-                    if (br_get(r, 1)) mb->i4mode[ras] = (int8_t)pm;
-                    else { int rem = br_get(r, 3); mb->i4mode[ras] = (int8_t)(rem < pm ? rem : rem + 1); }
+                    if (br_get(r, 1)) { mb->i4mode[ras] = (int8_t)pm; if (sy) sy[38 + blk] = 1; }
+                    else { int rem = br_get(r, 3); mb->i4mode[ras] = (int8_t)(rem < pm ? rem : rem + 1); if (sy) sy[54 + blk] = rem; }
                 }
                 mb->cmode = br_ue(r);
                 uint32_t c = br_ue(r);
                 if (c > 47) return -1;
                 mb->cbp = CBP_INTRA_FROM_CODE[c];
+                if (sy) { sy[71] = mb->cbp; sy[76] = (int32_t)c; }
             } else {
                 mb->type = MBT_I16;
                 mb->i16mode = (itype - 1) % 4;
@@ -362,6 +379,7 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
                 mb->cmode = br_ue(r);
             }
             if (mb->cmode > 3) return -1;
+            if (sy) sy[70] = mb->cmode;
         } else {
             /* P macroblock: mb_pred / sub_mb_pred (7.3.5.1, 7.3.5.2) */
             for (int k = 0; k < 4; k++) mb->ref[k] = 0;
@@ -392,6 +410,10 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
                 }
             }
             mb->done4 = 0;
+            if (sy) {
+                for (int i = 0; i < 4; i++) sy[2 + i] = mb->sub_type[i];
+                for (int i = 0; i < np; i++) { sy[6 + 2 * i] = mvd[i][0]; sy[7 + 2 * i] = mvd[i][1]; }
+            }
             for (int i = 0; i < np; i++) {
                 int mvp[2], mv[2];
                 mvp_part(d->mbs, mb, d->mbw, mbx, mby, px[i], py[i], pw[i], ph[i], shape[i], mvp);
@@ -401,15 +423,28 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
             uint32_t c = br_ue(r);
             if (c > 47) return -1;
             mb->cbp = CBP_INTER_FROM_CODE[c];
+            if (sy) { sy[71] = mb->cbp; sy[76] = (int32_t)c; }
         }
         if (mb->type != MBT_IPCM) {
             if (mb->cbp || mb->type == MBT_I16) {
                 int dq = br_se(r);
                 if (dq < -26 || dq > 25) return -1;
                 qp = (qp + dq + 52) % 52;
+                if (sy) sy[72] = dq;
             }
             mb->qp = qp;
             parse_residual(d, r, mb, mbx, mby);
+            if (sy) {  /* the levels as parsed, blocks in parse order (luma4x4BlkIdx), each in scan order */
+                for (int k = 0; k < 16; k++) sy[80 + k] = mb->lumadc[k];
+                const int ac = mb->type == MBT_I16;   /* AC blocks: their 15 levels parsed into scan 1..15 */
+                for (int blk = 0; blk < 16; blk++)
+                    for (int k = 0; k < 16 - ac; k++) sy[96 + 16 * blk + k] = mb->luma[BLK2RAS[blk]][k + ac];
+                for (int pl = 0; pl < 2; pl++) {
+                    for (int k = 0; k < 4; k++) sy[352 + 4 * pl + k] = mb->cdc[pl][k];
+                    for (int blk = 0; blk < 4; blk++)
+                        for (int k = 0; k < 15; k++) sy[360 + 64 * pl + 16 * blk + k] = mb->cac[pl][blk][k + 1];
+                }
+            }
         }
         if (r->err) return -1;
         recon_mb(d, mb, mbx, mby);
@@ -417,6 +452,7 @@ static int decode_slice(H264ODec *d, BR *r, int nal_type, int nal_ref_idc) {
         more = br_more_rbsp(r);
     }
 #undef H264O_SLICE_MB
+#undef H264O_SYN_OPEN
     if (more && addr >= total && br_more_rbsp(r)) return -1;  /* slice data past the picture's end */
     return 1;
 }
@@ -545,6 +581,13 @@ int h264o_dec_records(const H264ODec *d, int32_t *out) {
         r[54] = m->slice_first; r[55] = m->dbk_idc; r[56] = m->dbk_a; r[57] = m->dbk_b;
         r[58] = d->cqp_off; r[59] = 0;
     }
+    return n;
+}
+
+int h264o_dec_syntax(const H264ODec *d, int32_t *out) {
+    if (!d || !d->mbs || !d->syn) return -1;
+    const int n = d->mbw * d->mbh;
+    memcpy(out, d->syn, (size_t)n * H264O_SYN_INTS * sizeof(int32_t));
     return n;
 }
 

@@ -500,6 +500,23 @@ int h264o_table(const char *name, double *out) {
     else if (!strcmp(name, "dbk_alpha")) { for (int i = 0; i < 52; i++) out[n++] = DBK_ALPHA[i]; }
     else if (!strcmp(name, "dbk_beta")) { for (int i = 0; i < 52; i++) out[n++] = DBK_BETA[i]; }
     else if (!strcmp(name, "dbk_tc0")) { for (int i = 0; i < 52 * 3; i++) out[n++] = DBK_TC0[i / 3][i % 3]; }
+    /* the reconstruction's and the CAVLC's tables (tests/test_recon_reference.py) */
+    else if (!strcmp(name, "zigzag4")) { for (int i = 0; i < 16; i++) out[n++] = ZIGZAG4[i]; }
+    else if (!strcmp(name, "blk2ras")) { for (int i = 0; i < 16; i++) out[n++] = BLK2RAS[i]; }
+    else if (!strcmp(name, "dequant_v")) { for (int i = 0; i < 18; i++) out[n++] = DEQUANT_V[i / 3][i % 3]; }
+    else if (!strcmp(name, "pos_class")) { for (int i = 0; i < 16; i++) out[n++] = POS_CLASS[i]; }
+    else if (!strcmp(name, "cbp_intra")) { for (int i = 0; i < 48; i++) out[n++] = CBP_INTRA_FROM_CODE[i]; }
+    else if (!strcmp(name, "cbp_inter")) { for (int i = 0; i < 48; i++) out[n++] = CBP_INTER_FROM_CODE[i]; }
+    else if (!strcmp(name, "ct_len")) { for (int i = 0; i < 4 * 68; i++) out[n++] = CT_LEN[i / 68][i % 68]; }
+    else if (!strcmp(name, "ct_code")) { for (int i = 0; i < 4 * 68; i++) out[n++] = CT_CODE[i / 68][i % 68]; }
+    else if (!strcmp(name, "ct_dc_len")) { for (int i = 0; i < 20; i++) out[n++] = CT_DC_LEN[i]; }
+    else if (!strcmp(name, "ct_dc_code")) { for (int i = 0; i < 20; i++) out[n++] = CT_DC_CODE[i]; }
+    else if (!strcmp(name, "tz_len")) { for (int i = 0; i < 15 * 16; i++) out[n++] = TZ_LEN[i / 16][i % 16]; }
+    else if (!strcmp(name, "tz_code")) { for (int i = 0; i < 15 * 16; i++) out[n++] = TZ_CODE[i / 16][i % 16]; }
+    else if (!strcmp(name, "tz_dc_len")) { for (int i = 0; i < 12; i++) out[n++] = TZ_DC_LEN[i / 4][i % 4]; }
+    else if (!strcmp(name, "tz_dc_code")) { for (int i = 0; i < 12; i++) out[n++] = TZ_DC_CODE[i / 4][i % 4]; }
+    else if (!strcmp(name, "rb_len")) { for (int i = 0; i < 7 * 15; i++) out[n++] = RB_LEN[i / 15][i % 15]; }
+    else if (!strcmp(name, "rb_code")) { for (int i = 0; i < 7 * 15; i++) out[n++] = RB_CODE[i / 15][i % 15]; }
     else return -1;
     return n;
 }

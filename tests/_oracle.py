@@ -38,6 +38,7 @@ class Oracle:
         L.h264o_dec_coded_size.argtypes = [vp, vp, vp]
         L.h264o_dec_prefilter.argtypes = [vp, vp]
         L.h264o_dec_records.argtypes = [vp, vp]
+        L.h264o_dec_syntax.argtypes = [vp, vp]
         L.h264o_table.argtypes = [ctypes.c_char_p, vp]
         L.h264o_rgba_to_i420.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
         L.h264o_i420_to_rgba.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
@@ -156,6 +157,15 @@ class ODec:
         out = np.zeros((cw // 16) * (ch // 16) * self.REC_INTS, np.int32)
         assert self.L.h264o_dec_records(self.d, out.ctypes.data) == out.size // self.REC_INTS
         return out.reshape(-1, self.REC_INTS)
+
+    SYN_INTS = 872  # H264O_SYN_INTS
+
+    def syntax(self):
+        """-> int32 [macroblocks, SYN_INTS]: the parsed syntax elements of every macroblock (layout: h264o_api.h)"""
+        cw, ch = self.coded_size()
+        out = np.zeros((cw // 16) * (ch // 16) * self.SYN_INTS, np.int32)
+        assert self.L.h264o_dec_syntax(self.d, out.ctypes.data) == out.size // self.SYN_INTS
+        return out.reshape(-1, self.SYN_INTS)
 
     def __del__(self):
         try:

@@ -46,11 +46,12 @@ def nal(ref_idc, typ, rbsp):
     return bytes(out)
 
 
-def p_frame(mbw, mbh, frame_num, poc_lsb, rng, max_mvd=96, skip_prob=0.2, qp_delta=0, dbk_idc=0, first_mb=0):
+def p_frame(mbw, mbh, frame_num, poc_lsb, rng, max_mvd=96, skip_prob=0.2, qp_delta=0, dbk_idc=0, first_mb=0, log=None):
     """One P access unit: each MB P_Skip (runs) with probability skip_prob, else P_L0_16x16 with a
     random mvd in [-max_mvd, max_mvd] quarter samples and coded_block_pattern 0. first_mb > 0 makes
     it the second slice of a two-slice picture (MBs first_mb..end). poc_lsb is unused: the encoder's SPS
-    has POC type 2 (the order follows frame_num)."""
+    has POC type 2 (the order follows frame_num). log: a list that receives, per macroblock, None for a skipped one
+    or its mvd (x, y)."""
     w = BitWriter()
     w.ue(first_mb)          # first_mb_in_slice
     w.ue(5)                 # slice_type P (all slices of the picture P)
@@ -67,12 +68,17 @@ def p_frame(mbw, mbh, frame_num, poc_lsb, rng, max_mvd=96, skip_prob=0.2, qp_del
     for _ in range(mbw * mbh - first_mb):
         if rng.random() < skip_prob:
             run += 1
+            if log is not None:
+                log.append(None)
             continue
         w.ue(run)           # mb_skip_run
         run = 0
         w.ue(0)             # mb_type P_L0_16x16
-        w.se(int(rng.integers(-max_mvd, max_mvd + 1)))
-        w.se(int(rng.integers(-max_mvd, max_mvd + 1)))
+        mvd = (int(rng.integers(-max_mvd, max_mvd + 1)), int(rng.integers(-max_mvd, max_mvd + 1)))
+        w.se(mvd[0])
+        w.se(mvd[1])
+        if log is not None:
+            log.append(mvd)
         w.ue(0)             # coded_block_pattern (inter, codeNum 0 -> 0)
     if run:
         w.ue(run)
@@ -149,6 +155,7 @@ class SyntaxGen:
         self.poc_type, self.dpoaz = poc_type, dpoaz  # POC type 0 / 1 (delta_pic_order_always_zero_flag) / 2
         self.tc_choice = None  # TotalCoeff distribution of generated blocks (None: the default mix)
         self._spec = None      # the scripted macroblock being written (_slice's script=), else None
+        self._cur = {}         # the macroblock log entry being filled (mblog)
         self.frame_num = 0
         self.poc = 0
         self.idr_id = 0
@@ -228,6 +235,7 @@ class SyntaxGen:
         n = self.L.h264o_cavlc_bits(coef.ctypes.data, len(coef), nc, self._bits.ctypes.data, self._bits.size)
         assert n > 0
         w.raw(self._bits[:n].tobytes())
+        self._cur.setdefault('blocks', []).append([int(v) for v in coef])
         return int(np.count_nonzero(coef))
 
     def _residual(self, w, nn, mx, my, cur, mtype, cbp, qp, i16):
@@ -259,6 +267,7 @@ class SyntaxGen:
         else:
             dq = int(rng.integers(-26, 26))   # wraps across 0 / 51
         w.se(dq)
+        self._cur['dq'] = dq
         return (qp + dq + 52) % 52
 
     def _intra(self, w, nn, i4m, kinds, mx, my, qp, in_p, kind):
@@ -271,13 +280,17 @@ class SyntaxGen:
         self._last_cbp = 0
         if kind == 'pcm':
             w.ue(off + 25)
+            self._cur['mb_type'] = off + 25
             w.align_zero()
             if self._spec is not None and 'samples' in self._spec:   # scripted: the 384 pcm_sample bytes (Y, Cb, Cr)
+                self._cur['pcm'] = [int(v) for v in self._spec['samples']]
                 for v in self._spec['samples']:
                     w.u(int(v), 8)
                 return qp, [16] * 24, None
+            self._cur['pcm'] = []
             for _ in range(384):
-                w.u(int(rng.integers(1, 256)), 8)
+                self._cur['pcm'].append(int(rng.integers(1, 256)))
+                w.u(self._cur['pcm'][-1], 8)
             return qp, [16] * 24, None
         if kind == 'i16' and self._spec is not None and 'mode' in self._spec:
             # scripted I_16x16 with no coefficient at all: prediction mode 'mode' (its neighbours must be available),
@@ -286,12 +299,15 @@ class SyntaxGen:
             w.ue(0)
             dq = int(self._spec.get('dq', 0))
             w.se(dq)
+            self._cur.update(mb_type=off + 1 + int(self._spec['mode']), chroma_mode=0, dq=dq)
             qp = (qp + dq + 52) % 52
             self._block(w, np.zeros(16, np.int16), self._nc(nn, None, mx, my, cur, 0))
             return qp, cur, None
         cm = int(rng.choice([m for m, nd in _CHROMA_NEEDS.items() if _ok(nd, top_mb, left_mb, tl_mb)]))
+        self._cur['chroma_mode'] = cm
         if kind == 'i4':
             w.ue(off + 0)
+            self._cur.update(mb_type=off, prev=[], rem=[])
             modes = [2] * 16
             for k in range(16):
                 ras = _BLK_ORDER[k]
@@ -316,6 +332,8 @@ class SyntaxGen:
                 else:
                     w.u(0, 1)
                     w.u(m if m < pm else m - 1, 3)
+                self._cur['prev'].append(int(m == pm))
+                self._cur['rem'].append(0 if m == pm else (m if m < pm else m - 1))
             w.ue(cm)
             cbp = int(rng.integers(0, 48))
             self._last_cbp = cbp
@@ -332,6 +350,7 @@ class SyntaxGen:
             cbpc, cbpl = self.i16_cbp >> 4, self.i16_cbp & 15
         self._last_cbp = cbpl | (cbpc << 4)
         w.ue(off + 1 + pm16 + 4 * cbpc + (12 if cbpl else 0))
+        self._cur['mb_type'] = off + 1 + pm16 + 4 * cbpc + (12 if cbpl else 0)
         w.ue(cm)
         qp = self._qp_delta(w, qp)
         self._residual(w, nn, mx, my, cur, 'i16', cbpl | (cbpc << 4), qp, True)
@@ -376,7 +395,8 @@ class SyntaxGen:
         increasing; a key left out takes the picture-wide argument) -> the RBSP of each slice in
         raster order (the single-slice default returns one). script = {macroblock address: spec} writes those
         macroblocks as told instead of drawing them: {'kind': 'pcm', 'samples': 384 values}, {'kind': 'i16', 'mode': m,
-        'dq': d} (no coefficients), {'kind': 'skip'}, or any {'kind': k} of the mix with random content"""
+        'dq': d} (no coefficients), {'kind': 'skip'}, or any {'kind': k} of the mix with random content; an inter kind takes
+        'mvd': [(x, y), ...] (mvd_l0 of its partitions in parse order) and, for 'p8x8', 'subs': the four sub_mb_type"""
         rng = self.rng
         mbw, mbh = self.mbw, self.mbh
         slices = slices or [{'first': 0}]
@@ -389,6 +409,8 @@ class SyntaxGen:
         probs = np.array([mix[k] for k in names], float)
         probs /= probs.sum()
         self.log = []   # per MB: (mb type code as h264o_dec_mbinfo reports it, QPY, coded_block_pattern)
+        self.mblog = []  # per MB: the syntax elements as written (mb_type -1: skipped; mvd, sub types, intra mode flags,
+                         # chroma mode, cbp, dq, the levels of every residual block in parse order, pcm samples)
         out = []
         w, run, si, islice, qp = None, 0, -1, idr, 0
         for my in range(mbh):
@@ -405,12 +427,15 @@ class SyntaxGen:
                     islice = idr or sd.get('intra', False)
                     w, run = FastBits(), 0
                     qp = self._header(w, addr, idr, islice, sd.get('qp_delta', qp_delta), sd.get('dbk', dbk), override, reorder, ref_idc)
+                    slice_qp = qp
                 kind = names[int(rng.choice(len(names), p=probs))]
                 self._spec = script.get(addr) if script else None
                 if self._spec is not None:
                     kind = self._spec['kind']
                 if islice and kind in ('skip', 'p16', 'p16x8', 'p8x16', 'p8x8'):
                     kind = 'i4'
+                self._cur = dict(mb_type=-1, slice_qp=slice_qp, first=self._first, cbp=0)
+                self.mblog.append(self._cur)
                 if kind == 'skip':
                     run += 1
                     nn[my][mx], kinds[my][mx] = [0] * 24, 'skip'
@@ -423,24 +448,37 @@ class SyntaxGen:
                 if kind in ('i4', 'i16', 'pcm'):
                     qp, nn[my][mx], i4m[my][mx] = self._intra(w, nn, i4m, kinds, mx, my, qp, not islice, kind)
                     self.log.append(({'i4': 0, 'i16': 1, 'pcm': 7}[kind], qp, self._last_cbp))
+                    self._cur['cbp'] = self._last_cbp
                     continue
                 cur = [0] * 24
                 mt = {'p16': 0, 'p16x8': 1, 'p8x16': 2, 'p8x8': 3}[kind]
                 w.ue(mt)
+                self._cur.update(mb_type=mt, subs=[0] * 4, mvd=[])
+                given = list(self._spec['mvd']) if self._spec is not None and 'mvd' in self._spec else None   # scripted mvd_l0
+
+                def mvd():
+                    v = given.pop(0) if given is not None else (int(rng.integers(-max_mvd, max_mvd + 1)), int(rng.integers(-max_mvd, max_mvd + 1)))
+                    w.se(int(v[0])); w.se(int(v[1]))
+                    self._cur['mvd'].append((int(v[0]), int(v[1])))
                 if mt < 3:
                     for _ in range(1 if mt == 0 else 2):
-                        w.se(int(rng.integers(-max_mvd, max_mvd + 1))); w.se(int(rng.integers(-max_mvd, max_mvd + 1)))
+                        mvd()
                 else:
-                    subs = [int(rng.integers(0, 4)) for _ in range(4)]
+                    if self._spec is not None and self._spec.get('subs') is not None:   # scripted sub_mb_type
+                        subs = [int(v) for v in self._spec['subs']]
+                    else:
+                        subs = [int(rng.integers(0, 4)) for _ in range(4)]
+                    self._cur['subs'] = subs
                     for s_ in subs:
                         w.ue(s_)
                     for s_ in subs:
                         for _ in range({0: 1, 1: 2, 2: 2, 3: 4}[s_]):
-                            w.se(int(rng.integers(-max_mvd, max_mvd + 1))); w.se(int(rng.integers(-max_mvd, max_mvd + 1)))
+                            mvd()
                 cbp = int(rng.integers(0, 48)) if rng.random() < 0.85 else 0
                 if cbp_fixed is not None:
                     cbp = cbp_fixed
                 w.ue(self.L.h264o_cbp_code(cbp, 0))
+                self._cur['cbp'] = cbp
                 if cbp:
                     qp = self._qp_delta(w, qp)
                     self._residual(w, nn, mx, my, cur, kind, cbp, qp, False)
