@@ -8,8 +8,15 @@
 // Same MB-row wavefront as the encoder: one wave per (stream, MB row); the unfiltered bottom line
 // of each MB is handed to the row below as {epoch,payload} granules. Residuals of all 24 blocks
 // are computed in parallel (lane per block); the only serial chain is the Intra4x4 one (16 steps of
-// 16-lane prediction+add). Inter reference pixels of a MB are staged in a 48x48 LDS tile when its
-// motion vectors allow, otherwise sampled from HBM with clamping.
+// 16-lane prediction+add).
+// Inter prediction reads one reference plane: the edge-padded integer picture G (dec_planes_kernel,
+// enc_planes.inc), of which each row wave keeps columns [X-24, X+40) of rows [Y-24, Y+40) in a 64-column
+// LDS ring (the encoder's window geometry, one plane instead of its four). A decoder samples every block
+// once, at a vector it knows, so the half-sample values b, h, j are computed where they are used
+// (8.4.2.2.1, six-tap filters over the window, in registers) and are never stored. A macroblock whose
+// vectors are all whole-sample reads its four samples per lane and nothing else. A macroblock with a
+// block whose filter footprint leaves the window (mb_in_window) interpolates from the deblocked picture
+// in HBM with clamping (GlobGet).
 namespace h264mi {
 
 // prof: 16 section totals (diagnostic); streamed: the slice data is still being parsed -- each row waits
@@ -84,27 +91,20 @@ DEV bool prog_wait(GLOBAL uint64_t *prog, uint32_t tag, uint32_t need, int32_t *
     return false;
 }
 
-// H264MI_REC_TILE 1: an LDS tile (2.3 KB) for MBs whose vectors leave the window but fit 48x48, and an LDS
-// copy of I_PCM samples; 0 (default): those MBs interpolate from the global reference plane and I_PCM samples
-// are read from the coefficient image -- 21 KB of LDS instead of 23.7, seven reconstruction workgroups per CU
-// instead of six: bench +1.4 %, the encoder beside it 5.33 -> 5.04 ms (profiles/round5/ab_recon_notile.txt)
-#ifndef H264MI_REC_TILE
-#define H264MI_REC_TILE 0
-#endif
+// MBs whose vectors leave the window interpolate from the deblocked picture in HBM and I_PCM samples are read
+// from the coefficient image (an LDS tile for the former and an LDS copy of the latter cost a workgroup per CU
+// and 1.4 % of the bench when the windows held four planes, profiles/round5/ab_recon_notile.txt).
+constexpr int DWIN_ROWS = 64;            // window rows [Y-24, Y+40), one per lane of the strip loads
+constexpr int DWIN_LO = -24, DWIN_HI = 40;   // luma window, rows and columns relative to the MB: [DWIN_LO, DWIN_HI)
+constexpr int DWINC_LO = -12, DWINC_HI = 20; // chroma window
 struct DecLds {
-    alignas(16) uint8_t win[4][64 * 64];   // reference planes G, b, h, j: 64-column ring (enc_mb.inc layout)
+    alignas(16) uint8_t win[DWIN_ROWS * WIN_RING];  // integer reference plane G: 64-column ring (enc_mb.inc layout)
     alignas(16) uint8_t winc[2][32 * 32];  // Cb, Cr ring
     alignas(16) uint32_t cf[208];          // this MB's MbCoef image (only blocks with TotalCoeff > 0 are valid)
-#if H264MI_REC_TILE
-    alignas(16) uint8_t tile[48 * 48];
-#endif
     alignas(16) int16_t res[24][16];
     int dcval[24];                      // reconstructed DC coefficients (I16 luma 0..15, chroma 16..23)
     alignas(16) uint8_t rec[256];
     alignas(16) uint8_t recc[2][64];
-#if H264MI_REC_TILE
-    alignas(16) uint8_t pcm[384];
-#endif
     uint8_t top[24];
     uint8_t topc[2][12];
     uint8_t left[16], leftc[2][8];
@@ -116,17 +116,93 @@ struct DecLds {
     alignas(16) MbInfo linfo;  // resolved record of the left MB
 };
 
-// 4 window bytes at absolute column gx of window row wr, plane p (ring of 64 columns, enc_mb.inc layout)
-DEV uint32_t dwin4(const DecLds &S, int p, int wr, int gx) {
+// 4 window bytes at absolute column gx of window row wr (ring of 64 columns, enc_mb.inc layout)
+DEV uint32_t dwin4(const DecLds &S, int wr, int gx) {
     const int sl = (gx + 24) & 63;
-    const uint32_t *row = (const uint32_t *)&S.win[p][wr * WIN_RING];
+    const uint32_t *row = (const uint32_t *)&S.win[wr * WIN_RING];
     return __builtin_amdgcn_alignbyte(row[((sl >> 2) + 1) & 15], row[sl >> 2], sl & 3);
 }
 
-struct TileGet {
-    const uint8_t *t; int x0, y0;
-    DEV int operator()(int x, int y) const { return t[(y - y0) * 48 + (x - x0)]; }
-};
+// ---------------------------------------------------------------- luma interpolation from the G window
+// Samples gx-2 .. gx+6 of window row wr, the footprint of the horizontal six-tap filter over a lane's four
+// samples gx..gx+3: lo = samples 0..3 of the nine, mid = 4..7, hi = the ninth. Three ring dwords whatever
+// the alignment. The row index is clamped to the window: mb_in_window admits a macroblock only if every row
+// a lane *uses* is inside, and a lane that computes a filter for its neighbours' sake (the filters run under
+// wave-uniform branches) then reads some valid row and drops the result.
+struct WRow { uint32_t lo, mid, hi; };
+DEV WRow dwin_row(const DecLds &S, int wr, int gx) {
+    const int sl = (gx - 2 + 24) & 63, d = sl >> 2, sh = sl & 3;
+    const uint32_t *row = (const uint32_t *)&S.win[clip3(0, DWIN_ROWS - 1, wr) * WIN_RING];
+    const uint32_t d0 = row[d], d1 = row[(d + 1) & 15], d2 = row[(d + 2) & 15];
+    return WRow{__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh), (d2 >> (8 * sh)) & 255u};
+}
+// the lane's four samples of the row, at column offset dx (0 or 1)
+DEV uint32_t wrow_quad(const WRow &r, int dx) { return __builtin_amdgcn_alignbyte(r.mid, r.lo, 2 + dx); }
+// unrounded horizontal taps b1 (8-241) of the lane's four samples
+DEV void wrow_b1(const WRow &r, int t[4]) {
+    int s[9];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { s[k] = (r.lo >> (8 * k)) & 255; s[4 + k] = (r.mid >> (8 * k)) & 255; }
+    s[8] = r.hi;
+#pragma unroll
+    for (int k = 0; k < 4; k++) t[k] = tap6(s[k], s[k + 1], s[k + 2], s[k + 3], s[k + 4], s[k + 5]);
+}
+DEV uint32_t pack_clip_shr(const int t[4], int rnd, int sh) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) o |= (uint32_t)clip1_shr(t[k] + rnd, sh) << (8 * k);
+    return o;
+}
+// 8.4.2.2.1 for a macroblock with at least one fractional vector: four prediction samples per lane (columns
+// gx..gx+3 of window row wr, position idx = yFrac * 4 + xFrac of the lane's 4x4 block). Every position is the
+// rounded average of two of {G, b, h, j} at the offsets qsel() tabulates (at most one operand of each kind),
+// with b = Clip1((b1 + 16) >> 5), h likewise down the column, j = Clip1((tap6 of six rows' b1 + 512) >> 10)
+// -- the formulas the encoder's planes hold (enc_planes.inc), over the same edge-padded G. The blocks of one
+// macroblock may differ in position: which of the three filters any lane needs is decided for the wave with a
+// ballot, every lane runs those and selects its operands; no per-lane branch. Whole wave: every lane active.
+DEV uint32_t dec_luma_frac(const DecLds &S, int wr, int gx, int idx) {
+    const QSel q = qsel(idx);
+    const bool ub = __ballot(q.p1 == 1 || q.p2 == 1) != 0, uh = __ballot(q.p1 == 2 || q.p2 == 2) != 0;
+    const bool uj = __ballot(q.p1 == 3 || q.p2 == 3) != 0;
+    const int gdx = q.p1 == 0 ? q.dx1 : q.dx2, gdy = q.p1 == 0 ? q.dy1 : q.dy2;  // the G operand's offset
+    const int bdy = q.p1 == 1 ? q.dy1 : q.dy2, hdx = q.p1 == 2 ? q.dx1 : q.dx2;  // b's row, h's column offset
+    const WRow r2 = dwin_row(S, wr, gx);
+    WRow r3 = r2;  // row wr + 1: only positions with yFrac 3 read it, and those need h or j
+    uint32_t vb = 0, vh = 0, vj = 0;
+    if (uh || uj) {
+        const WRow r0 = dwin_row(S, wr - 2, gx), r1 = dwin_row(S, wr - 1, gx), r4 = dwin_row(S, wr + 2, gx), r5 = dwin_row(S, wr + 3, gx);
+        r3 = dwin_row(S, wr + 1, gx);
+        if (uh) {
+            const uint32_t c0 = wrow_quad(r0, hdx), c1 = wrow_quad(r1, hdx), c2 = wrow_quad(r2, hdx), c3 = wrow_quad(r3, hdx);
+            const uint32_t c4 = wrow_quad(r4, hdx), c5 = wrow_quad(r5, hdx);
+            int t[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int s = 8 * k;
+                t[k] = tap6((c0 >> s) & 255, (c1 >> s) & 255, (c2 >> s) & 255, (c3 >> s) & 255, (c4 >> s) & 255, (c5 >> s) & 255);
+            }
+            vh = pack_clip_shr(t, 16, 5);
+        }
+        if (uj) {
+            int t0[4], t1[4], t2[4], t3[4], t4[4], t5[4], t[4];
+            wrow_b1(r0, t0); wrow_b1(r1, t1); wrow_b1(r2, t2); wrow_b1(r3, t3); wrow_b1(r4, t4); wrow_b1(r5, t5);
+#pragma unroll
+            for (int k = 0; k < 4; k++) t[k] = tap6(t0[k], t1[k], t2[k], t3[k], t4[k], t5[k]);
+            vj = pack_clip_shr(t, 512, 10);
+        }
+    }
+    if (ub) {
+        const WRow rb{bdy ? r3.lo : r2.lo, bdy ? r3.mid : r2.mid, bdy ? r3.hi : r2.hi};
+        int t[4];
+        wrow_b1(rb, t);
+        vb = pack_clip_shr(t, 16, 5);
+    }
+    const uint32_t vg = gdy ? wrow_quad(r3, 0) : wrow_quad(r2, gdx);
+    const uint32_t pa = q.p1 == 0 ? vg : (q.p1 == 1 ? vb : (q.p1 == 2 ? vh : vj));
+    const uint32_t pb = q.p2 == 0 ? vg : (q.p2 == 1 ? vb : (q.p2 == 2 ? vh : vj));
+    return (pa | pb) - (((pa ^ pb) & 0xFEFEFEFEu) >> 1);  // bytewise (a + b + 1) >> 1
+}
+
 struct GlobGet {
     GLOBAL const uint8_t *p; int w, h;
     DEV int operator()(int x, int y) const { return p[clip3(0, h - 1, y) * w + clip3(0, w - 1, x)]; }
@@ -330,15 +406,26 @@ DEV void resolve_record(DecLds &S, int mbx, uint32_t nbm) {
     }
 }
 
-// Every 4x4 block's reference samples (luma via the planes, chroma bilinear) lie inside the LDS
-// windows: luma columns/rows [-24, 40) and chroma [-12, 20) relative to the MB.
+// Every sample the window paths read for the MB's 4x4 blocks lies inside the LDS windows: luma columns/rows
+// [DWIN_LO, DWIN_HI) = [-24, 40) and chroma [DWINC_LO, DWINC_HI) = [-12, 20) relative to the MB. Exact, per
+// block and per direction:
+//   luma    the block's samples p .. p+3 at its integer displacement, widened by the six-tap footprint -- 2
+//           before, 3 after -- in a direction whose vector component has a fractional part (dec_luma_frac);
+//   chroma  the block's 2x2 samples c .. c+1 and the right / lower neighbour c+2, which the bilinear form
+//           reads whatever the fraction (weight 0 for a whole-sample component).
+// For a whole-sample component the chroma window binds on the far side (p <= 35: one less than luma alone),
+// for a fractional one the luma footprint (p - 2 >= -24, p + 6 <= 39).
 // Lane-parallel (block lane & 15 per lane), whole wave: call with every lane active.
 DEV bool mb_in_window(const MbInfo &I) {
     const int b = threadIdx.x & 15;
     const uint32_t mv = ((const uint32_t *)I.mv)[b];
-    const int x = (b & 3) * 4 + ((int)(int16_t)(mv & 0xffff) >> 2), y = (b >> 2) * 4 + ((int)(int16_t)(mv >> 16) >> 2);
-    const bool ok = min(x, y) >= -24 && max(x, y) + 5 <= 40;  // 4 samples + the second plane's +1 offset
-    return __ballot(!ok) == 0;  // chroma: (mv >> 3) spans half the luma range (inside [-12, 20))
+    const int mvx = (int16_t)(mv & 0xffff), mvy = (int16_t)(mv >> 16);
+    const int x = (b & 3) * 4 + (mvx >> 2), y = (b >> 2) * 4 + (mvy >> 2);
+    const int fx = (mvx & 3) != 0, fy = (mvy & 3) != 0;
+    const int cx = (b & 3) * 2 + (mvx >> 3), cy = (b >> 2) * 2 + (mvy >> 3);
+    const bool okl = min(x - 2 * fx, y - 2 * fy) >= DWIN_LO && max(x + 3 * fx, y + 3 * fy) + 3 < DWIN_HI;
+    const bool okc = min(cx, cy) >= DWINC_LO && max(cx, cy) + 2 < DWINC_HI;
+    return __ballot(!(okl && okc)) == 0;
 }
 
 // Tickets [0, S*mbh) reconstruct MB rows; tickets [S*mbh, 2*S*mbh) are the deblocking rows that
@@ -391,14 +478,16 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
     const int Y = mby * 16;
     GLOBAL uint64_t *grow_prev = gbl(D.gran) + (size_t)(mby > 0 ? mby - 1 : 0) * mbw * H264MI_GRANULES_PER_MB;
     GLOBAL uint64_t *grow = gbl(D.gran) + (size_t)mby * mbw * H264MI_GRANULES_PER_MB;
-    const int Y0 = Y - 24;
+    const int Y0 = Y + DWIN_LO;
+    static_assert(DWIN_HI - DWIN_LO == DWIN_ROWS && DWIN_ROWS == 64 && WIN_RING == 64, "one window row per lane, 64-column ring");
+    static_assert(-DWIN_LO <= H264MI_LPADY && DWIN_HI - 16 <= H264MI_LPADY && -DWIN_LO <= H264MI_LPADX && DWIN_HI - 16 <= H264MI_LPADX,
+                  "the window of an edge macroblock lies inside the plane's padding");
     // ---- one MB ahead: the MB record and coefficient image (written by the parse launch) and the
-    // reference window strips (enc_mb.inc window layout; lane -> 4 luma strips + 1 chroma strip)
-    GLOBAL const uint8_t *plw[4];
-    for (int k = 0; k < 4; k++) plw[k] = gbl((const uint8_t *)D.pl[k]) + (ptrdiff_t)(Y0 + lane) * D.ps;
+    // reference window strips (enc_mb.inc window layout; lane -> 1 luma strip + 1 chroma strip)
+    GLOBAL const uint8_t *plw = gbl((const uint8_t *)D.pl) + (ptrdiff_t)(Y0 + lane) * D.ps;
     GLOBAL const uint8_t *plcw = gbl((const uint8_t *)D.plc[lane >> 5]) + (ptrdiff_t)(mby * 8 - 12 + (lane & 31)) * D.psc;
     uint32_t pf_info = 0, pf_cf[4] = {0, 0, 0, 0};
-    u32x4 pf_w[4];
+    u32x4 pf_w = {0, 0, 0, 0};
     u32x2 pf_c = {0, 0};
     auto issue = [&](int mx) {
         const int mi = mby * mbw + mx;
@@ -407,16 +496,13 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
 #pragma unroll
         for (int k = 0; k < 4; k++) if (lane + 64 * k < 208) pf_cf[k] = cf32[lane + 64 * k];
         if (has_ref && mx > 0) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) pf_w[k] = *(GLOBAL const u32x4 *)(plw[k] + 16 * mx + 24);
+            pf_w = *(GLOBAL const u32x4 *)(plw + 16 * mx + 24);
             pf_c = *(GLOBAL const u32x2 *)(plcw + 8 * mx + 12);
         }
     };
     if (has_ref) {  // initial window: luma columns [-24, 40), chroma [-12, 20)
 #pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) *(u32x4 *)&S.win[k][lane * WIN_RING + 16 * j] = *(GLOBAL const u32x4 *)(plw[k] - 24 + 16 * j);
+        for (int j = 0; j < 4; j++) *(u32x4 *)&S.win[lane * WIN_RING + 16 * j] = *(GLOBAL const u32x4 *)(plw - 24 + 16 * j);
 #pragma unroll
         for (int j = 0; j < 4; j++) *(u32x2 *)&S.winc[lane >> 5][(lane & 31) * WINC_RING + 8 * j] = *(GLOBAL const u32x2 *)(plcw - 12 + 8 * j);
     }
@@ -497,12 +583,7 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
         // ---- levels stay in S.cf (only blocks with TotalCoeff > 0 were stored; the residual stage
         // masks the others); I_PCM samples are the record's payload
         const MbCoef &CF = *(const MbCoef *)S.cf;
-#if H264MI_REC_TILE
-        if (ipcm) for (int k = lane; k < 384; k += 64) S.pcm[k] = ((const uint8_t *)&CF)[k];
-        const uint8_t *PCM = S.pcm;
-#else
         const uint8_t *PCM = (const uint8_t *)&CF;  // the record's payload, in S.cf
-#endif
         // ---- neighbour pixels: intra prediction only (an inter MB never waited for the row above's samples,
         // so S.gp may be stale then; S.left / S.leftc are rewritten by every MB's outputs)
         const bool has_top = nbm & NB_B, has_left = nbm & NB_A, has_tr = nbm & NB_C, has_tl = nbm & NB_D;
@@ -603,15 +684,16 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
                 S.rec[i] = (uint8_t)clip1(i16_pred(S, k16, I.i16mode, x, y) + S.res[ras][(y & 3) * 4 + (x & 3)]);
             }
         } else if (inwin) {
-            // inter from the reference planes window: each sample is a rounded average of two plane
-            // samples (8.4.2.2.1), no interpolation on the chain
+            // inter from the G window: a macroblock of whole-sample vectors (wave-uniform) reads its samples and
+            // nothing else; any other runs the six-tap filters its blocks need (dec_luma_frac)
             {  // one row of four samples of one 4x4 block per lane (one vector per block)
                 const int y = lane >> 2, x0 = (lane & 3) * 4, ras = (y >> 2) * 4 + (x0 >> 2);
                 const int mx = I.mv[ras][0], my = I.mv[ras][1];
-                const QSel q = qsel((my & 3) * 4 + (mx & 3));
+                const int idx = (my & 3) * 4 + (mx & 3);
                 const int gx = X + x0 + (mx >> 2), wr = Y + y + (my >> 2) - Y0;
-                const uint32_t pa = dwin4(S, q.p1, wr + q.dy1, gx + q.dx1), pb = dwin4(S, q.p2, wr + q.dy2, gx + q.dx2);
-                const uint32_t pv = (pa | pb) - (((pa ^ pb) & 0xFEFEFEFEu) >> 1);  // bytewise (a + b + 1) >> 1
+                uint32_t pv;
+                if (__ballot(idx != 0) == 0) pv = dwin4(S, wr, gx);
+                else pv = dec_luma_frac(S, wr, gx, idx);
                 uint32_t o = 0;
                 if (has_res) {
                     const u32x2 r2 = *(const u32x2 *)&S.res[ras][(y & 3) * 4];
@@ -624,33 +706,13 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
                 *(uint32_t *)&S.rec[y * 16 + x0] = o;
             }
         } else {
-#if H264MI_REC_TILE
-            // inter: bounding box of the 16 blocks' reference areas
-            int x0 = 1 << 30, y0 = 1 << 30, x1 = -(1 << 30), y1 = -(1 << 30);
-            for (int b = 0; b < 16; b++) {
-                int ix = X + (b & 3) * 4 + (I.mv[b][0] >> 2), iy = Y + (b >> 2) * 4 + (I.mv[b][1] >> 2);
-                x0 = min(x0, ix - 2); y0 = min(y0, iy - 2); x1 = max(x1, ix + 4 + 3); y1 = max(y1, iy + 4 + 3);
-            }
-            const bool use_tile = (x1 - x0) <= 48 && (y1 - y0) <= 48;
-            if (use_tile) {
-                for (int i = lane; i < 48 * 48; i += 64) {
-                    int tx = i % 48, ty = i / 48;
-                    S.tile[i] = R0[clip3(0, ch - 1, y0 + ty) * cw + clip3(0, cw - 1, x0 + tx)];
-                }
-                wave_lds_sync();
-            }
-            const TileGet tg{S.tile, x0, y0};
-#endif
+            // inter with a block outside the window (or no window): interpolation from the deblocked picture
             const GlobGet gg{R0, cw, ch};
             for (int i = lane; i < 256; i += 64) {
                 int x = i & 15, y = i >> 4, ras = (y >> 2) * 4 + (x >> 2);
                 int mx = I.mv[ras][0], my = I.mv[ras][1];
                 int gx = X + x + (mx >> 2), gy = Y + y + (my >> 2);
-#if H264MI_REC_TILE
-                int pv = use_tile ? qpel(tg, gx, gy, mx & 3, my & 3) : qpel(gg, gx, gy, mx & 3, my & 3);
-#else
                 int pv = qpel(gg, gx, gy, mx & 3, my & 3);
-#endif
                 S.rec[i] = (uint8_t)clip1(pv + (has_res ? S.res[ras][(y & 3) * 4 + (x & 3)] : 0));
             }
         }
@@ -711,8 +773,7 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
         if (lane < 32) ((uint32_t *)&S.linfo)[lane] = ((const uint32_t *)&S.info)[lane];
         if (has_ref && mbx + 1 < mbw) {  // slide the window: MB x+1's new strip (columns X+40..X+55)
             const int nx = mbx + 1;
-#pragma unroll
-            for (int k = 0; k < 4; k++) *(u32x4 *)&S.win[k][lane * WIN_RING + ((16 * nx + 48) & 63)] = pf_w[k];
+            *(u32x4 *)&S.win[lane * WIN_RING + ((16 * nx + 48) & 63)] = pf_w;
             *(u32x2 *)&S.winc[lane >> 5][(lane & 31) * WINC_RING + ((8 * nx + 24) & 31)] = pf_c;
         }
         wave_lds_sync();

@@ -9,7 +9,10 @@
 //   j(x, y) = Clip1((tap6 of b1(x, y-2..y+3)) + 512) >> 10,  b1 = unrounded horizontal tap (8-245/8-247)
 // so quarter samples are a rounded average of two plane samples (8-250..8-261, qsel() in
 // enc_mb.inc) and the MB wavefront never interpolates on its critical path. HBM-bound: reads the
-// picture once, writes 4 padded luma + 2 padded chroma planes (~10 MB per 1080p stream).
+// picture once, writes 4 padded luma + 2 padded chroma planes (~10 MB per 1080p stream). These blocks
+// run inside enc_post_kernel (below).
+// The decoder does not use b, h, j: dec_planes_kernel (below) pads G and chroma only, in the same
+// geometry, and dec_recon.inc filters at the point of use.
 namespace h264mi {
 
 // ystrips: luma row strips (blockIdx.y below it); the blocks above it copy the padded chroma planes
@@ -96,9 +99,6 @@ DEV void ref_planes_block(const PlanesLaunch &a, int bx, int by, int bz, int gx)
         for (int i = 0; i < 5; i++) { Mw[i] = Mw[i + 1]; Bw[i][0] = Bw[i + 1][0]; Bw[i][1] = Bw[i + 1][1]; }
     }
 }
-__global__ __launch_bounds__(PT_Q, 8) void ref_planes_kernel(PlanesLaunch a) {
-    ref_planes_block(a, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x);
-}
 
 // Chroma: edge-replicated copies, four samples per thread and dword, PT_H rows per thread: thread i of the
 // chroma blocks -> plane, row strip, column quad (consecutive threads: consecutive quads of a row); CPADX
@@ -129,11 +129,34 @@ static void ref_planes_grid(int cw, int ch, int &gx, int &gy, int &ystrips) {
     const int cq = 2 * ((cw / 2 + 2 * H264MI_CPADX) / 4) * ((ch / 2 + 2 * H264MI_CPADY + PT_H - 1) / PT_H);  // chroma threads
     gy = ystrips + (cq + gx * PT_Q - 1) / (gx * PT_Q);
 }
-static int launch_ref_planes(int S, int cw, int ch, const PlanesDesc *pd, hipStream_t st) {
+// The decoder's reference planes: the edge-padded integer plane G (D.pl[0]; pl[1..3] are not touched and may
+// be null) and the two padded chroma planes, in the geometry above and on the same grid -- a padding copy, no
+// taps. The decoder's reconstruction samples every block once at a known vector and runs the six-tap filters
+// where a vector is fractional (dec_recon.inc), so the b / h / j planes would be written (6.9 MB per 1080p
+// stream and frame) for nothing. A thread copies its column quad over the strip's PT_H rows, all loads first.
+__global__ __launch_bounds__(PT_Q) void dec_planes_kernel(PlanesLaunch a) {
+    const PlanesDesc &D = a.pd[blockIdx.z];
+    if (D.active && *D.active == 0) return;
+    if ((int)blockIdx.y >= a.ystrips) {
+        ref_planes_chroma(a, D, (((int)blockIdx.y - a.ystrips) * (int)gridDim.x + (int)blockIdx.x) * PT_Q + (int)threadIdx.x);
+        return;
+    }
+    const int cw = a.cw, ch = a.ch;
+    const int q = (int)blockIdx.x * PT_Q + (int)threadIdx.x;
+    if (q * 4 >= cw + 2 * H264MI_LPADX) return;
+    const int x0 = q * 4 - H264MI_LPADX, ya = (int)blockIdx.y * PT_H - H264MI_LPADY;  // the quad's first sample, the first row
+    const uint8_t *ref = D.src[D.parity ? (*D.parity & 1) : 0][0];
+    uint32_t v[PT_H];
+#pragma unroll
+    for (int r = 0; r < PT_H; r++) v[r] = planes_row_bytes(ref + (size_t)clip3(0, ch - 1, ya + r) * cw, x0, cw);
+#pragma unroll
+    for (int r = 0; r < PT_H; r++) *(uint32_t *)(D.pl[0] + (ptrdiff_t)(ya + r) * D.ps + x0) = v[r];
+}
+static int launch_dec_planes(int S, int cw, int ch, const PlanesDesc *pd, hipStream_t st) {
     int gx, gy, ystrips;
     ref_planes_grid(cw, ch, gx, gy, ystrips);
     const PlanesLaunch pla{S, cw, ch, pd, ystrips};
-    hipLaunchKernelGGL(ref_planes_kernel, dim3(gx, gy, S), dim3(PT_Q), 0, st, pla);
+    hipLaunchKernelGGL(dec_planes_kernel, dim3(gx, gy, S), dim3(PT_Q), 0, st, pla);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

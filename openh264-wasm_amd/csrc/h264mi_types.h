@@ -141,7 +141,7 @@ struct PlanesDesc {
     const uint8_t *src[2][3];  // candidate source pictures (Y, U, V, coded size), src[*parity & 1] (src[0] if parity == nullptr)
     const int32_t *parity;
     const int32_t *active;     // nullptr, or build only if nonzero (decoder: a picture was produced)
-    uint8_t *pl[4];            // padded G, b, h, j planes at their origin (H264MI_LPADX/Y margins)
+    uint8_t *pl[4];            // padded G, b, h, j planes at their origin (H264MI_LPADX/Y margins); decoder: G only, the rest null
     uint8_t *plc[2];           // padded Cb, Cr at their origin (H264MI_CPADX/Y margins)
     int32_t ps, psc;
 };
@@ -226,7 +226,8 @@ struct DecDesc {
     DecFrame *frm;          // this frame slot's NAL table and parse result
     int32_t cw, ch;         // allocated coded size
     uint64_t *egran;        // MB -> deblocking hand-off, 128 granules per MB (per stream)
-    uint8_t *pl[4];         // padded planes of the reference picture (as the encoder's, per stream)
-    uint8_t *plc[2];
+    uint8_t *pl;            // edge-padded integer luma plane G of the reference picture at its origin (per stream;
+                            // H264MI_LPADX/Y margins, the encoder's geometry -- no half-sample planes: dec_recon.inc)
+    uint8_t *plc[2];        // padded Cb, Cr
     int32_t ps, psc;
 };

@@ -153,7 +153,9 @@ static DecCtx *dec_create(int mbw, int mbh, int S, hipStream_t stream, int B = 1
     const size_t off_egr = off_dgran + al(8 * (size_t)H264MI_DBK_GRANULES_PER_MB * c->nmb);
     const size_t lps = (size_t)c->cw + 2 * H264MI_LPADX, lph = (size_t)c->ch + 2 * H264MI_LPADY;
     const size_t cps = (size_t)c->cw / 2 + 2 * H264MI_CPADX, cph = (size_t)c->ch / 2 + 2 * H264MI_CPADY;
-    const size_t off_pl = off_egr + al(8 * 128 * (size_t)c->nmb), off_plc = off_pl + 4 * al(lps * lph);
+    // reference planes: the padded integer luma plane and padded chroma (no half-sample planes: dec_recon.inc
+    // interpolates from the integer plane -- 3 x 2.3 MB per 1080p stream less than the encoder's layout)
+    const size_t off_pl = off_egr + al(8 * 128 * (size_t)c->nmb), off_plc = off_pl + al(lps * lph);
     const size_t per_stream = off_plc + 2 * al(cps * cph);
     const size_t off_coef = al(sizeof(MbInfo) * c->nmb), off_frm = off_coef + al(sizeof(MbCoef) * c->nmb);
     const size_t per_slot = off_frm + al(sizeof(DecFrame));
@@ -188,14 +190,14 @@ static DecCtx *dec_create(int mbw, int mbh, int S, hipStream_t stream, int B = 1
             d.gran = (uint64_t *)(b + off_gran); d.dgran = (uint64_t *)(b + off_dgran);
             d.info = (MbInfo *)q; d.coef = (MbCoef *)(q + off_coef); d.frm = (DecFrame *)(q + off_frm);
             d.st = c->d_st + s; d.cw = c->cw; d.ch = c->ch; d.egran = (uint64_t *)(b + off_egr);
-            for (int k = 0; k < 4; k++) d.pl[k] = b + off_pl + k * al(lps * lph) + H264MI_LPADY * lps + H264MI_LPADX;
+            d.pl = b + off_pl + H264MI_LPADY * lps + H264MI_LPADX;
             for (int k = 0; k < 2; k++) d.plc[k] = b + off_plc + k * al(cps * cph) + H264MI_CPADY * cps + H264MI_CPADX;
             d.ps = (int)lps; d.psc = (int)cps;
             if (f == 0) {  // planes of the stream's reference picture, built after each reconstructed frame
                 PlanesDesc &pd = hp[s];
                 for (int i = 0; i < 3; i++) { pd.src[0][i] = d.pic[0][i]; pd.src[1][i] = d.pic[1][i]; }
                 pd.parity = &c->d_st[s].parity; pd.active = &c->d_st[s].got_pic;
-                for (int k = 0; k < 4; k++) pd.pl[k] = d.pl[k];
+                pd.pl[0] = d.pl; pd.pl[1] = pd.pl[2] = pd.pl[3] = nullptr;  // dec_planes_kernel writes G and chroma only
                 pd.plc[0] = d.plc[0]; pd.plc[1] = d.plc[1]; pd.ps = d.ps; pd.psc = d.psc;
             }
             DbkDesc &k = hd[(size_t)f * S + s];
@@ -302,7 +304,7 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
         } else if (outputs)
             hipLaunchKernelGGL(dec_output_kernel, dim3((2 * c->ch + 3) / 4, S), dim3(256), 0, c->stream,
                                DecOutLaunch{S, c->cw, c->ch, df, c->d_in + (size_t)(slot0 + f) * S});
-        if (launch_ref_planes(S, c->cw, c->ch, c->d_pd, c->stream) != 0) return -1;  // the next frame's reference planes
+        if (launch_dec_planes(S, c->cw, c->ch, c->d_pd, c->stream) != 0) return -1;  // the next frame's padded reference planes
     }
     HIPCHECK(hipEventRecord(c->ev_recon[g], c->stream));
     HIPCHECK(hipGetLastError());
