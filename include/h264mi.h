@@ -403,6 +403,59 @@ int h264mi_mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, 
 int h264mi_enc_encode_composed(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc,
                                const h264mi_cell *cells, int ncells, int bg_y, int bg_cb, int bg_cr);
 
+/* Alpha-blended overlays on the device: a label, a watermark, a frame round the active speaker.
+   An I420A sprite is a tight ow x oh frame (both even, 2..8192): Y (ow * oh bytes), Cb and Cr ((ow/2) * (oh/2) each),
+   then A (ow * oh, full resolution; straight alpha, not premultiplied, 255 opaque); 2 * ow * oh + 2 * (ow/2) * (oh/2)
+   bytes, nsprites of them back to back at any alignment. A placement takes the w x h crop of sprite `sprite` at
+   (sx, sy) 1:1 onto canvas `canvas` at (dx, dy); there is no scaling. */
+typedef struct h264mi_overlay {
+    int32_t sprite;          /* sprite, 0 .. nsprites - 1 */
+    int32_t canvas;          /* canvas, 0 .. ncanvas - 1 */
+    int32_t sx, sy, w, h;    /* crop: a rectangle of the sprite */
+    int32_t dx, dy;          /* where its first sample goes on the canvas */
+    int32_t opacity;         /* 0 .. 256, scales the sprite's alpha; 256 leaves it as it is */
+    int32_t reserved;        /* 0 */
+} h264mi_overlay;            /* 40 bytes */
+#define H264MI_OVERLAY_PER_LAUNCH 64 /* placements that travel in one kernel launch's arguments */
+/* async on hip_stream: n tight RGBA8 frames (4 * w * h bytes, 4-byte aligned) at d_rgba to n I420A sprites at d_dst
+   (any alignment), one launch. Y, Cb and Cr are exactly the bytes h264mi_rgba_to_i420_dev gives for the same RGBA
+   (chroma from the top-left pixel of each 2x2, alpha ignored); A is the RGBA's fourth byte. Returns -1, before the
+   device is touched, on a null pointer, a misaligned source, n <= 0, or a side that is odd or outside 2..8192. */
+int h264mi_rgba_to_i420a_dev(void *d_dst, const void *d_rgba, int w, int h, int n, void *hip_stream);
+/* async on hip_stream. Canvases: ncanvas tight cw x ch I420 frames (even, 2..8192) back to back at d_canvas, any
+   alignment. Every placement is blended onto its rectangle in plain non-negative integers. For a luma sample with
+   sprite alpha A, sprite sample s and canvas sample d:
+     a   = (A * opacity + 128) >> 8                 0 .. 255
+     out = (d * (255 - a) + s * a + 127) / 255      floor division
+   and for a chroma sample the same blend with a = (a00 + a01 + a10 + a11 + 2) >> 2 over the effective alphas a of the
+   four luma positions it covers. a == 0 keeps the canvas byte, a == 255 copies the sprite's; A = 255 with opacity 256
+   is a == 255. No byte outside a rectangle is written. Placements may overlap: the result is that of applying them one
+   after another in list order, the last on top. ov is a host array, read before the call returns; placements travel
+   as kernel arguments, and the list is cut into launches, in list order on the stream, at every placement that shares
+   a sample of a canvas with one already in the launch and after H264MI_OVERLAY_PER_LAUNCH placements, so that stream
+   order is the order of the list. Exact integers: the same bytes from run to run.
+   Returns 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer; ncanvas or
+   nsprites <= 0; nov <= 0 or above 4096; a size that is odd or outside 2..8192; sx, sy, w, h, dx or dy odd or
+   negative, w or h below 2; a crop not inside the sprite or a rectangle not inside the canvas; sprite or canvas out
+   of range; opacity outside 0..256; reserved != 0; sprite and canvas byte ranges that overlap. Scaled or rotated
+   sprites, premultiplied alpha and text rendering are not provided (callers render labels to RGBA). */
+int h264mi_i420_overlay_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_sprites, int ow, int oh, int nsprites,
+                            const h264mi_overlay *ov, int nov, void *hip_stream);
+/* the encoder's persistent overlay list: the canvases are its nstreams input frames. The list is copied and held by
+   the encoder; the sprites stay the caller's device memory and are read in stream order at every frame step, so a
+   caller may animate them (on the encoder's stream, h264mi_enc_stream, or ordered against it: an encoder made without
+   a stream has a non-blocking one of its own, which does not wait for the null stream). With a list in force h264mi_enc_encode_rgba, _scaled and _composed blend it into the input
+   area after their own launches and before the frame step; h264mi_enc_encode(e, d_frames) first copies the caller's
+   frames into the input area (one device-to-device async copy on the encoder's stream; none when d_frames is
+   h264mi_enc_input_buffer itself), blends there and runs the frame step from the input area: the caller's frames are
+   never modified, and a d_frames that partly overlaps the input area is refused with nothing enqueued. The quality
+   records then compare the overlaid source with the reconstruction. nov == 0 clears the list; with no list in force
+   every path enqueues exactly what it did before. Returns -1, with the previous list still in force, on everything
+   h264mi_i420_overlay_dev refuses, a canvas the encoder has not, and sprites that overlap the input area. */
+int h264mi_enc_set_overlays(h264mi_encoder *e, const void *d_sprites, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov);
+/* placements in force (0: none), -1 on a null encoder */
+int h264mi_enc_overlays(h264mi_encoder *e);
+
 /* library self-description */
 const char *h264mi_version(void);
 

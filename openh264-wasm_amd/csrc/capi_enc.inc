@@ -190,9 +190,47 @@ int h264mi_enc_frames_skipped(h264mi_encoder *e, int stream) {
     if (hipMemcpy(&st, e->c->d_st + stream, sizeof(EncState), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return st.skipped;
 }
+// the overlay list in force blended into the input area (DESIGN.md §5.6; overlay.hip); nothing without a list
+static int enc_blend_overlays(EncCtx *c) {
+    if (c->ov.empty()) return 0;
+    return launch_overlay_i420(c->d_src, c->w, c->h, c->ov_sprites, c->ov_w, c->ov_h, c->ov.data(), (int)c->ov.size(), c->stream);
+}
+// with an overlay list in force the caller's frames are copied into the input area, blended there and coded from there
 int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
     if (!e || !d_frames) return -1;
-    return enc_frame(e->c, (const uint8_t *)d_frames);
+    EncCtx *c = e->c;
+    if (c->ov.empty()) return enc_frame(c, (const uint8_t *)d_frames);
+    if (d_frames != (const void *)c->d_src) {
+        const uintptr_t a = (uintptr_t)d_frames, b = (uintptr_t)c->d_src, nb = (uintptr_t)c->S * c->fbytes;
+        if (a < b + nb && b < a + nb) return -1;  // partly inside the input area
+        if (hipMemcpyAsync(c->d_src, d_frames, nb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
+    }
+    if (enc_blend_overlays(c) != 0) return -1;
+    return enc_frame(c, c->d_src);
+}
+int h264mi_enc_set_overlays(h264mi_encoder *e, const void *d_sprites, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov) {
+    if (!e) return -1;
+    EncCtx *c = e->c;
+    if (nov == 0) { c->ov.clear(); c->ov_sprites = nullptr; return 0; }
+    if (!d_sprites || !overlay_args_ok(c->w, c->h, c->S, ow, oh, nsprites, ov, nov) ||
+        overlay_ranges_overlap(c->d_src, c->w, c->h, c->S, d_sprites, ow, oh, nsprites))
+        return -1;
+    c->ov.assign(ov, ov + nov);
+    c->ov_sprites = (const uint8_t *)d_sprites; c->ov_w = ow; c->ov_h = oh;
+    return 0;
+}
+int h264mi_enc_overlays(h264mi_encoder *e) { return e ? (int)e->c->ov.size() : -1; }
+// Sprites from RGBA and the standalone blend (DESIGN.md §5.6; overlay.hip)
+int h264mi_rgba_to_i420a_dev(void *d_dst, const void *d_rgba, int w, int h, int n, void *hip_stream) {
+    if (!d_dst || !d_rgba || ((uintptr_t)d_rgba & 3) || !rgba_to_i420a_args_ok(w, h, n)) return -1;
+    return launch_rgba_to_i420a((const uint8_t *)d_rgba, w, h, n, (uint8_t *)d_dst, (hipStream_t)hip_stream);
+}
+int h264mi_i420_overlay_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_sprites, int ow, int oh, int nsprites,
+                            const h264mi_overlay *ov, int nov, void *hip_stream) {
+    if (!d_canvas || !d_sprites || !overlay_args_ok(cw, ch, ncanvas, ow, oh, nsprites, ov, nov) ||
+        overlay_ranges_overlap(d_canvas, cw, ch, ncanvas, d_sprites, ow, oh, nsprites))
+        return -1;
+    return launch_overlay_i420((uint8_t *)d_canvas, cw, ch, (const uint8_t *)d_sprites, ow, oh, ov, nov, (hipStream_t)hip_stream);
 }
 // nstreams tight RGBA8 frames back to back: one batched conversion into the encoder's own input area on its
 // stream, then the frame step as h264mi_enc_encode runs it
@@ -200,6 +238,7 @@ int h264mi_enc_encode_rgba(h264mi_encoder *e, const void *d_rgba_frames) {
     if (!e || !d_rgba_frames || ((uintptr_t)d_rgba_frames & 3)) return -1;
     EncCtx *c = e->c;
     if (launch_rgba_to_i420((const uint8_t *)d_rgba_frames, c->w, c->h, c->S, c->d_src, c->stream) != 0) return -1;
+    if (enc_blend_overlays(c) != 0) return -1;
     return enc_frame(c, c->d_src);
 }
 // Area-average downscaling (DESIGN.md §5.3; scale.hip): n tight I420 frames of one geometry pair, one launch
@@ -215,6 +254,7 @@ int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w,
     EncCtx *c = e->c;
     if (!scale_args_ok(c->w, c->h, src_w, src_h, c->S) || scale_ranges_overlap(c->d_src, c->w, c->h, d_frames, src_w, src_h, c->S)) return -1;
     if (launch_scale_i420(c->d_src, c->w, c->h, (const uint8_t *)d_frames, src_w, src_h, c->S, c->stream) != 0) return -1;
+    if (enc_blend_overlays(c) != 0) return -1;
     return enc_frame(c, c->d_src);
 }
 // Several pictures into one (DESIGN.md §5.4; compose.hip): every cell's crop of a source frame area-averaged into its
@@ -245,6 +285,7 @@ int h264mi_enc_encode_composed(h264mi_encoder *e, const void *d_src, int src_w, 
     if (bg_y > 255 || bg_cb > 255 || bg_cr > 255 || (bg_y >= 0 && !fill_args_ok(c->w, c->h, c->S, bg_y, bg_cb, bg_cr))) return -1;
     if (bg_y >= 0 && launch_fill_i420(c->d_src, c->w, c->h, c->S, bg_y, bg_cb, bg_cr, c->stream) != 0) return -1;
     if (launch_compose_i420(c->d_src, c->w, c->h, (const uint8_t *)d_src, src_w, src_h, cells, ncells, c->stream) != 0) return -1;
+    if (enc_blend_overlays(c) != 0) return -1;
     return enc_frame(c, c->d_src);
 }
 const void *h264mi_enc_input_buffer(h264mi_encoder *e) { return e ? e->c->d_src : nullptr; }

@@ -190,6 +190,11 @@ struct EncCtx {
     int ncu = 256;               // the device's CUs (enc_frame's build choice)
     std::vector<hipEvent_t> ev;
     int ev_used = 0;
+    // the overlay list in force (h264mi_enc_set_overlays; overlay.hip): host copies of the placements, the caller's
+    // sprites. Empty: every frame step enqueues what it did before the list existed
+    std::vector<h264mi_overlay> ov;
+    const uint8_t *ov_sprites = nullptr;
+    int ov_w = 0, ov_h = 0;
 };
 
 struct EncMbLaunch {  // enc_mb_kernel reads the source frames through this launch-time base
@@ -380,6 +385,12 @@ bool compose_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc
 bool compose_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *src, int src_w, int src_h, int nsrc);
 bool fill_args_ok(int w, int h, int n, int y, int cb, int cr);
 int mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch);
+// overlay.hip (likewise)
+int launch_overlay_i420(uint8_t *dst, int cw, int ch, const uint8_t *spr, int ow, int oh, const h264mi_overlay *ov, int nov, hipStream_t s);
+int launch_rgba_to_i420a(const uint8_t *d_rgba, int w, int h, int n, uint8_t *d_out, hipStream_t s);
+bool overlay_args_ok(int cw, int ch, int ncanvas, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov);
+bool overlay_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *spr, int ow, int oh, int nsprites);
+bool rgba_to_i420a_args_ok(int w, int h, int n);
 
 // One frame step for all S streams. src: S tight I420 frames, contiguous, in device memory.
 static int enc_frame(EncCtx *c, const uint8_t *d_frames) {

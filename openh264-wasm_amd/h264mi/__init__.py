@@ -136,6 +136,10 @@ def lib():
             'h264mi_i420_fill_dev': (i, [vp, i, i, i, i, i, i, vp]),
             'h264mi_mosaic_cells': (i, [vp, i, i, i, i, i, i]),
             'h264mi_enc_encode_composed': (i, [vp, vp, i, i, i, vp, i, i, i, i]),
+            'h264mi_rgba_to_i420a_dev': (i, [vp, vp, i, i, i, vp]),
+            'h264mi_i420_overlay_dev': (i, [vp, i, i, i, vp, i, i, i, vp, i, vp]),
+            'h264mi_enc_set_overlays': (i, [vp, vp, i, i, i, vp, i]),
+            'h264mi_enc_overlays': (i, [vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -308,6 +312,7 @@ class BatchEncoder:
         self._e = self._L.h264mi_enc_create(width, height, bitrate, nstreams, ctypes.c_void_p(hs))
         if not self._e:
             raise RuntimeError('h264mi_enc_create failed')
+        self._ov_sprites = None  # the sprite tensor of the overlay list in force (set_overlays)
         _live.add(self)
 
     def encode(self, frames):
@@ -344,6 +349,32 @@ class BatchEncoder:
         if self._L.h264mi_enc_encode_composed(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
                                               y, cb, cr) != 0:
             raise ValueError(f'h264mi_enc_encode_composed refused {len(arr)} cells of {nsrc} sources {src_w}x{src_h} -> {self.w}x{self.h}')
+
+    def set_overlays(self, sprites, ow, oh, nsprites, overlays):
+        """sprites: uint8 CUDA tensor holding nsprites I420A sprites of ow x oh back to back (i420a_bytes each), any
+        alignment; overlays: a sequence of Overlay whose canvases are this encoder's S input frames. From the next
+        frame step on every encode*() blends the list into the input area, in list order, in front of the frame step
+        (h264mi_enc_set_overlays); encode() then codes a copy of the caller's frames, which stay as they are. The
+        encoder keeps the placements and a reference to the tensor, whose bytes are read at every step. An empty
+        sequence clears the list. ValueError, with the previous list still in force, for whatever i420_overlay
+        refuses, a canvas the encoder has not, or sprites inside the input area."""
+        arr = _overlay_array(overlays)
+        if len(arr) == 0:
+            return self.clear_overlays()
+        assert sprites.is_cuda and (nsprites <= 0 or min(ow, oh) <= 0 or sprites.numel() >= nsprites * i420a_bytes(ow, oh))
+        if self._L.h264mi_enc_set_overlays(self._e, ctypes.c_void_p(sprites.data_ptr()), int(ow), int(oh), int(nsprites), arr, len(arr)) != 0:
+            raise ValueError(f'h264mi_enc_set_overlays refused {len(arr)} placements of {nsprites} sprites {ow}x{oh} on {self.w}x{self.h}')
+        self._ov_sprites = sprites
+
+    def clear_overlays(self):
+        """no overlay list from the next frame step on: every encode*() enqueues what it did before one was set"""
+        if self._L.h264mi_enc_set_overlays(self._e, None, 0, 0, 0, None, 0) != 0:
+            raise RuntimeError('h264mi_enc_set_overlays failed')
+        self._ov_sprites = None
+
+    def overlays(self):
+        """placements in force (h264mi_enc_overlays)"""
+        return self._L.h264mi_enc_overlays(self._e)
 
     def force_idr(self, stream=-1):
         self._L.h264mi_enc_force_idr(self._e, stream)
@@ -797,6 +828,57 @@ def i420_compose(canvas, cw, ch, ncanvas, src, src_w, src_h, nsrc, cells, stream
     if lib().h264mi_i420_compose_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(src.data_ptr()), src_w, src_h,
                                      nsrc, arr, len(arr), ctypes.c_void_p(hs)) != 0:
         raise ValueError(f'bad arguments: {len(arr)} cells of {nsrc} sources {src_w}x{src_h} on {ncanvas} canvases {cw}x{ch}')
+
+
+class Overlay(ctypes.Structure):
+    """h264mi_overlay (include/h264mi.h): the w x h crop at (sx, sy) of sprite `sprite` blended 1:1 onto canvas
+    `canvas` at (dx, dy), its alpha scaled by opacity / 256; reserved is 0; 40 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('sprite', 'canvas', 'sx', 'sy', 'w', 'h', 'dx', 'dy', 'opacity', 'reserved')]
+
+    def __repr__(self):
+        return 'Overlay(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
+
+
+def _overlay_array(overlays):
+    overlays = list(overlays)
+    return (Overlay * len(overlays))(*overlays)
+
+
+def i420a_bytes(w, h):
+    """bytes of a tight w x h I420A sprite: Y, Cb, Cr, then a full-resolution alpha plane"""
+    return 2 * w * h + 2 * (w // 2) * (h // 2)
+
+
+def rgba_to_i420a(dst, src, w, h, n, stream=None):
+    """n tight RGBA8 frames (uint8 CUDA tensor src, 4-byte aligned) to n I420A sprites (dst, any alignment), one launch,
+    async on stream (default: the current one); h264mi_rgba_to_i420a_dev. Y, Cb, Cr as rgba_to_i420, A the fourth byte.
+    ValueError on a bad argument (an odd side or one outside 2..8192, n <= 0, a misaligned source)."""
+    import torch
+    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
+    assert dst.is_contiguous() and src.is_contiguous()
+    assert n <= 0 or min(w, h) <= 0 or (dst.numel() >= n * i420a_bytes(w, h) and src.numel() >= n * w * h * 4)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_rgba_to_i420a_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {w}x{h}, {n} frames')
+
+
+def i420_overlay(canvas, cw, ch, ncanvas, sprites, ow, oh, nsprites, overlays, stream=None):
+    """every placement's crop of one of nsprites I420A sprites of ow x oh (uint8 CUDA tensor sprites) alpha-blended onto
+    its rectangle of one of ncanvas tight cw x ch I420 frames (canvas), any alignment, async on stream (default: the
+    current one); h264mi_i420_overlay_dev. Placements may overlap: list order, the last on top. Canvas bytes outside the
+    rectangles keep their value. Exact integers: the bytes equal tests/overlayref.py's. ValueError on a bad argument
+    (odd fields, a crop outside the sprite, a rectangle outside the canvas, opacity outside 0..256, reserved != 0,
+    overlapping buffers, no placement or more than 4096)."""
+    import torch
+    assert canvas.is_cuda and sprites.is_cuda and canvas.dtype == torch.uint8 and sprites.dtype == torch.uint8
+    assert canvas.is_contiguous() and sprites.is_contiguous()
+    cfb = cw * ch + 2 * (cw // 2) * (ch // 2)
+    assert min(ncanvas, nsprites, ow, oh, cw, ch) <= 0 or (canvas.numel() >= ncanvas * cfb and sprites.numel() >= nsprites * i420a_bytes(ow, oh))
+    arr = _overlay_array(overlays)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_i420_overlay_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(sprites.data_ptr()), ow, oh,
+                                     nsprites, arr, len(arr), ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {len(arr)} placements of {nsprites} sprites {ow}x{oh} on {ncanvas} canvases {cw}x{ch}')
 
 
 def i420_fill(frames, w, h, n, y, cb, cr, stream=None):
