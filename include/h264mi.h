@@ -349,7 +349,7 @@ int h264mi_i420_to_rgba_dev(void *d_rgba, const void *d_i420, int w, int h, int 
    equal a restatement on any host; equal sizes return the source bytes, 2:1 both ways gives (a + b + c + d + 2) >> 2.
    Returns 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer, n <= 0, an
    odd size, dw outside 2..sw, dh outside 2..sh, sw or sh above 4096, or source and destination byte ranges that
-   overlap. Upscaling and other filters are not provided. */
+   overlap. Enlarging is h264mi_i420_upscale_dev below; other shrinking filters are not provided. */
 int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, void *hip_stream);
 
 /* Several pictures into one on the device: a gallery of decoded streams, one composed picture per
@@ -373,7 +373,8 @@ typedef struct h264mi_cell {
    4096, or a canvas side above 8192; a crop not inside the source, or a rectangle not inside the canvas; dw outside
    2..sw or dh outside 2..sh; src or canvas out of range; two cells of one canvas whose rectangles share a sample;
    source and canvas byte ranges that overlap. A picture-in-picture is two calls in stream order, not overlapping
-   cells. Upscaling, blending and per-source geometries within one call are not provided. */
+   cells. Enlarging cells go through h264mi_i420_compose_any_dev below, blending through h264mi_i420_overlay_dev;
+   per-source geometries within one call are not provided. */
 int h264mi_i420_compose_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,
                             const h264mi_cell *cells, int ncells, void *hip_stream);
 /* async on hip_stream: every Y sample of n tight w x h I420 frames at d_frames (any alignment) is set to y, every Cb
@@ -384,7 +385,7 @@ int h264mi_i420_fill_dev(void *d_frames, int w, int h, int n, int y, int cb, int
    arithmetic is integers, all divisions floor divisions. cols = the smallest c with c * c >= n, rows = (n + cols - 1)
    / cols; source k goes to slot column k % cols, slot row k / cols. The slot is [X0, X1) x [Y0, Y1) with
    X0 = 2 * (col * cw / (2 * cols)), X1 = 2 * ((col + 1) * cw / (2 * cols)), Y0 and Y1 likewise from row, ch, rows. The
-   picture inside the slot keeps the source's shape and is never enlarged:
+   picture inside the slot keeps the source's shape and is never enlarged (h264mi_speaker_cells below may enlarge):
      dw = min(src_w, X1 - X0, 2 * ((Y1 - Y0) * src_w / (2 * src_h)))
      dh = min(src_h, Y1 - Y0, 2 * (dw * src_h / (2 * src_w)))
    and is centred: dx = X0 + 2 * ((X1 - X0 - dw) / 4), dy = Y0 + 2 * ((Y1 - Y0 - dh) / 4). The crop is the whole source.
@@ -455,6 +456,65 @@ int h264mi_i420_overlay_dev(void *d_canvas, int cw, int ch, int ncanvas, const v
 int h264mi_enc_set_overlays(h264mi_encoder *e, const void *d_sprites, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov);
 /* placements in force (0: none), -1 on a null encoder */
 int h264mi_enc_overlays(h264mi_encoder *e);
+
+/* Enlarging on the device: a low rung filling most of a larger canvas, a gallery of small pictures on
+   a large one, a 4:3 source pillar-boxed into a larger 16:9 encode. Exact integers, int32 throughout. */
+#define H264MI_FILTER_BILINEAR 0
+#define H264MI_FILTER_BICUBIC 1      /* Catmull-Rom */
+#define H264MI_UPSCALE_PER_LAUNCH 64 /* enlarging cells that travel in one kernel launch's arguments */
+/* async on hip_stream: n tight sw x sh I420 frames back to back at d_src (any alignment) to n tight dw x dh frames at
+   d_dst, dw >= sw and dh >= sh. Every plane is enlarged on its own (Y sw x sh -> dw x dh; Cb, Cr sw/2 x sh/2 ->
+   dw/2 x dh/2). For a plane of pw x ph samples enlarged to qw x qh, per axis, with sample centres aligned and 16
+   phases (o the output index, p = pw or ph, q = qw or qh):
+     N = (2 o + 1) p - q                      may be negative
+     P = floor((16 N + q) / (2 q))            floor division, not C truncation
+     i = P >> 4 (arithmetic), f = P & 15
+     taps at i - 1, i, i + 1, i + 2, each index clamped to 0 .. p - 1: edge samples repeat
+     bicubic weights (sum 8192):  W-1 = -f^3 + 32 f^2 - 256 f      W0 = 3 f^3 - 80 f^2 + 8192
+                                  W1 = -3 f^3 + 64 f^2 + 256 f     W2 = f^3 - 16 f^2
+     bilinear weights (sum 8192): W-1 = 0, W0 = (16 - f) 512, W1 = f 512, W2 = 0
+   Horizontal first: h = sum_k Wx_k p(x_k, j), exact, |h| < 2^22; H = (h + 16) >> 5 (arithmetic; 8 fractional bits,
+   -8160 .. 73440). Then vertical: v = sum_k Wy_k H(ox, y_k), |v| <= 9216 * 73440 + 1024 * 8160 < 2^31;
+   out = clamp((v + 2^20) >> 21, 0, 255). p == q gives f = 0, i = o and the source bytes; a constant plane stays
+   constant. The same bytes from run to run, equal to a restatement on any host.
+   Returns 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer, n <= 0, an odd
+   size, sw or sh outside 2..4096, dw outside sw..8192, dh outside sh..8192, a filter that is neither of the two, or
+   source and destination byte ranges that overlap. Wider filters (Lanczos) are not provided. */
+int h264mi_i420_upscale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, int filter, void *hip_stream);
+/* async on hip_stream: h264mi_i420_compose_dev with cells that may enlarge. The same h264mi_cell, buffers and checks,
+   except for each cell's size rule. A cell with dw <= sw && dh <= sh is a shrinking cell: it takes compose's path and
+   gets exactly the bytes h264mi_i420_compose_dev gives it, equal sizes (a copy) included. A cell with dw >= sw &&
+   dh >= sh and one of them larger is an enlarging cell: per plane its rectangle receives the crop enlarged by the
+   formula of h264mi_i420_upscale_dev with pw x ph = the crop's size in the plane (origin and sizes halved for chroma)
+   and qw x qh = the rectangle's; the taps clamp to the crop: nothing outside the crop is read, even where the source
+   frame has samples there. filter applies to the enlarging cells only. No two cells of one canvas, of either kind,
+   may share a sample, so the result does not depend on the cells' order; the shrinking cells are launched first
+   (64 to a launch), then the enlarging ones (H264MI_UPSCALE_PER_LAUNCH to a launch), on the same stream.
+   Returns 0, or -1 before the device is touched on everything h264mi_i420_compose_dev refuses but a rectangle
+   larger than its crop, on a cell that enlarges one axis and shrinks the other, and on an unknown filter. */
+int h264mi_i420_compose_any_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,
+                                const h264mi_cell *cells, int ncells, int filter, void *hip_stream);
+/* host only: the active-speaker layout of n whole src_w x src_h sources on canvas 0 of cw x ch, into out[0 .. n - 1].
+   Integers and floor divisions. For n == 1 the slot is the whole canvas. For n >= 2 a strip of height
+   SH = 2 * (ch / 8) lies at the bottom: source `speaker` has the slot [0, cw) x [0, ch - SH), the other m = n - 1
+   sources, in index order, slot k = 0 .. m - 1 of the strip: X0 = 2 * (k * cw / (2 * m)),
+   X1 = 2 * ((k + 1) * cw / (2 * m)), Y0 = ch - SH, Y1 = ch. Inside its slot a picture keeps the source's shape, may be
+   enlarged, and is centred as in h264mi_mosaic_cells:
+     dw = min(X1 - X0, 2 * ((Y1 - Y0) * src_w / (2 * src_h)))
+     dh = min(Y1 - Y0, 2 * (dw * src_h / (2 * src_w)))
+     dx = X0 + 2 * ((X1 - X0 - dw) / 4), dy = Y0 + 2 * ((Y1 - Y0 - dh) / 4)
+   out[k] is source k's cell; the crop is the whole source. dw > src_w implies dh >= src_h and dw < src_w implies
+   dh < src_h: no cell enlarges one axis and shrinks the other. Returns n, or -1 on a bad argument (a null pointer,
+   n <= 0 or above 4096, speaker outside 0 .. n - 1, sizes that h264mi_i420_compose_any_dev refuses), on cap < n, or
+   when some dw or dh comes out below 2. 3 sources of 640x360 on 1280x720 with speaker 1: the speaker 960x540 at
+   (160, 0), sources 0 and 2 320x180 at (160, 540) and (800, 540). */
+int h264mi_speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch);
+/* async, as h264mi_enc_encode_composed, with cells of both kinds as h264mi_i420_compose_any_dev takes them: an optional
+   fill, the shrinking cells' launch(es), the enlarging cells' launch(es), an overlay list in force, then the frame
+   step, everything on the encoder's stream. Returns -1 and enqueues nothing on whatever h264mi_i420_compose_any_dev or
+   h264mi_enc_encode_composed (the size rule apart) refuses. */
+int h264mi_enc_encode_composed_any(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc,
+                                   const h264mi_cell *cells, int ncells, int filter, int bg_y, int bg_cb, int bg_cr);
 
 /* library self-description */
 const char *h264mi_version(void);

@@ -7,6 +7,7 @@ SRC_QUALITY = os.path.join(HERE, 'csrc', 'quality.hip')  # its own code object (
 SRC_SCALE = os.path.join(HERE, 'csrc', 'scale.hip')  # likewise
 SRC_COMPOSE = os.path.join(HERE, 'csrc', 'compose.hip')  # likewise
 SRC_OVERLAY = os.path.join(HERE, 'csrc', 'overlay.hip')  # likewise
+SRC_UPSCALE = os.path.join(HERE, 'csrc', 'upscale.hip')  # likewise
 OUT = os.path.join(HERE, 'lib', 'libh264mi.so')
 
 
@@ -17,7 +18,7 @@ def build(force=False, verbose=False):
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wno-unused-result',
-           '-Wno-pass-failed', '-o', OUT + '.tmp', SRC, SRC_QUALITY, SRC_SCALE, SRC_COMPOSE, SRC_OVERLAY]
+           '-Wno-pass-failed', '-o', OUT + '.tmp', SRC, SRC_QUALITY, SRC_SCALE, SRC_COMPOSE, SRC_OVERLAY, SRC_UPSCALE]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)

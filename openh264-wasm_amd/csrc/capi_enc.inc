@@ -288,6 +288,36 @@ int h264mi_enc_encode_composed(h264mi_encoder *e, const void *d_src, int src_w, 
     if (enc_blend_overlays(c) != 0) return -1;
     return enc_frame(c, c->d_src);
 }
+// Enlarging (DESIGN.md §5.7; upscale.hip): whole frames, cells of both kinds, the active-speaker layout
+int h264mi_i420_upscale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, int filter, void *hip_stream) {
+    if (!d_dst || !d_src || !upscale_args_ok(dw, dh, sw, sh, n, filter) || upscale_ranges_overlap(d_dst, dw, dh, d_src, sw, sh, n)) return -1;
+    return launch_upscale_i420((uint8_t *)d_dst, dw, dh, (const uint8_t *)d_src, sw, sh, n, filter, (hipStream_t)hip_stream);
+}
+int h264mi_i420_compose_any_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,
+                                const h264mi_cell *cells, int ncells, int filter, void *hip_stream) {
+    if (!d_canvas || !d_src || !compose_any_args_ok(cw, ch, ncanvas, src_w, src_h, nsrc, cells, ncells, filter) ||
+        compose_ranges_overlap(d_canvas, cw, ch, ncanvas, d_src, src_w, src_h, nsrc))
+        return -1;
+    return launch_compose_any_i420((uint8_t *)d_canvas, cw, ch, (const uint8_t *)d_src, src_w, src_h, cells, ncells, filter,
+                                   (hipStream_t)hip_stream);
+}
+int h264mi_speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch) {
+    return speaker_cells(out, cap, n, speaker, src_w, src_h, cw, ch);
+}
+// h264mi_enc_encode_composed with cells that may enlarge. Every refusal comes before the first launch
+int h264mi_enc_encode_composed_any(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
+                                   int filter, int bg_y, int bg_cb, int bg_cr) {
+    if (!e || !d_src) return -1;
+    EncCtx *c = e->c;
+    if (!compose_any_args_ok(c->w, c->h, c->S, src_w, src_h, nsrc, cells, ncells, filter) ||
+        compose_ranges_overlap(c->d_src, c->w, c->h, c->S, d_src, src_w, src_h, nsrc))
+        return -1;
+    if (bg_y > 255 || bg_cb > 255 || bg_cr > 255 || (bg_y >= 0 && !fill_args_ok(c->w, c->h, c->S, bg_y, bg_cb, bg_cr))) return -1;
+    if (bg_y >= 0 && launch_fill_i420(c->d_src, c->w, c->h, c->S, bg_y, bg_cb, bg_cr, c->stream) != 0) return -1;
+    if (launch_compose_any_i420(c->d_src, c->w, c->h, (const uint8_t *)d_src, src_w, src_h, cells, ncells, filter, c->stream) != 0) return -1;
+    if (enc_blend_overlays(c) != 0) return -1;
+    return enc_frame(c, c->d_src);
+}
 const void *h264mi_enc_input_buffer(h264mi_encoder *e) { return e ? e->c->d_src : nullptr; }
 size_t h264mi_enc_frame_bytes(h264mi_encoder *e) { return e ? e->c->fbytes : 0; }
 size_t h264mi_enc_rgba_frame_bytes(h264mi_encoder *e) { return e ? (size_t)e->c->w * e->c->h * 4 : 0; }

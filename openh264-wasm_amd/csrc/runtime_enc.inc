@@ -391,6 +391,14 @@ int launch_rgba_to_i420a(const uint8_t *d_rgba, int w, int h, int n, uint8_t *d_
 bool overlay_args_ok(int cw, int ch, int ncanvas, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov);
 bool overlay_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *spr, int ow, int oh, int nsprites);
 bool rgba_to_i420a_args_ok(int w, int h, int n);
+// upscale.hip (likewise)
+int launch_upscale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, int filter, hipStream_t s);
+bool upscale_args_ok(int dw, int dh, int sw, int sh, int n, int filter);
+bool upscale_ranges_overlap(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n);
+int launch_compose_any_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
+                            int filter, hipStream_t s);
+bool compose_any_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells, int filter);
+int speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch);
 
 // One frame step for all S streams. src: S tight I420 frames, contiguous, in device memory.
 static int enc_frame(EncCtx *c, const uint8_t *d_frames) {

@@ -140,6 +140,10 @@ def lib():
             'h264mi_i420_overlay_dev': (i, [vp, i, i, i, vp, i, i, i, vp, i, vp]),
             'h264mi_enc_set_overlays': (i, [vp, vp, i, i, i, vp, i]),
             'h264mi_enc_overlays': (i, [vp]),
+            'h264mi_i420_upscale_dev': (i, [vp, i, i, vp, i, i, i, i, vp]),
+            'h264mi_i420_compose_any_dev': (i, [vp, i, i, i, vp, i, i, i, vp, i, i, vp]),
+            'h264mi_speaker_cells': (i, [vp, i, i, i, i, i, i, i]),
+            'h264mi_enc_encode_composed_any': (i, [vp, vp, i, i, i, vp, i, i, i, i, i]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -349,6 +353,19 @@ class BatchEncoder:
         if self._L.h264mi_enc_encode_composed(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
                                               y, cb, cr) != 0:
             raise ValueError(f'h264mi_enc_encode_composed refused {len(arr)} cells of {nsrc} sources {src_w}x{src_h} -> {self.w}x{self.h}')
+
+    def encode_composed_any(self, src, src_w, src_h, nsrc, cells, filter=1, bg=(16, 128, 128)):
+        """encode_composed() with cells that may enlarge (i420_compose_any): a cell no larger than its crop is
+        area-averaged as there, a cell at least as large both ways is enlarged with filter (FILTER_BILINEAR or
+        FILTER_BICUBIC), taps clamped to the crop; then an overlay list in force and the frame step of encode(), all on
+        the encoder's stream (h264mi_enc_encode_composed_any). ValueError, with nothing enqueued, for whatever
+        i420_compose_any refuses or a background above 255."""
+        assert src.is_cuda and (nsrc <= 0 or min(src_w, src_h) <= 0 or src.numel() >= nsrc * (src_w * src_h + 2 * (src_w // 2) * (src_h // 2)))
+        arr = _cell_array(cells)
+        y, cb, cr = (-1, 0, 0) if bg is None else (int(v) for v in bg)
+        if self._L.h264mi_enc_encode_composed_any(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
+                                                  int(filter), y, cb, cr) != 0:
+            raise ValueError(f'h264mi_enc_encode_composed_any refused {len(arr)} cells of {nsrc} sources {src_w}x{src_h} -> {self.w}x{self.h}')
 
     def set_overlays(self, sprites, ow, oh, nsprites, overlays):
         """sprites: uint8 CUDA tensor holding nsprites I420A sprites of ow x oh back to back (i420a_bytes each), any
@@ -828,6 +845,55 @@ def i420_compose(canvas, cw, ch, ncanvas, src, src_w, src_h, nsrc, cells, stream
     if lib().h264mi_i420_compose_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(src.data_ptr()), src_w, src_h,
                                      nsrc, arr, len(arr), ctypes.c_void_p(hs)) != 0:
         raise ValueError(f'bad arguments: {len(arr)} cells of {nsrc} sources {src_w}x{src_h} on {ncanvas} canvases {cw}x{ch}')
+
+
+FILTER_BILINEAR = 0  # H264MI_FILTER_BILINEAR
+FILTER_BICUBIC = 1   # H264MI_FILTER_BICUBIC (Catmull-Rom)
+
+
+def i420_upscale(dst, src, sw, sh, dw, dh, n, filter=FILTER_BICUBIC, stream=None):
+    """n tight sw x sh I420 frames (uint8 CUDA tensor src, any alignment) enlarged to n tight dw x dh frames (dst) with
+    FILTER_BILINEAR or FILTER_BICUBIC, async on stream (default: the current one); h264mi_i420_upscale_dev. Exact
+    integers: the bytes equal tests/upscaleref.py's; equal sizes copy. ValueError on a bad argument (odd sizes, dw < sw,
+    dh < sh, a source above 4096, a destination above 8192, an unknown filter, n <= 0, overlapping buffers)."""
+    import torch
+    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
+    assert dst.is_contiguous() and src.is_contiguous()
+    sfb, dfb = sw * sh + 2 * (sw // 2) * (sh // 2), dw * dh + 2 * (dw // 2) * (dh // 2)
+    assert n <= 0 or min(sw, sh, dw, dh) <= 0 or (dst.numel() >= n * dfb and src.numel() >= n * sfb)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_i420_upscale_dev(ctypes.c_void_p(dst.data_ptr()), dw, dh, ctypes.c_void_p(src.data_ptr()), sw, sh, n, int(filter),
+                                     ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {sw}x{sh} -> {dw}x{dh}, {n} frames, filter {filter}')
+
+
+def speaker_cells(n, speaker, src_w, src_h, cw, ch):
+    """the active-speaker layout of n whole src_w x src_h sources on canvas 0 of cw x ch as a list of Cell
+    (h264mi_speaker_cells; host only): source `speaker` above a strip of the others an eighth of the canvas high, every
+    picture as large as its slot allows at the source's shape, enlarged where the slot is larger, centred. ValueError
+    on a bad argument or a cell below 2 samples."""
+    arr = (Cell * max(int(n), 1))()
+    if lib().h264mi_speaker_cells(arr, len(arr), int(n), int(speaker), int(src_w), int(src_h), int(cw), int(ch)) != n:
+        raise ValueError(f'bad arguments: {n} sources {src_w}x{src_h} on {cw}x{ch}, speaker {speaker}')
+    return list(arr)
+
+
+def i420_compose_any(canvas, cw, ch, ncanvas, src, src_w, src_h, nsrc, cells, filter=FILTER_BICUBIC, stream=None):
+    """i420_compose() with cells that may enlarge (h264mi_i420_compose_any_dev): a cell no larger than its crop gets
+    i420_compose's bytes, a cell at least as large both ways is enlarged with filter as i420_upscale does, taps clamped
+    to the crop. Exact integers: the bytes equal tests/upscaleref.py's. ValueError on whatever i420_compose refuses but
+    a rectangle larger than its crop, on a cell that enlarges one axis and shrinks the other, and on an unknown
+    filter."""
+    import torch
+    assert canvas.is_cuda and src.is_cuda and canvas.dtype == torch.uint8 and src.dtype == torch.uint8
+    assert canvas.is_contiguous() and src.is_contiguous()
+    sfb, cfb = src_w * src_h + 2 * (src_w // 2) * (src_h // 2), cw * ch + 2 * (cw // 2) * (ch // 2)
+    assert min(ncanvas, nsrc, src_w, src_h, cw, ch) <= 0 or (canvas.numel() >= ncanvas * cfb and src.numel() >= nsrc * sfb)
+    arr = _cell_array(cells)
+    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if lib().h264mi_i420_compose_any_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(src.data_ptr()), src_w, src_h,
+                                         nsrc, arr, len(arr), int(filter), ctypes.c_void_p(hs)) != 0:
+        raise ValueError(f'bad arguments: {len(arr)} cells of {nsrc} sources {src_w}x{src_h} on {ncanvas} canvases {cw}x{ch}, filter {filter}')
 
 
 class Overlay(ctypes.Structure):
