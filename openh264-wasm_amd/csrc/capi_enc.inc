@@ -190,10 +190,13 @@ int h264mi_enc_frames_skipped(h264mi_encoder *e, int stream) {
     if (hipMemcpy(&st, e->c->d_st + stream, sizeof(EncState), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return st.skipped;
 }
-// the overlay list in force blended into the input area (DESIGN.md §5.6; overlay.hip); nothing without a list
-static int enc_blend_overlays(EncCtx *c) {
-    if (c->ov.empty()) return 0;
-    return launch_overlay_i420(c->d_src, c->w, c->h, c->ov_sprites, c->ov_w, c->ov_h, c->ov.data(), (int)c->ov.size(), c->stream);
+// the tail of every entry point that codes the input area: the overlay list in force blended into it (DESIGN.md §5.6;
+// overlay.hip; nothing without a list), then the frame step
+static int enc_code_input(EncCtx *c) {
+    if (!c->ov.empty() &&
+        launch_overlay_i420(c->d_src, c->w, c->h, c->ov_sprites, c->ov_w, c->ov_h, c->ov.data(), (int)c->ov.size(), c->stream) != 0)
+        return -1;
+    return enc_frame(c, c->d_src);
 }
 // with an overlay list in force the caller's frames are copied into the input area, blended there and coded from there
 int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
@@ -201,19 +204,18 @@ int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
     EncCtx *c = e->c;
     if (c->ov.empty()) return enc_frame(c, (const uint8_t *)d_frames);
     if (d_frames != (const void *)c->d_src) {
-        const uintptr_t a = (uintptr_t)d_frames, b = (uintptr_t)c->d_src, nb = (uintptr_t)c->S * c->fbytes;
-        if (a < b + nb && b < a + nb) return -1;  // partly inside the input area
+        const size_t nb = (size_t)c->S * c->fbytes;
+        if (byte_ranges_overlap(d_frames, nb, c->d_src, nb)) return -1;  // partly inside the input area
         if (hipMemcpyAsync(c->d_src, d_frames, nb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
     }
-    if (enc_blend_overlays(c) != 0) return -1;
-    return enc_frame(c, c->d_src);
+    return enc_code_input(c);
 }
 int h264mi_enc_set_overlays(h264mi_encoder *e, const void *d_sprites, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov) {
     if (!e) return -1;
     EncCtx *c = e->c;
     if (nov == 0) { c->ov.clear(); c->ov_sprites = nullptr; return 0; }
     if (!d_sprites || !overlay_args_ok(c->w, c->h, c->S, ow, oh, nsprites, ov, nov) ||
-        overlay_ranges_overlap(c->d_src, c->w, c->h, c->S, d_sprites, ow, oh, nsprites))
+        byte_ranges_overlap(c->d_src, c->S * i420_bytes(c->w, c->h), d_sprites, nsprites * i420a_bytes(ow, oh)))
         return -1;
     c->ov.assign(ov, ov + nov);
     c->ov_sprites = (const uint8_t *)d_sprites; c->ov_w = ow; c->ov_h = oh;
@@ -228,7 +230,7 @@ int h264mi_rgba_to_i420a_dev(void *d_dst, const void *d_rgba, int w, int h, int 
 int h264mi_i420_overlay_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_sprites, int ow, int oh, int nsprites,
                             const h264mi_overlay *ov, int nov, void *hip_stream) {
     if (!d_canvas || !d_sprites || !overlay_args_ok(cw, ch, ncanvas, ow, oh, nsprites, ov, nov) ||
-        overlay_ranges_overlap(d_canvas, cw, ch, ncanvas, d_sprites, ow, oh, nsprites))
+        byte_ranges_overlap(d_canvas, ncanvas * i420_bytes(cw, ch), d_sprites, nsprites * i420a_bytes(ow, oh)))
         return -1;
     return launch_overlay_i420((uint8_t *)d_canvas, cw, ch, (const uint8_t *)d_sprites, ow, oh, ov, nov, (hipStream_t)hip_stream);
 }
@@ -238,12 +240,11 @@ int h264mi_enc_encode_rgba(h264mi_encoder *e, const void *d_rgba_frames) {
     if (!e || !d_rgba_frames || ((uintptr_t)d_rgba_frames & 3)) return -1;
     EncCtx *c = e->c;
     if (launch_rgba_to_i420((const uint8_t *)d_rgba_frames, c->w, c->h, c->S, c->d_src, c->stream) != 0) return -1;
-    if (enc_blend_overlays(c) != 0) return -1;
-    return enc_frame(c, c->d_src);
+    return enc_code_input(c);
 }
 // Area-average downscaling (DESIGN.md §5.3; scale.hip): n tight I420 frames of one geometry pair, one launch
 int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, void *hip_stream) {
-    if (!d_dst || !d_src || !scale_args_ok(dw, dh, sw, sh, n) || scale_ranges_overlap(d_dst, dw, dh, d_src, sw, sh, n)) return -1;
+    if (!d_dst || !d_src || !scale_args_ok(dw, dh, sw, sh, n) || i420_ranges_overlap(d_dst, dw, dh, n, d_src, sw, sh, n)) return -1;
     return launch_scale_i420((uint8_t *)d_dst, dw, dh, (const uint8_t *)d_src, sw, sh, n, (hipStream_t)hip_stream);
 }
 // nstreams tight src_w x src_h I420 frames back to back: one batched downscale into the encoder's own input area on
@@ -252,17 +253,17 @@ int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw
 int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w, int src_h) {
     if (!e || !d_frames) return -1;
     EncCtx *c = e->c;
-    if (!scale_args_ok(c->w, c->h, src_w, src_h, c->S) || scale_ranges_overlap(c->d_src, c->w, c->h, d_frames, src_w, src_h, c->S)) return -1;
+    if (!scale_args_ok(c->w, c->h, src_w, src_h, c->S) || i420_ranges_overlap(c->d_src, c->w, c->h, c->S, d_frames, src_w, src_h, c->S))
+        return -1;
     if (launch_scale_i420(c->d_src, c->w, c->h, (const uint8_t *)d_frames, src_w, src_h, c->S, c->stream) != 0) return -1;
-    if (enc_blend_overlays(c) != 0) return -1;
-    return enc_frame(c, c->d_src);
+    return enc_code_input(c);
 }
 // Several pictures into one (DESIGN.md §5.4; compose.hip): every cell's crop of a source frame area-averaged into its
 // rectangle of a canvas, 64 cells to a launch
 int h264mi_i420_compose_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,
                             const h264mi_cell *cells, int ncells, void *hip_stream) {
-    if (!d_canvas || !d_src || !compose_args_ok(cw, ch, ncanvas, src_w, src_h, nsrc, cells, ncells) ||
-        compose_ranges_overlap(d_canvas, cw, ch, ncanvas, d_src, src_w, src_h, nsrc))
+    if (!d_canvas || !d_src || !cells_ok(cw, ch, ncanvas, src_w, src_h, nsrc, cells, ncells, false) ||
+        i420_ranges_overlap(d_canvas, cw, ch, ncanvas, d_src, src_w, src_h, nsrc))
         return -1;
     return launch_compose_i420((uint8_t *)d_canvas, cw, ch, (const uint8_t *)d_src, src_w, src_h, cells, ncells, (hipStream_t)hip_stream);
 }
@@ -274,29 +275,36 @@ int h264mi_mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, 
     return mosaic_cells(out, cap, n, src_w, src_h, cw, ch);
 }
 // the encoder's nstreams input frames as the canvases: an optional fill, the compose launch(es), then the frame step
-// as h264mi_enc_encode runs it, all on the encoder's stream. Every refusal comes before the first launch
-int h264mi_enc_encode_composed(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
-                               int bg_y, int bg_cb, int bg_cr) {
+// as h264mi_enc_encode runs it, all on the encoder's stream. With may_enlarge the cells may enlarge, with filter.
+// Every refusal comes before the first launch
+static int enc_encode_cells(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
+                            bool may_enlarge, int filter, int bg_y, int bg_cb, int bg_cr) {
     if (!e || !d_src) return -1;
     EncCtx *c = e->c;
-    if (!compose_args_ok(c->w, c->h, c->S, src_w, src_h, nsrc, cells, ncells) ||
-        compose_ranges_overlap(c->d_src, c->w, c->h, c->S, d_src, src_w, src_h, nsrc))
+    if ((may_enlarge && !filter_ok(filter)) || !cells_ok(c->w, c->h, c->S, src_w, src_h, nsrc, cells, ncells, may_enlarge) ||
+        i420_ranges_overlap(c->d_src, c->w, c->h, c->S, d_src, src_w, src_h, nsrc))
         return -1;
     if (bg_y > 255 || bg_cb > 255 || bg_cr > 255 || (bg_y >= 0 && !fill_args_ok(c->w, c->h, c->S, bg_y, bg_cb, bg_cr))) return -1;
     if (bg_y >= 0 && launch_fill_i420(c->d_src, c->w, c->h, c->S, bg_y, bg_cb, bg_cr, c->stream) != 0) return -1;
-    if (launch_compose_i420(c->d_src, c->w, c->h, (const uint8_t *)d_src, src_w, src_h, cells, ncells, c->stream) != 0) return -1;
-    if (enc_blend_overlays(c) != 0) return -1;
-    return enc_frame(c, c->d_src);
+    const uint8_t *src = (const uint8_t *)d_src;
+    const int rc = may_enlarge ? launch_compose_any_i420(c->d_src, c->w, c->h, src, src_w, src_h, cells, ncells, filter, c->stream)
+                               : launch_compose_i420(c->d_src, c->w, c->h, src, src_w, src_h, cells, ncells, c->stream);
+    return rc != 0 ? -1 : enc_code_input(c);
+}
+int h264mi_enc_encode_composed(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
+                               int bg_y, int bg_cb, int bg_cr) {
+    return enc_encode_cells(e, d_src, src_w, src_h, nsrc, cells, ncells, false, 0, bg_y, bg_cb, bg_cr);
 }
 // Enlarging (DESIGN.md §5.7; upscale.hip): whole frames, cells of both kinds, the active-speaker layout
 int h264mi_i420_upscale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, int filter, void *hip_stream) {
-    if (!d_dst || !d_src || !upscale_args_ok(dw, dh, sw, sh, n, filter) || upscale_ranges_overlap(d_dst, dw, dh, d_src, sw, sh, n)) return -1;
+    if (!d_dst || !d_src || !upscale_args_ok(dw, dh, sw, sh, n, filter) || i420_ranges_overlap(d_dst, dw, dh, n, d_src, sw, sh, n))
+        return -1;
     return launch_upscale_i420((uint8_t *)d_dst, dw, dh, (const uint8_t *)d_src, sw, sh, n, filter, (hipStream_t)hip_stream);
 }
 int h264mi_i420_compose_any_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,
                                 const h264mi_cell *cells, int ncells, int filter, void *hip_stream) {
-    if (!d_canvas || !d_src || !compose_any_args_ok(cw, ch, ncanvas, src_w, src_h, nsrc, cells, ncells, filter) ||
-        compose_ranges_overlap(d_canvas, cw, ch, ncanvas, d_src, src_w, src_h, nsrc))
+    if (!d_canvas || !d_src || !filter_ok(filter) || !cells_ok(cw, ch, ncanvas, src_w, src_h, nsrc, cells, ncells, true) ||
+        i420_ranges_overlap(d_canvas, cw, ch, ncanvas, d_src, src_w, src_h, nsrc))
         return -1;
     return launch_compose_any_i420((uint8_t *)d_canvas, cw, ch, (const uint8_t *)d_src, src_w, src_h, cells, ncells, filter,
                                    (hipStream_t)hip_stream);
@@ -304,19 +312,10 @@ int h264mi_i420_compose_any_dev(void *d_canvas, int cw, int ch, int ncanvas, con
 int h264mi_speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch) {
     return speaker_cells(out, cap, n, speaker, src_w, src_h, cw, ch);
 }
-// h264mi_enc_encode_composed with cells that may enlarge. Every refusal comes before the first launch
+// h264mi_enc_encode_composed with cells that may enlarge
 int h264mi_enc_encode_composed_any(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
                                    int filter, int bg_y, int bg_cb, int bg_cr) {
-    if (!e || !d_src) return -1;
-    EncCtx *c = e->c;
-    if (!compose_any_args_ok(c->w, c->h, c->S, src_w, src_h, nsrc, cells, ncells, filter) ||
-        compose_ranges_overlap(c->d_src, c->w, c->h, c->S, d_src, src_w, src_h, nsrc))
-        return -1;
-    if (bg_y > 255 || bg_cb > 255 || bg_cr > 255 || (bg_y >= 0 && !fill_args_ok(c->w, c->h, c->S, bg_y, bg_cb, bg_cr))) return -1;
-    if (bg_y >= 0 && launch_fill_i420(c->d_src, c->w, c->h, c->S, bg_y, bg_cb, bg_cr, c->stream) != 0) return -1;
-    if (launch_compose_any_i420(c->d_src, c->w, c->h, (const uint8_t *)d_src, src_w, src_h, cells, ncells, filter, c->stream) != 0) return -1;
-    if (enc_blend_overlays(c) != 0) return -1;
-    return enc_frame(c, c->d_src);
+    return enc_encode_cells(e, d_src, src_w, src_h, nsrc, cells, ncells, true, filter, bg_y, bg_cb, bg_cr);
 }
 const void *h264mi_enc_input_buffer(h264mi_encoder *e) { return e ? e->c->d_src : nullptr; }
 size_t h264mi_enc_frame_bytes(h264mi_encoder *e) { return e ? e->c->fbytes : 0; }

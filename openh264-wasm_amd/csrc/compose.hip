@@ -23,11 +23,13 @@
 //    outside the source frame.
 //
 // A translation unit and a code object of its own, as quality.hip and scale.hip are: the library's other kernels stay
-// byte for byte what they were. The host runtime (capi_enc.inc) reaches it through the functions at the end.
+// byte for byte what they were. The host runtime (capi_enc.inc) reaches it through the functions picture_host.h declares;
+// the checks of a cell list and the cell table of a launch are there too.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
+#include "picture_host.h"
 
 namespace h264mi {
 #define CDEV __device__ __forceinline__
@@ -35,15 +37,8 @@ namespace h264mi {
 #define H264MI_COMPOSE_ROWS 16          // output rows per wave
 #define H264MI_COMPOSE_BATCH 8          // source rows whose loads are in flight together
 #define H264MI_COMPOSE_CELLS 64         // cells per launch: the argument block is 1.9 KB
-#define H264MI_COMPOSE_MAX_CELLS 4096   // cells per call
-#define H264MI_COMPOSE_MAX_BLOCKS 2048  // 8 blocks of 256 on each of 256 CUs; the rest is a stride loop
-#define H264MI_COMPOSE_MAX_SRC 4096     // source side: 255 * 4096^2 + 4096^2 / 2 < 2^32
-#define H264MI_COMPOSE_MAX_CANVAS 8192  // canvas side: a rectangle field fits 16 bits
 
-struct ComposeCell {  // a cell as the kernel reads it, 24 bytes
-    int32_t src, canvas;
-    uint16_t sx, sy, sw, sh, dx, dy, dw, dh;
-};
+typedef PictureCell ComposeCell;  // a cell as the kernel reads it, 24 bytes (picture_host.h)
 struct ComposeLaunch {
     const uint8_t *src;
     uint8_t *dst;
@@ -217,19 +212,16 @@ __global__ __launch_bounds__(256) void fill_kernel(FillLaunch a) {
     }
 }
 
-static size_t i420_bytes(int w, int h) { return (size_t)w * h + 2 * (size_t)(w / 2) * (h / 2); }
-
 // arguments of a fill call
 bool fill_args_ok(int w, int h, int n, int y, int cb, int cr) {
-    return n > 0 && w > 0 && h > 0 && !((w | h) & 1) && w <= H264MI_COMPOSE_MAX_CANVAS && h <= H264MI_COMPOSE_MAX_CANVAS &&
-           y >= 0 && y <= 255 && cb >= 0 && cb <= 255 && cr >= 0 && cr <= 255;
+    return n > 0 && canvas_ok(w, h) && y >= 0 && y <= 255 && cb >= 0 && cb <= 255 && cr >= 0 && cr <= 255;
 }
 int launch_fill_i420(uint8_t *dst, int w, int h, int n, int y, int cb, int cr, hipStream_t s) {
     FillLaunch a{};
     a.dst = dst; a.fb = i420_bytes(w, h); a.yb = (size_t)w * h; a.cb = (size_t)(w / 2) * (h / 2);
     a.v[0] = 0x01010101u * (uint32_t)y; a.v[1] = 0x01010101u * (uint32_t)cb; a.v[2] = 0x01010101u * (uint32_t)cr;
     const size_t blocks = (a.fb / 16 + 2 + 255) / 256;
-    const unsigned gx = (unsigned)std::min(blocks, (size_t)std::max(1, H264MI_COMPOSE_MAX_BLOCKS / n));
+    const unsigned gx = (unsigned)std::min(blocks, (size_t)std::max(1, PIC_MAX_BLOCKS / n));
     (void)hipGetLastError();
     for (int f0 = 0; f0 < n; f0 += 65535) {  // gridDim.y is 16 bits
         FillLaunch b = a;
@@ -239,36 +231,10 @@ int launch_fill_i420(uint8_t *dst, int w, int h, int n, int y, int cb, int cr, h
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// arguments of a compose call, everything but the pointers' values: counts, sizes, every cell's fields, and no two
-// cells of one canvas that share a sample
-bool compose_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells) {
-    if (!cells || ncanvas <= 0 || nsrc <= 0 || ncells <= 0 || ncells > H264MI_COMPOSE_MAX_CELLS) return false;
-    if (((cw | ch | src_w | src_h) & 1) || cw < 2 || ch < 2 || src_w < 2 || src_h < 2) return false;
-    if (src_w > H264MI_COMPOSE_MAX_SRC || src_h > H264MI_COMPOSE_MAX_SRC || cw > H264MI_COMPOSE_MAX_CANVAS || ch > H264MI_COMPOSE_MAX_CANVAS)
-        return false;
-    for (int k = 0; k < ncells; k++) {
-        const h264mi_cell &c = cells[k];
-        if (c.src < 0 || c.src >= nsrc || c.canvas < 0 || c.canvas >= ncanvas) return false;
-        if ((c.sx | c.sy | c.sw | c.sh | c.dx | c.dy | c.dw | c.dh) & 1) return false;
-        if (c.sx < 0 || c.sy < 0 || c.sw < 2 || c.sh < 2 || c.sw > src_w - c.sx || c.sh > src_h - c.sy) return false;  // sx <= src_w: no overflow
-        if (c.sx > src_w || c.sy > src_h) return false;
-        if (c.dw < 2 || c.dw > c.sw || c.dh < 2 || c.dh > c.sh) return false;
-        if (c.dx < 0 || c.dy < 0 || c.dx > cw || c.dy > ch || c.dw > cw - c.dx || c.dh > ch - c.dy) return false;
-    }
-    for (int k = 1; k < ncells; k++)
-        for (int j = 0; j < k; j++) {
-            const h264mi_cell &a = cells[k], &b = cells[j];
-            if (a.canvas == b.canvas && a.dx < b.dx + b.dw && b.dx < a.dx + a.dw && a.dy < b.dy + b.dh && b.dy < a.dy + a.dh) return false;
-        }
-    return true;
+static int compose_cell_waves(int dw, int dh) {
+    return compose_nstrip(dw) * compose_nseg(dh) + 2 * compose_nstrip(dw / 2) * compose_nseg(dh / 2);
 }
-// whether the byte ranges of nsrc source frames at src and ncanvas canvases at canvas share a byte
-bool compose_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *src, int src_w, int src_h, int nsrc) {
-    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)canvas;
-    const uintptr_t sb = (uintptr_t)nsrc * i420_bytes(src_w, src_h), db = (uintptr_t)ncanvas * i420_bytes(cw, ch);
-    return s0 < d0 + db && d0 < s0 + sb;
-}
-// cells (as compose_args_ok accepts them) into the canvases at dst, H264MI_COMPOSE_CELLS to a launch
+// cells (as cells_ok accepts them without enlarging) into the canvases at dst, H264MI_COMPOSE_CELLS to a launch
 int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
                         hipStream_t s) {
     ComposeLaunch a{};
@@ -276,27 +242,15 @@ int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int sr
     a.src_w = src_w; a.src_h = src_h; a.cw = cw; a.ch = ch;
     (void)hipGetLastError();
     for (int k0 = 0; k0 < ncells; k0 += H264MI_COMPOSE_CELLS) {
-        a.ncells = std::min(ncells - k0, H264MI_COMPOSE_CELLS);
-        a.first[0] = 0;
-        for (int k = 0; k < a.ncells; k++) {
-            const h264mi_cell &c = cells[k0 + k];
-            a.cell[k] = ComposeCell{c.src, c.canvas, (uint16_t)c.sx, (uint16_t)c.sy, (uint16_t)c.sw, (uint16_t)c.sh,
-                                    (uint16_t)c.dx, (uint16_t)c.dy, (uint16_t)c.dw, (uint16_t)c.dh};
-            // at most 128 * 512 + 2 * 64 * 256 waves a cell, 64 cells: far below 2^31
-            a.first[k + 1] = a.first[k] + compose_nstrip(c.dw) * compose_nseg(c.dh) + 2 * compose_nstrip(c.dw / 2) * compose_nseg(c.dh / 2);
-        }
-        const int blocks = (a.first[a.ncells] + 3) / 4;
-        hipLaunchKernelGGL(compose_kernel, dim3((unsigned)std::min(blocks, H264MI_COMPOSE_MAX_BLOCKS)), dim3(256), 0, s, a);
+        a.ncells = fill_cell_table(a.cell, a.first, cells + k0, std::min(ncells - k0, H264MI_COMPOSE_CELLS), compose_cell_waves);
+        hipLaunchKernelGGL(compose_kernel, dim3(launch_blocks(a.first[a.ncells])), dim3(256), 0, s, a);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // the gallery layout of include/h264mi.h (h264mi_mosaic_cells): host only, integers, floor divisions
 int mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch) {
-    if (!out || n <= 0 || n > H264MI_COMPOSE_MAX_CELLS || cap < n) return -1;
-    if (((cw | ch | src_w | src_h) & 1) || cw < 2 || ch < 2 || src_w < 2 || src_h < 2) return -1;
-    if (src_w > H264MI_COMPOSE_MAX_SRC || src_h > H264MI_COMPOSE_MAX_SRC || cw > H264MI_COMPOSE_MAX_CANVAS || ch > H264MI_COMPOSE_MAX_CANVAS)
-        return -1;
+    if (!layout_args_ok(out, cap, n, src_w, src_h, cw, ch)) return -1;
     int cols = 1;
     while (cols * cols < n) cols++;
     const int rows = (n + cols - 1) / cols;
@@ -304,10 +258,7 @@ int mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw,
         const int col = k % cols, row = k / cols;
         const int X0 = 2 * (col * cw / (2 * cols)), X1 = 2 * ((col + 1) * cw / (2 * cols));
         const int Y0 = 2 * (row * ch / (2 * rows)), Y1 = 2 * ((row + 1) * ch / (2 * rows));
-        const int dw = std::min(std::min(src_w, X1 - X0), 2 * ((Y1 - Y0) * src_w / (2 * src_h)));
-        const int dh = std::min(std::min(src_h, Y1 - Y0), 2 * (dw * src_h / (2 * src_w)));
-        if (dw < 2 || dh < 2) return -1;
-        out[k] = h264mi_cell{k, 0, 0, 0, src_w, src_h, X0 + 2 * ((X1 - X0 - dw) / 4), Y0 + 2 * ((Y1 - Y0 - dh) / 4), dw, dh};
+        if (!fit_centred(out + k, k, src_w, src_h, X0, X1, Y0, Y1, false)) return -1;
     }
     return n;
 }

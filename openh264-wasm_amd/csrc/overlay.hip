@@ -29,19 +29,18 @@
 // allocation, no copies.
 //
 // A translation unit and a code object of its own, as quality.hip, scale.hip and compose.hip are: the library's other
-// kernels stay byte for byte what they were. The host runtime (capi_enc.inc) reaches it through the functions at the end.
+// kernels stay byte for byte what they were. The host runtime (capi_enc.inc) reaches it through the functions
+// picture_host.h declares.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
+#include "picture_host.h"
 
 namespace h264mi {
 #define ODEV __device__ __forceinline__
 
 #define H264MI_OVERLAY_ROWS 16          // luma rows per wave
-#define H264MI_OVERLAY_MAX 4096         // placements per call
-#define H264MI_OVERLAY_MAX_BLOCKS 2048  // 8 blocks of 256 on each of 256 CUs; the rest is a stride loop
-#define H264MI_OVERLAY_MAX_SIDE 8192    // sprite and canvas side: a geometry field fits 16 bits
 
 struct OverlayItem {  // a placement as the kernel reads it, 24 bytes
     int32_t sprite, canvas;
@@ -205,16 +204,12 @@ __global__ __launch_bounds__(256) void rgba_to_i420a_kernel(const uint8_t *__res
     }
 }
 
-static size_t i420_bytes(int w, int h) { return (size_t)w * h + 2 * (size_t)(w / 2) * (h / 2); }
-static size_t i420a_bytes(int w, int h) { return 2 * (size_t)w * h + 2 * (size_t)(w / 2) * (h / 2); }
-static bool side_ok(int v) { return v >= 2 && v <= H264MI_OVERLAY_MAX_SIDE && !(v & 1); }
-
 // arguments of a conversion to sprites
-bool rgba_to_i420a_args_ok(int w, int h, int n) { return side_ok(w) && side_ok(h) && n > 0; }
+bool rgba_to_i420a_args_ok(int w, int h, int n) { return canvas_ok(w, h) && n > 0; }
 int launch_rgba_to_i420a(const uint8_t *d_rgba, int w, int h, int n, uint8_t *d_out, hipStream_t s) {
     const int ny = std::min(n, 256);
     const long long units = (long long)((w + 3) / 4) * (h / 2);
-    const long long bx = std::max(1LL, std::min((units + 255) / 256, (long long)(H264MI_OVERLAY_MAX_BLOCKS / ny)));
+    const long long bx = std::max(1LL, std::min((units + 255) / 256, (long long)(PIC_MAX_BLOCKS / ny)));
     (void)hipGetLastError();
     hipLaunchKernelGGL(rgba_to_i420a_kernel, dim3((unsigned)bx, (unsigned)ny), dim3(256), 0, s, d_rgba, d_out, w, h, n);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -222,8 +217,8 @@ int launch_rgba_to_i420a(const uint8_t *d_rgba, int w, int h, int n, uint8_t *d_
 
 // arguments of an overlay call, everything but the pointers' values: counts, sizes and every placement's fields
 bool overlay_args_ok(int cw, int ch, int ncanvas, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov) {
-    if (!ov || ncanvas <= 0 || nsprites <= 0 || nov <= 0 || nov > H264MI_OVERLAY_MAX) return false;
-    if (!side_ok(cw) || !side_ok(ch) || !side_ok(ow) || !side_ok(oh)) return false;
+    if (!ov || ncanvas <= 0 || nsprites <= 0 || nov <= 0 || nov > PIC_MAX_LIST) return false;
+    if (!canvas_ok(cw, ch) || !canvas_ok(ow, oh)) return false;
     for (int k = 0; k < nov; k++) {
         const h264mi_overlay &p = ov[k];
         if (p.sprite < 0 || p.sprite >= nsprites || p.canvas < 0 || p.canvas >= ncanvas) return false;
@@ -235,12 +230,6 @@ bool overlay_args_ok(int cw, int ch, int ncanvas, int ow, int oh, int nsprites, 
     }
     return true;
 }
-// whether the byte ranges of nsprites sprites at spr and ncanvas canvases at canvas share a byte
-bool overlay_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *spr, int ow, int oh, int nsprites) {
-    const uintptr_t s0 = (uintptr_t)spr, d0 = (uintptr_t)canvas;
-    const uintptr_t sb = (uintptr_t)nsprites * i420a_bytes(ow, oh), db = (uintptr_t)ncanvas * i420_bytes(cw, ch);
-    return s0 < d0 + db && d0 < s0 + sb;
-}
 // the launch that starts at placement k0 ends before the value returned: the first placement that shares a sample of
 // a canvas with one already in the launch, or H264MI_OVERLAY_PER_LAUNCH placements, or the list's end
 int overlay_launch_end(const h264mi_overlay *ov, int nov, int k0) {
@@ -250,13 +239,15 @@ int overlay_launch_end(const h264mi_overlay *ov, int nov, int k0) {
         bool shared = false;
         for (int j = k0; j < k1 && !shared; j++) {
             const h264mi_overlay &q = ov[j];
-            shared = p.canvas == q.canvas && p.dx < q.dx + q.w && q.dx < p.dx + p.w && p.dy < q.dy + q.h && q.dy < p.dy + p.h;
+            shared = p.canvas == q.canvas && rects_share(p.dx, p.dy, p.w, p.h, q.dx, q.dy, q.w, q.h);
         }
         if (shared) break;
     }
     return k1;
 }
-// placements (as overlay_args_ok accepts them) onto the canvases at dst, launch after launch in list order
+// placements (as overlay_args_ok accepts them) onto the canvases at dst, launch after launch in list order. The table
+// is filled here and not by picture_host.h's fill_cell_table: a placement is another structure than a cell (one size,
+// an opacity) and its launches end where overlay_launch_end says, not after a fixed count
 int launch_overlay_i420(uint8_t *dst, int cw, int ch, const uint8_t *spr, int ow, int oh, const h264mi_overlay *ov, int nov, hipStream_t s) {
     OverlayLaunch a{};
     a.spr = spr; a.dst = dst; a.sfb = i420a_bytes(ow, oh); a.dfb = i420_bytes(cw, ch);
@@ -272,8 +263,7 @@ int launch_overlay_i420(uint8_t *dst, int cw, int ch, const uint8_t *spr, int ow
                                     (uint16_t)p.dx, (uint16_t)p.dy, (uint16_t)p.opacity, 0};
             a.first[k + 1] = a.first[k] + overlay_nstrip(p.w) * overlay_nseg(p.h);  // at most 128 * 512 a placement, 64 of them
         }
-        const int blocks = (a.first[a.n] + 3) / 4;
-        hipLaunchKernelGGL(overlay_kernel, dim3((unsigned)std::min(blocks, H264MI_OVERLAY_MAX_BLOCKS)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(overlay_kernel, dim3(launch_blocks(a.first[a.n])), dim3(256), 0, s, a);
         k0 = k1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;

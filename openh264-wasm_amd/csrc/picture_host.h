@@ -1,0 +1,153 @@
+// picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip)
+// and the runtime (runtime_enc.inc, capi_enc.inc) share: byte counts, the limits of a call, the checks of a cell
+// list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
+// the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
+// and upscale launch structs hold. DESIGN.md §5.8.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <stddef.h>
+#include <stdint.h>
+#include "../../include/h264mi.h"
+
+struct EncDesc;  // h264mi_types.h
+
+namespace h264mi {
+
+// ---- limits of a picture call
+// source side. Area average (scale, compose): the numerator 255 * 4096^2 + 4096^2 / 2 stays below 2^32. Enlarging:
+// the phase numerator 16 N + 33 q stays below 2^31 with q <= PIC_MAX_SIDE
+constexpr int PIC_MAX_SRC = 4096;
+// canvas, destination and sprite side: a geometry field of a device cell or placement fits 16 bits
+constexpr int PIC_MAX_SIDE = 8192;
+// cells or placements per call; H264MI_COMPOSE_CELLS, H264MI_UPSCALE_PER_LAUNCH or H264MI_OVERLAY_PER_LAUNCH of them
+// travel in one launch's arguments
+constexpr int PIC_MAX_LIST = 4096;
+// blocks per launch: 8 blocks of 256 on each of 256 CUs; the rest is a stride loop
+constexpr int PIC_MAX_BLOCKS = 2048;
+
+// ---- bytes
+static inline size_t i420_bytes(int w, int h) { return (size_t)w * h + 2 * (size_t)(w / 2) * (h / 2); }
+static inline size_t i420a_bytes(int w, int h) { return 2 * (size_t)w * h + 2 * (size_t)(w / 2) * (h / 2); }
+// whether abytes bytes at a and bbytes bytes at b share a byte
+static inline bool byte_ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+// the same for na tight aw x ah I420 frames at a and nb tight bw x bh ones at b
+static inline bool i420_ranges_overlap(const void *a, int aw, int ah, int na, const void *b, int bw, int bh, int nb) {
+    return byte_ranges_overlap(a, (size_t)na * i420_bytes(aw, ah), b, (size_t)nb * i420_bytes(bw, bh));
+}
+
+// ---- geometry
+static inline bool side_ok(int v, int max) { return v >= 2 && v <= max && !(v & 1); }
+// a canvas, destination or sprite: even sides from 2 within PIC_MAX_SIDE
+static inline bool canvas_ok(int w, int h) { return side_ok(w, PIC_MAX_SIDE) && side_ok(h, PIC_MAX_SIDE); }
+// a call that takes src_w x src_h pictures to cw x ch ones: the same, and the source within PIC_MAX_SRC
+static inline bool sides_ok(int cw, int ch, int src_w, int src_h) {
+    return canvas_ok(cw, ch) && side_ok(src_w, PIC_MAX_SRC) && side_ok(src_h, PIC_MAX_SRC);
+}
+static inline bool filter_ok(int filter) { return filter == H264MI_FILTER_BILINEAR || filter == H264MI_FILTER_BICUBIC; }
+// whether two rectangles share a sample (touching ones do not)
+static inline bool rects_share(int ax, int ay, int aw, int ah, int bx, int by, int bw, int bh) {
+    return ax < bx + bw && bx < ax + aw && ay < by + bh && by < ay + ah;
+}
+// blocks of four waves for a launch's waves
+static inline unsigned launch_blocks(long long waves) { return (unsigned)std::min((waves + 3) / 4, (long long)PIC_MAX_BLOCKS); }
+
+// ---- cell lists
+// the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
+static inline int cell_kind(const h264mi_cell &c) {
+    if (c.dw <= c.sw && c.dh <= c.sh) return 0;
+    if (c.dw >= c.sw && c.dh >= c.sh) return 1;
+    return -1;
+}
+// arguments of a call that takes a cell list, everything but the pointers' values: counts, sizes, every cell's fields
+// (a rectangle no larger than its crop, or with may_enlarge at least as large both ways, never one way only), and no
+// two cells of one canvas that share a sample. No cell is read before cells and ncells are known to be good
+static inline bool cells_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells, bool may_enlarge) {
+    if (!cells || ncanvas <= 0 || nsrc <= 0 || ncells <= 0 || ncells > PIC_MAX_LIST || !sides_ok(cw, ch, src_w, src_h)) return false;
+    for (int k = 0; k < ncells; k++) {
+        const h264mi_cell &c = cells[k];
+        if (c.src < 0 || c.src >= nsrc || c.canvas < 0 || c.canvas >= ncanvas) return false;
+        if ((c.sx | c.sy | c.sw | c.sh | c.dx | c.dy | c.dw | c.dh) & 1) return false;
+        if (c.sx < 0 || c.sy < 0 || c.sx > src_w || c.sy > src_h) return false;
+        if (c.sw < 2 || c.sh < 2 || c.sw > src_w - c.sx || c.sh > src_h - c.sy) return false;  // sx <= src_w: no overflow
+        if (c.dx < 0 || c.dy < 0 || c.dx > cw || c.dy > ch) return false;
+        if (c.dw < 2 || c.dh < 2 || c.dw > cw - c.dx || c.dh > ch - c.dy) return false;
+        const int kind = cell_kind(c);
+        if (kind < 0 || (kind == 1 && !may_enlarge)) return false;
+    }
+    for (int k = 1; k < ncells; k++)
+        for (int j = 0; j < k; j++) {
+            const h264mi_cell &a = cells[k], &b = cells[j];
+            if (a.canvas == b.canvas && rects_share(a.dx, a.dy, a.dw, a.dh, b.dx, b.dy, b.dw, b.dh)) return false;
+        }
+    return true;
+}
+
+// ---- cell tables
+struct PictureCell {  // a cell as compose_kernel and upscale_kernel read it, 24 bytes
+    int32_t src, canvas;
+    uint16_t sx, sy, sw, sh, dx, dy, dw, dh;
+};
+static_assert(sizeof(PictureCell) == 24, "the launch structs count on it");
+static inline PictureCell picture_cell(const h264mi_cell &c) {
+    return PictureCell{c.src, c.canvas, (uint16_t)c.sx, (uint16_t)c.sy, (uint16_t)c.sw, (uint16_t)c.sh,
+                       (uint16_t)c.dx, (uint16_t)c.dy, (uint16_t)c.dw, (uint16_t)c.dh};
+}
+// a launch's table: cell[k] from cells[k], and the prefix first[] of waves per cell (cell k's waves are first[k] ..
+// first[k + 1] - 1; a cell has at most 128 * 512 + 2 * 64 * 256 waves, a launch 64 cells: far below 2^31). Returns n
+static inline int fill_cell_table(PictureCell *cell, int *first, const h264mi_cell *cells, int n, int (*waves)(int dw, int dh)) {
+    first[0] = 0;
+    for (int k = 0; k < n; k++) {
+        cell[k] = picture_cell(cells[k]);
+        first[k + 1] = first[k] + waves(cells[k].dw, cells[k].dh);
+    }
+    return n;
+}
+
+// ---- layouts
+// cell k of a layout: the largest picture of the whole source's shape in the slot X0..X1 x Y0..Y1 (no larger than the
+// source unless may_enlarge), even sides, centred on even offsets, on canvas 0. false when a side falls below 2
+static inline bool fit_centred(h264mi_cell *out, int k, int src_w, int src_h, int X0, int X1, int Y0, int Y1, bool may_enlarge) {
+    const int cap_w = may_enlarge ? X1 - X0 : std::min(src_w, X1 - X0), cap_h = may_enlarge ? Y1 - Y0 : std::min(src_h, Y1 - Y0);
+    const int dw = std::min(cap_w, 2 * ((Y1 - Y0) * src_w / (2 * src_h)));
+    const int dh = std::min(cap_h, 2 * (dw * src_h / (2 * src_w)));
+    if (dw < 2 || dh < 2) return false;
+    *out = h264mi_cell{k, 0, 0, 0, src_w, src_h, X0 + 2 * ((X1 - X0 - dw) / 4), Y0 + 2 * ((Y1 - Y0 - dh) / 4), dw, dh};
+    return true;
+}
+// arguments of a layout call: room for n cells, and the geometry
+static inline bool layout_args_ok(const h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch) {
+    return out && n > 0 && n <= PIC_MAX_LIST && cap >= n && sides_ok(cw, ch, src_w, src_h);
+}
+
+// ---- what the code objects export to the runtime
+// quality.hip
+int launch_quality_enc(h264mi_quality *d_out, const uint8_t *d_frames, size_t fbytes, int w, int h, int cw, const EncDesc *desc, int S,
+                       hipStream_t s);
+int launch_quality_i420(h264mi_quality *d_out, const uint8_t *a, const uint8_t *b, int w, int h, int n, hipStream_t s);
+bool quality_args_ok(int w, int h, int n);
+// scale.hip
+int launch_scale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, hipStream_t s);
+bool scale_args_ok(int dw, int dh, int sw, int sh, int n);
+// compose.hip
+int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
+                        hipStream_t s);
+int launch_fill_i420(uint8_t *dst, int w, int h, int n, int y, int cb, int cr, hipStream_t s);
+bool fill_args_ok(int w, int h, int n, int y, int cb, int cr);
+int mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch);
+// overlay.hip
+int launch_overlay_i420(uint8_t *dst, int cw, int ch, const uint8_t *spr, int ow, int oh, const h264mi_overlay *ov, int nov, hipStream_t s);
+int launch_rgba_to_i420a(const uint8_t *d_rgba, int w, int h, int n, uint8_t *d_out, hipStream_t s);
+bool overlay_args_ok(int cw, int ch, int ncanvas, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov);
+int overlay_launch_end(const h264mi_overlay *ov, int nov, int k0);
+bool rgba_to_i420a_args_ok(int w, int h, int n);
+// upscale.hip
+int launch_upscale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, int filter, hipStream_t s);
+bool upscale_args_ok(int dw, int dh, int sw, int sh, int n, int filter);
+int launch_compose_any_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
+                            int filter, hipStream_t s);
+int speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch);
+}  // namespace h264mi

@@ -24,12 +24,13 @@
 //
 // A translation unit and a code object of its own: the library's other kernels stay in theirs, byte for byte what
 // they were, and an encoder that never turns the records on runs exactly the device code it ran before. The host
-// runtime (runtime_enc.inc, capi_enc.inc) reaches it through the three functions at the end.
+// runtime (runtime_enc.inc, capi_enc.inc) reaches it through the three functions at the end, which picture_host.h declares.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
 #include "h264mi_types.h"
+#include "picture_host.h"
 
 namespace h264mi {
 #define QDEV __device__ __forceinline__

@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "picture_host.h"  // what quality.hip, scale.hip, compose.hip, overlay.hip and upscale.hip export, and the shared host rules
 
 namespace h264mi {
 
@@ -367,38 +368,6 @@ static EncCtx *enc_create(int w, int h, int bitrate, int S, hipStream_t stream) 
         (void)hipMemset(c->d_prof, 0, 64 * sizeof(uint64_t));  // 0..15 + 32..51 enc_mb_kernel, 16..21 deblocking rows
     return c;
 }
-
-// quality.hip (a translation unit of its own)
-int launch_quality_enc(h264mi_quality *d_out, const uint8_t *d_frames, size_t fbytes, int w, int h, int cw, const EncDesc *desc, int S,
-                       hipStream_t s);
-int launch_quality_i420(h264mi_quality *d_out, const uint8_t *a, const uint8_t *b, int w, int h, int n, hipStream_t s);
-bool quality_args_ok(int w, int h, int n);
-// scale.hip (likewise)
-int launch_scale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, hipStream_t s);
-bool scale_args_ok(int dw, int dh, int sw, int sh, int n);
-bool scale_ranges_overlap(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n);
-// compose.hip (likewise)
-int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
-                        hipStream_t s);
-int launch_fill_i420(uint8_t *dst, int w, int h, int n, int y, int cb, int cr, hipStream_t s);
-bool compose_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells);
-bool compose_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *src, int src_w, int src_h, int nsrc);
-bool fill_args_ok(int w, int h, int n, int y, int cb, int cr);
-int mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, int cw, int ch);
-// overlay.hip (likewise)
-int launch_overlay_i420(uint8_t *dst, int cw, int ch, const uint8_t *spr, int ow, int oh, const h264mi_overlay *ov, int nov, hipStream_t s);
-int launch_rgba_to_i420a(const uint8_t *d_rgba, int w, int h, int n, uint8_t *d_out, hipStream_t s);
-bool overlay_args_ok(int cw, int ch, int ncanvas, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov);
-bool overlay_ranges_overlap(const void *canvas, int cw, int ch, int ncanvas, const void *spr, int ow, int oh, int nsprites);
-bool rgba_to_i420a_args_ok(int w, int h, int n);
-// upscale.hip (likewise)
-int launch_upscale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, int filter, hipStream_t s);
-bool upscale_args_ok(int dw, int dh, int sw, int sh, int n, int filter);
-bool upscale_ranges_overlap(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n);
-int launch_compose_any_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
-                            int filter, hipStream_t s);
-bool compose_any_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells, int filter);
-int speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch);
 
 // One frame step for all S streams. src: S tight I420 frames, contiguous, in device memory.
 static int enc_frame(EncCtx *c, const uint8_t *d_frames) {

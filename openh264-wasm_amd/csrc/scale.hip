@@ -26,19 +26,18 @@
 // of the source plane or the qw x qh area of the destination plane.
 //
 // A translation unit and a code object of its own, as quality.hip is: the library's other kernels stay byte for
-// byte what they were. The host runtime (capi_enc.inc) reaches it through the two functions at the end.
+// byte what they were. The host runtime (capi_enc.inc) reaches it through the functions picture_host.h declares.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
+#include "picture_host.h"
 
 namespace h264mi {
 #define SDEV __device__ __forceinline__
 
 #define H264MI_SCALE_ROWS 16          // output rows per wave
 #define H264MI_SCALE_BATCH 8          // source rows whose loads are in flight together
-#define H264MI_SCALE_MAX_BLOCKS 2048  // 8 blocks of 256 on each of 256 CUs; the rest is a stride loop
-#define H264MI_SCALE_MAX_DIM 4096     // source side: 255 * 4096^2 + 4096^2 / 2 < 2^32
 
 struct ScalePlane { int pw, ph, qw, qh, nstrip, nseg; };  // source, destination samples; waves across / down
 struct ScaleLaunch {
@@ -161,17 +160,7 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleLaunch a) {
 }
 
 // arguments of a scale call: even sizes, 2 <= dw <= sw <= 4096, 2 <= dh <= sh <= 4096
-bool scale_args_ok(int dw, int dh, int sw, int sh, int n) {
-    return n > 0 && !((dw | dh | sw | sh) & 1) && dw >= 2 && dw <= sw && sw <= H264MI_SCALE_MAX_DIM && dh >= 2 && dh <= sh &&
-           sh <= H264MI_SCALE_MAX_DIM;
-}
-// whether the byte ranges of n source frames at src and n destination frames at dst share a byte
-bool scale_ranges_overlap(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n) {
-    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
-    const uintptr_t sb = (uintptr_t)n * ((size_t)sw * sh + 2 * (size_t)(sw / 2) * (sh / 2));
-    const uintptr_t db = (uintptr_t)n * ((size_t)dw * dh + 2 * (size_t)(dw / 2) * (dh / 2));
-    return s0 < d0 + db && d0 < s0 + sb;
-}
+bool scale_args_ok(int dw, int dh, int sw, int sh, int n) { return n > 0 && sides_ok(dw, dh, sw, sh) && dw <= sw && dh <= sh; }
 static ScalePlane scale_plane(int pw, int ph, int qw, int qh) {
     return ScalePlane{pw, ph, qw, qh, (qw + 63) / 64, (qh + H264MI_SCALE_ROWS - 1) / H264MI_SCALE_ROWS};
 }
@@ -186,9 +175,8 @@ int launch_scale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, 
     a.pl[0] = scale_plane(sw, sh, dw, dh);
     a.pl[1] = scale_plane(sw / 2, sh / 2, dw / 2, dh / 2);
     a.nwaves = a.pl[0].nstrip * a.pl[0].nseg + 2 * a.pl[1].nstrip * a.pl[1].nseg;
-    const long long blocks = ((long long)n * a.nwaves + 3) / 4;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(scale_kernel, dim3((unsigned)std::min(blocks, (long long)H264MI_SCALE_MAX_BLOCKS)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(scale_kernel, dim3(launch_blocks((long long)n * a.nwaves)), dim3(256), 0, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace h264mi

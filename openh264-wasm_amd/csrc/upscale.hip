@@ -22,27 +22,22 @@
 //
 // A translation unit and a code object of its own, as quality.hip, scale.hip, compose.hip and overlay.hip are: the
 // library's other kernels stay byte for byte what they were. Shrinking cells of a compose_any call go to compose.hip's
-// launch_compose_i420 as they are. The host runtime (capi_enc.inc) reaches this file through the functions at the end.
+// launch_compose_i420 as they are. The host runtime (capi_enc.inc) reaches this file through the functions
+// picture_host.h declares; the checks of a cell list and the cell table of a launch are there too.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>
 #include <stdint.h>
 #include "../../include/h264mi.h"
+#include "picture_host.h"
 
 namespace h264mi {
 #define CDEV __device__ __forceinline__
 
 #define H264MI_UPSCALE_ROWS 32          // output rows per wave
-#define H264MI_UPSCALE_MAX_CELLS 4096   // cells per call
-#define H264MI_UPSCALE_MAX_BLOCKS 2048  // 8 blocks of 256 on each of 256 CUs; the rest is a stride loop
-#define H264MI_UPSCALE_MAX_SRC 4096     // source side: 16 N + 33 q < 2^31
-#define H264MI_UPSCALE_MAX_DST 8192     // destination side: a rectangle field fits 16 bits
 #define H264MI_UPSCALE_MAX_ITEMS (1 << 30)  // waves' worth of work in one launch
 
-struct UpscaleCell {  // a cell as the kernel reads it, 24 bytes
-    int32_t src, canvas;
-    uint16_t sx, sy, sw, sh, dx, dy, dw, dh;
-};
+typedef PictureCell UpscaleCell;  // a cell as the kernel reads it, 24 bytes (picture_host.h)
 struct UpscaleLaunch {
     const uint8_t *src;
     uint8_t *dst;
@@ -166,117 +161,54 @@ __global__ __launch_bounds__(256) void upscale_kernel(UpscaleLaunch a) {
     }
 }
 
-static size_t up_i420_bytes(int w, int h) { return (size_t)w * h + 2 * (size_t)(w / 2) * (h / 2); }
 static int upscale_cell_waves(int dw, int dh) {  // at most 128 * 256 + 2 * 64 * 128 waves a cell
     return upscale_nstrip(dw) * upscale_nseg(dh) + 2 * upscale_nstrip(dw / 2) * upscale_nseg(dh / 2);
 }
 
 // arguments of a whole-frame upscale call, everything but the pointers' values
 bool upscale_args_ok(int dw, int dh, int sw, int sh, int n, int filter) {
-    if (n <= 0 || ((dw | dh | sw | sh) & 1)) return false;
-    if (filter != H264MI_FILTER_BILINEAR && filter != H264MI_FILTER_BICUBIC) return false;
-    if (sw < 2 || sh < 2 || sw > H264MI_UPSCALE_MAX_SRC || sh > H264MI_UPSCALE_MAX_SRC) return false;
-    return dw >= sw && dh >= sh && dw <= H264MI_UPSCALE_MAX_DST && dh <= H264MI_UPSCALE_MAX_DST;
-}
-// whether the byte ranges of n source frames at src and n destination frames at dst share a byte
-bool upscale_ranges_overlap(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n) {
-    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
-    const uintptr_t sb = (uintptr_t)n * up_i420_bytes(sw, sh), db = (uintptr_t)n * up_i420_bytes(dw, dh);
-    return s0 < d0 + db && d0 < s0 + sb;
+    return n > 0 && filter_ok(filter) && sides_ok(dw, dh, sw, sh) && dw >= sw && dh >= sh;
 }
 // n tight sw x sh I420 frames at src to n tight dw x dh frames at dst; arguments as upscale_args_ok accepts them. One
 // cell, the whole frame, repeated over the frames; as many frames to a launch as keep its wave count below 2^30
 int launch_upscale_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, int filter, hipStream_t s) {
+    const h264mi_cell whole{0, 0, 0, 0, sw, sh, 0, 0, dw, dh};
     UpscaleLaunch a{};
-    a.sfb = up_i420_bytes(sw, sh); a.dfb = up_i420_bytes(dw, dh);
+    a.sfb = i420_bytes(sw, sh); a.dfb = i420_bytes(dw, dh);
     a.src_w = sw; a.src_h = sh; a.cw = dw; a.ch = dh;
-    a.ncells = 1; a.filter = filter;
-    a.cell[0] = UpscaleCell{0, 0, 0, 0, (uint16_t)sw, (uint16_t)sh, 0, 0, (uint16_t)dw, (uint16_t)dh};
-    a.first[0] = 0;
-    a.first[1] = upscale_cell_waves(dw, dh);
+    a.filter = filter;
+    a.ncells = fill_cell_table(a.cell, a.first, &whole, 1, upscale_cell_waves);
     const int chunk = H264MI_UPSCALE_MAX_ITEMS / a.first[1];
     (void)hipGetLastError();
     for (int f0 = 0; f0 < n; f0 += chunk) {
         a.nrep = std::min(n - f0, chunk);
         a.src = src + (size_t)f0 * a.sfb;
         a.dst = dst + (size_t)f0 * a.dfb;
-        const long long blocks = ((long long)a.first[1] * a.nrep + 3) / 4;
-        hipLaunchKernelGGL(upscale_kernel, dim3((unsigned)std::min(blocks, (long long)H264MI_UPSCALE_MAX_BLOCKS)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(upscale_kernel, dim3(launch_blocks((long long)a.first[1] * a.nrep)), dim3(256), 0, s, a);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-
-// the kind of a cell whose fields are otherwise valid: 0 shrinking (equal sizes included), 1 enlarging, -1 mixed
-static int compose_any_kind(const h264mi_cell &c) {
-    if (c.dw <= c.sw && c.dh <= c.sh) return 0;
-    if (c.dw >= c.sw && c.dh >= c.sh) return 1;
-    return -1;
-}
-// arguments of a compose_any call, everything but the pointers' values: compose_args_ok's checks with the size rule
-// replaced (a rectangle may be larger than its crop both ways, never one way only), and no two cells of one canvas,
-// of either kind, that share a sample
-bool compose_any_args_ok(int cw, int ch, int ncanvas, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells, int filter) {
-    if (!cells || ncanvas <= 0 || nsrc <= 0 || ncells <= 0 || ncells > H264MI_UPSCALE_MAX_CELLS) return false;
-    if (filter != H264MI_FILTER_BILINEAR && filter != H264MI_FILTER_BICUBIC) return false;
-    if (((cw | ch | src_w | src_h) & 1) || cw < 2 || ch < 2 || src_w < 2 || src_h < 2) return false;
-    if (src_w > H264MI_UPSCALE_MAX_SRC || src_h > H264MI_UPSCALE_MAX_SRC || cw > H264MI_UPSCALE_MAX_DST || ch > H264MI_UPSCALE_MAX_DST)
-        return false;
-    for (int k = 0; k < ncells; k++) {
-        const h264mi_cell &c = cells[k];
-        if (c.src < 0 || c.src >= nsrc || c.canvas < 0 || c.canvas >= ncanvas) return false;
-        if ((c.sx | c.sy | c.sw | c.sh | c.dx | c.dy | c.dw | c.dh) & 1) return false;
-        if (c.sx < 0 || c.sy < 0 || c.sx > src_w || c.sy > src_h) return false;
-        if (c.sw < 2 || c.sh < 2 || c.sw > src_w - c.sx || c.sh > src_h - c.sy) return false;  // sx <= src_w: no overflow
-        if (c.dx < 0 || c.dy < 0 || c.dx > cw || c.dy > ch) return false;
-        if (c.dw < 2 || c.dh < 2 || c.dw > cw - c.dx || c.dh > ch - c.dy) return false;
-        if (compose_any_kind(c) < 0) return false;
-    }
-    for (int k = 1; k < ncells; k++)
-        for (int j = 0; j < k; j++) {
-            const h264mi_cell &a = cells[k], &b = cells[j];
-            if (a.canvas == b.canvas && a.dx < b.dx + b.dw && b.dx < a.dx + a.dw && a.dy < b.dy + b.dh && b.dy < a.dy + a.dh) return false;
-        }
-    return true;
-}
-// the cells of a call (as compose_any_args_ok accepts them) in list order, the shrinking ones and the enlarging ones
-void compose_any_split(const h264mi_cell *cells, int ncells, std::vector<h264mi_cell> &shrink, std::vector<h264mi_cell> &enlarge) {
-    shrink.clear();
-    enlarge.clear();
-    for (int k = 0; k < ncells; k++) (compose_any_kind(cells[k]) == 0 ? shrink : enlarge).push_back(cells[k]);
-}
-
-// compose.hip
-int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
-                        hipStream_t s);
 
 // enlarging cells into the canvases at dst, H264MI_UPSCALE_PER_LAUNCH to a launch
 static int launch_upscale_cells(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
                                 int filter, hipStream_t s) {
     UpscaleLaunch a{};
-    a.src = src; a.dst = dst; a.sfb = up_i420_bytes(src_w, src_h); a.dfb = up_i420_bytes(cw, ch);
+    a.src = src; a.dst = dst; a.sfb = i420_bytes(src_w, src_h); a.dfb = i420_bytes(cw, ch);
     a.src_w = src_w; a.src_h = src_h; a.cw = cw; a.ch = ch;
     a.nrep = 1; a.filter = filter;
     (void)hipGetLastError();
     for (int k0 = 0; k0 < ncells; k0 += H264MI_UPSCALE_PER_LAUNCH) {
-        a.ncells = std::min(ncells - k0, H264MI_UPSCALE_PER_LAUNCH);
-        a.first[0] = 0;
-        for (int k = 0; k < a.ncells; k++) {
-            const h264mi_cell &c = cells[k0 + k];
-            a.cell[k] = UpscaleCell{c.src, c.canvas, (uint16_t)c.sx, (uint16_t)c.sy, (uint16_t)c.sw, (uint16_t)c.sh,
-                                    (uint16_t)c.dx, (uint16_t)c.dy, (uint16_t)c.dw, (uint16_t)c.dh};
-            a.first[k + 1] = a.first[k] + upscale_cell_waves(c.dw, c.dh);  // 64 cells of at most 49152 waves: far below 2^31
-        }
-        const int blocks = (a.first[a.ncells] + 3) / 4;
-        hipLaunchKernelGGL(upscale_kernel, dim3((unsigned)std::min(blocks, H264MI_UPSCALE_MAX_BLOCKS)), dim3(256), 0, s, a);
+        a.ncells = fill_cell_table(a.cell, a.first, cells + k0, std::min(ncells - k0, H264MI_UPSCALE_PER_LAUNCH), upscale_cell_waves);
+        hipLaunchKernelGGL(upscale_kernel, dim3(launch_blocks(a.first[a.ncells])), dim3(256), 0, s, a);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-// cells of both kinds (as compose_any_args_ok accepts them): the shrinking ones through compose.hip as they are, then
-// the enlarging ones. The cells are disjoint, so the order of the two does not matter
+// cells of both kinds (as cells_ok accepts them with enlarging) in list order: the shrinking ones through compose.hip
+// as they are, then the enlarging ones. The cells are disjoint, so the order of the two does not matter
 int launch_compose_any_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
                             int filter, hipStream_t s) {
     std::vector<h264mi_cell> shrink, enlarge;
-    compose_any_split(cells, ncells, shrink, enlarge);
+    for (int k = 0; k < ncells; k++) (cell_kind(cells[k]) == 0 ? shrink : enlarge).push_back(cells[k]);
     if (!shrink.empty() && launch_compose_i420(dst, cw, ch, src, src_w, src_h, shrink.data(), (int)shrink.size(), s) != 0) return -1;
     if (!enlarge.empty() && launch_upscale_cells(dst, cw, ch, src, src_w, src_h, enlarge.data(), (int)enlarge.size(), filter, s) != 0) return -1;
     return 0;
@@ -284,10 +216,7 @@ int launch_compose_any_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, in
 
 // the active-speaker layout of include/h264mi.h (h264mi_speaker_cells): host only, integers, floor divisions
 int speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch) {
-    if (!out || n <= 0 || n > H264MI_UPSCALE_MAX_CELLS || cap < n || speaker < 0 || speaker >= n) return -1;
-    if (((cw | ch | src_w | src_h) & 1) || cw < 2 || ch < 2 || src_w < 2 || src_h < 2) return -1;
-    if (src_w > H264MI_UPSCALE_MAX_SRC || src_h > H264MI_UPSCALE_MAX_SRC || cw > H264MI_UPSCALE_MAX_DST || ch > H264MI_UPSCALE_MAX_DST)
-        return -1;
+    if (!layout_args_ok(out, cap, n, src_w, src_h, cw, ch) || speaker < 0 || speaker >= n) return -1;
     const int SH = n == 1 ? 0 : 2 * (ch / 8), m = n - 1;
     for (int k = 0, slot = 0; k < n; k++) {
         int X0 = 0, X1 = cw, Y0 = 0, Y1 = ch - SH;
@@ -295,10 +224,7 @@ int speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int 
             X0 = 2 * (slot * cw / (2 * m)); X1 = 2 * ((slot + 1) * cw / (2 * m)); Y0 = ch - SH; Y1 = ch;
             slot++;
         }
-        const int dw = std::min(X1 - X0, 2 * ((Y1 - Y0) * src_w / (2 * src_h)));
-        const int dh = std::min(Y1 - Y0, 2 * (dw * src_h / (2 * src_w)));
-        if (dw < 2 || dh < 2) return -1;
-        out[k] = h264mi_cell{k, 0, 0, 0, src_w, src_h, X0 + 2 * ((X1 - X0 - dw) / 4), Y0 + 2 * ((Y1 - Y0 - dh) / 4), dw, dh};
+        if (!fit_centred(out + k, k, src_w, src_h, X0, X1, Y0, Y1, true)) return -1;
     }
     return n;
 }

@@ -303,17 +303,33 @@ def psnr(sse, samples):
     return lib().h264mi_psnr(int(sse), int(samples))
 
 
+def _i420_bytes(w, h):
+    """bytes of a tight w x h I420 frame"""
+    return w * h + 2 * (w // 2) * (h // 2)
+
+
+def _assert_dev_u8(*tensors):
+    """these are contiguous uint8 device tensors"""
+    import torch
+    assert all(t.is_cuda and t.dtype == torch.uint8 for t in tensors)
+    assert all(t.is_contiguous() for t in tensors)
+
+
+def _hip_stream(stream):
+    """HIP handle of stream, or of the current stream"""
+    import torch
+    return ctypes.c_void_p(stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+
+
 class BatchEncoder:
     """S independent encoder streams of one geometry, frames and NAL units resident in HBM."""
 
     def __init__(self, width, height, bitrate, nstreams, stream=None):
-        import torch
         self.w, self.h, self.S = width, height, nstreams
         self.frame_bytes = width * height * 3 // 2
         self.rgba_frame_bytes = width * height * 4
         self._L = lib()
-        hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        self._e = self._L.h264mi_enc_create(width, height, bitrate, nstreams, ctypes.c_void_p(hs))
+        self._e = self._L.h264mi_enc_create(width, height, bitrate, nstreams, _hip_stream(stream))
         if not self._e:
             raise RuntimeError('h264mi_enc_create failed')
         self._ov_sprites = None  # the sprite tensor of the overlay list in force (set_overlays)
@@ -337,7 +353,7 @@ class BatchEncoder:
         (async): one batched area-average downscale (i420_scale) into the encoder's input area on its stream, then
         the frame step of encode(); the quality records then compare the scaled source with the reconstruction.
         ValueError, with nothing enqueued, for a source smaller than the encoder, an odd size or one above 4096."""
-        assert frames.is_cuda and frames.numel() >= self.S * (src_w * src_h + 2 * (src_w // 2) * (src_h // 2))
+        assert frames.is_cuda and frames.numel() >= self.S * _i420_bytes(src_w, src_h)
         if self._L.h264mi_enc_encode_scaled(self._e, ctypes.c_void_p(frames.data_ptr()), int(src_w), int(src_h)) != 0:
             raise ValueError(f'h264mi_enc_encode_scaled refused {src_w}x{src_h} -> {self.w}x{self.h}')
 
@@ -347,7 +363,7 @@ class BatchEncoder:
         the whole input area, with bg=None none (uncovered samples keep what the input area held); then every cell's
         crop area-averaged into its rectangle (i420_compose), then the frame step of encode(), all on the encoder's
         stream. ValueError, with nothing enqueued, for whatever i420_compose refuses or a background above 255."""
-        assert src.is_cuda and (nsrc <= 0 or min(src_w, src_h) <= 0 or src.numel() >= nsrc * (src_w * src_h + 2 * (src_w // 2) * (src_h // 2)))
+        assert src.is_cuda and (nsrc <= 0 or min(src_w, src_h) <= 0 or src.numel() >= nsrc * _i420_bytes(src_w, src_h))
         arr = _cell_array(cells)
         y, cb, cr = (-1, 0, 0) if bg is None else (int(v) for v in bg)
         if self._L.h264mi_enc_encode_composed(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
@@ -360,7 +376,7 @@ class BatchEncoder:
         FILTER_BICUBIC), taps clamped to the crop; then an overlay list in force and the frame step of encode(), all on
         the encoder's stream (h264mi_enc_encode_composed_any). ValueError, with nothing enqueued, for whatever
         i420_compose_any refuses or a background above 255."""
-        assert src.is_cuda and (nsrc <= 0 or min(src_w, src_h) <= 0 or src.numel() >= nsrc * (src_w * src_h + 2 * (src_w // 2) * (src_h // 2)))
+        assert src.is_cuda and (nsrc <= 0 or min(src_w, src_h) <= 0 or src.numel() >= nsrc * _i420_bytes(src_w, src_h))
         arr = _cell_array(cells)
         y, cb, cr = (-1, 0, 0) if bg is None else (int(v) for v in bg)
         if self._L.h264mi_enc_encode_composed_any(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
@@ -555,11 +571,9 @@ class BatchDecoder:
     def __init__(self, width, height, nstreams, stream=None, max_frames=1, groups=0, parse_streams=3):
         """groups: slot groups of max_frames frames in the decoder's ring (0 = default, up to 16; 2 for a
         caller that waits for every call); parse_streams: HIP streams entropy decoding rotates over"""
-        import torch
         self.w, self.h, self.S, self.B = width, height, nstreams, max_frames
         self._L = lib()
-        hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        self._d = self._L.h264mi_dec_create_ring(width, height, nstreams, max_frames, groups, parse_streams, ctypes.c_void_p(hs))
+        self._d = self._L.h264mi_dec_create_ring(width, height, nstreams, max_frames, groups, parse_streams, _hip_stream(stream))
         if not self._d:
             raise RuntimeError('h264mi_dec_create failed')
         _live.add(self)
@@ -718,9 +732,7 @@ class NalRing:
         return self._L.h264mi_ring_size_dev(self._r, t)
 
     def release(self, t, stream=None):
-        import torch
-        hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        if self._L.h264mi_ring_release(self._r, t, ctypes.c_void_p(hs)) != 0:
+        if self._L.h264mi_ring_release(self._r, t, _hip_stream(stream)) != 0:
             raise RuntimeError('h264mi_ring_release failed')
 
     def stats(self):
@@ -768,12 +780,9 @@ def _hiprt():
 
 
 def _convert_dev(fn, dst, src, dst_bytes, src_bytes, w, h, n, stream):
-    import torch
-    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
-    assert dst.is_contiguous() and src.is_contiguous()
+    _assert_dev_u8(dst, src)
     assert n <= 0 or (dst.numel() >= n * dst_bytes and src.numel() >= n * src_bytes)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    if fn(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, ctypes.c_void_p(hs)) != 0:
+    if fn(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {w}x{h}, {n} frames')
 
 
@@ -793,14 +802,10 @@ def i420_scale(dst, src, sw, sh, dw, dh, n, stream=None):
     frames (dst), one launch, async on stream (default: the current one); h264mi_i420_scale_dev. Exact integers:
     the bytes equal tests/scaleref.py's. ValueError on a bad argument (odd sizes, dw > sw, dh > sh, a source above
     4096, n <= 0, overlapping buffers)."""
-    import torch
-    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
-    assert dst.is_contiguous() and src.is_contiguous()
-    sfb, dfb = sw * sh + 2 * (sw // 2) * (sh // 2), dw * dh + 2 * (dw // 2) * (dh // 2)
-    assert n <= 0 or min(sw, sh, dw, dh) <= 0 or (dst.numel() >= n * dfb and src.numel() >= n * sfb)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _assert_dev_u8(dst, src)
+    assert n <= 0 or min(sw, sh, dw, dh) <= 0 or (dst.numel() >= n * _i420_bytes(dw, dh) and src.numel() >= n * _i420_bytes(sw, sh))
     if lib().h264mi_i420_scale_dev(ctypes.c_void_p(dst.data_ptr()), dw, dh, ctypes.c_void_p(src.data_ptr()), sw, sh, n,
-                                   ctypes.c_void_p(hs)) != 0:
+                                   _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {sw}x{sh} -> {dw}x{dh}, {n} frames')
 
 
@@ -835,15 +840,12 @@ def i420_compose(canvas, cw, ch, ncanvas, src, src_w, src_h, nsrc, cells, stream
     bytes equal tests/composeref.py's. ValueError on a bad argument (odd fields, a crop outside the source, a rectangle
     outside the canvas or larger than its crop, overlapping cells of one canvas, overlapping buffers, more than 4096
     cells)."""
-    import torch
-    assert canvas.is_cuda and src.is_cuda and canvas.dtype == torch.uint8 and src.dtype == torch.uint8
-    assert canvas.is_contiguous() and src.is_contiguous()
-    sfb, cfb = src_w * src_h + 2 * (src_w // 2) * (src_h // 2), cw * ch + 2 * (cw // 2) * (ch // 2)
-    assert min(ncanvas, nsrc, src_w, src_h, cw, ch) <= 0 or (canvas.numel() >= ncanvas * cfb and src.numel() >= nsrc * sfb)
+    _assert_dev_u8(canvas, src)
+    assert min(ncanvas, nsrc, src_w, src_h, cw, ch) <= 0 or (canvas.numel() >= ncanvas * _i420_bytes(cw, ch) and
+                                                             src.numel() >= nsrc * _i420_bytes(src_w, src_h))
     arr = _cell_array(cells)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
     if lib().h264mi_i420_compose_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(src.data_ptr()), src_w, src_h,
-                                     nsrc, arr, len(arr), ctypes.c_void_p(hs)) != 0:
+                                     nsrc, arr, len(arr), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {len(arr)} cells of {nsrc} sources {src_w}x{src_h} on {ncanvas} canvases {cw}x{ch}')
 
 
@@ -856,14 +858,10 @@ def i420_upscale(dst, src, sw, sh, dw, dh, n, filter=FILTER_BICUBIC, stream=None
     FILTER_BILINEAR or FILTER_BICUBIC, async on stream (default: the current one); h264mi_i420_upscale_dev. Exact
     integers: the bytes equal tests/upscaleref.py's; equal sizes copy. ValueError on a bad argument (odd sizes, dw < sw,
     dh < sh, a source above 4096, a destination above 8192, an unknown filter, n <= 0, overlapping buffers)."""
-    import torch
-    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
-    assert dst.is_contiguous() and src.is_contiguous()
-    sfb, dfb = sw * sh + 2 * (sw // 2) * (sh // 2), dw * dh + 2 * (dw // 2) * (dh // 2)
-    assert n <= 0 or min(sw, sh, dw, dh) <= 0 or (dst.numel() >= n * dfb and src.numel() >= n * sfb)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _assert_dev_u8(dst, src)
+    assert n <= 0 or min(sw, sh, dw, dh) <= 0 or (dst.numel() >= n * _i420_bytes(dw, dh) and src.numel() >= n * _i420_bytes(sw, sh))
     if lib().h264mi_i420_upscale_dev(ctypes.c_void_p(dst.data_ptr()), dw, dh, ctypes.c_void_p(src.data_ptr()), sw, sh, n, int(filter),
-                                     ctypes.c_void_p(hs)) != 0:
+                                     _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {sw}x{sh} -> {dw}x{dh}, {n} frames, filter {filter}')
 
 
@@ -884,15 +882,12 @@ def i420_compose_any(canvas, cw, ch, ncanvas, src, src_w, src_h, nsrc, cells, fi
     to the crop. Exact integers: the bytes equal tests/upscaleref.py's. ValueError on whatever i420_compose refuses but
     a rectangle larger than its crop, on a cell that enlarges one axis and shrinks the other, and on an unknown
     filter."""
-    import torch
-    assert canvas.is_cuda and src.is_cuda and canvas.dtype == torch.uint8 and src.dtype == torch.uint8
-    assert canvas.is_contiguous() and src.is_contiguous()
-    sfb, cfb = src_w * src_h + 2 * (src_w // 2) * (src_h // 2), cw * ch + 2 * (cw // 2) * (ch // 2)
-    assert min(ncanvas, nsrc, src_w, src_h, cw, ch) <= 0 or (canvas.numel() >= ncanvas * cfb and src.numel() >= nsrc * sfb)
+    _assert_dev_u8(canvas, src)
+    assert min(ncanvas, nsrc, src_w, src_h, cw, ch) <= 0 or (canvas.numel() >= ncanvas * _i420_bytes(cw, ch) and
+                                                             src.numel() >= nsrc * _i420_bytes(src_w, src_h))
     arr = _cell_array(cells)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
     if lib().h264mi_i420_compose_any_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(src.data_ptr()), src_w, src_h,
-                                         nsrc, arr, len(arr), int(filter), ctypes.c_void_p(hs)) != 0:
+                                         nsrc, arr, len(arr), int(filter), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {len(arr)} cells of {nsrc} sources {src_w}x{src_h} on {ncanvas} canvases {cw}x{ch}, filter {filter}')
 
 
@@ -919,12 +914,9 @@ def rgba_to_i420a(dst, src, w, h, n, stream=None):
     """n tight RGBA8 frames (uint8 CUDA tensor src, 4-byte aligned) to n I420A sprites (dst, any alignment), one launch,
     async on stream (default: the current one); h264mi_rgba_to_i420a_dev. Y, Cb, Cr as rgba_to_i420, A the fourth byte.
     ValueError on a bad argument (an odd side or one outside 2..8192, n <= 0, a misaligned source)."""
-    import torch
-    assert dst.is_cuda and src.is_cuda and dst.dtype == torch.uint8 and src.dtype == torch.uint8
-    assert dst.is_contiguous() and src.is_contiguous()
+    _assert_dev_u8(dst, src)
     assert n <= 0 or min(w, h) <= 0 or (dst.numel() >= n * i420a_bytes(w, h) and src.numel() >= n * w * h * 4)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    if lib().h264mi_rgba_to_i420a_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, ctypes.c_void_p(hs)) != 0:
+    if lib().h264mi_rgba_to_i420a_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {w}x{h}, {n} frames')
 
 
@@ -935,26 +927,21 @@ def i420_overlay(canvas, cw, ch, ncanvas, sprites, ow, oh, nsprites, overlays, s
     rectangles keep their value. Exact integers: the bytes equal tests/overlayref.py's. ValueError on a bad argument
     (odd fields, a crop outside the sprite, a rectangle outside the canvas, opacity outside 0..256, reserved != 0,
     overlapping buffers, no placement or more than 4096)."""
-    import torch
-    assert canvas.is_cuda and sprites.is_cuda and canvas.dtype == torch.uint8 and sprites.dtype == torch.uint8
-    assert canvas.is_contiguous() and sprites.is_contiguous()
-    cfb = cw * ch + 2 * (cw // 2) * (ch // 2)
-    assert min(ncanvas, nsprites, ow, oh, cw, ch) <= 0 or (canvas.numel() >= ncanvas * cfb and sprites.numel() >= nsprites * i420a_bytes(ow, oh))
+    _assert_dev_u8(canvas, sprites)
+    assert min(ncanvas, nsprites, ow, oh, cw, ch) <= 0 or (canvas.numel() >= ncanvas * _i420_bytes(cw, ch) and
+                                                           sprites.numel() >= nsprites * i420a_bytes(ow, oh))
     arr = _overlay_array(overlays)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
     if lib().h264mi_i420_overlay_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(sprites.data_ptr()), ow, oh,
-                                     nsprites, arr, len(arr), ctypes.c_void_p(hs)) != 0:
+                                     nsprites, arr, len(arr), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {len(arr)} placements of {nsprites} sprites {ow}x{oh} on {ncanvas} canvases {cw}x{ch}')
 
 
 def i420_fill(frames, w, h, n, y, cb, cr, stream=None):
     """n tight w x h I420 frames (uint8 CUDA tensor, any alignment) set to the colour (y, cb, cr), async on stream
     (default: the current one); h264mi_i420_fill_dev. ValueError on a bad argument."""
-    import torch
-    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()
-    assert n <= 0 or min(w, h) <= 0 or frames.numel() >= n * (w * h + 2 * (w // 2) * (h // 2))
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    if lib().h264mi_i420_fill_dev(ctypes.c_void_p(frames.data_ptr()), w, h, n, int(y), int(cb), int(cr), ctypes.c_void_p(hs)) != 0:
+    _assert_dev_u8(frames)
+    assert n <= 0 or min(w, h) <= 0 or frames.numel() >= n * _i420_bytes(w, h)
+    if lib().h264mi_i420_fill_dev(ctypes.c_void_p(frames.data_ptr()), w, h, n, int(y), int(cb), int(cr), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, colour ({y}, {cb}, {cr})')
 
 
@@ -962,14 +949,12 @@ def i420_quality(out, a, b, w, h, n, stream=None):
     """distortion records of n pairs of tight I420 frames (uint8 CUDA tensors a, b, any alignment) into out (a CUDA
     tensor of at least 64 * n bytes, 8-byte aligned: n h264mi_quality records), one launch, async on stream
     (default: the current one); h264mi_i420_quality_dev. Read them with quality_records()."""
-    import torch
-    assert out.is_cuda and a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8
-    assert out.is_contiguous() and a.is_contiguous() and b.is_contiguous()
-    fb = w * h + 2 * (w // 2) * (h // 2)
+    assert out.is_cuda and out.is_contiguous()
+    _assert_dev_u8(a, b)
+    fb = _i420_bytes(w, h)
     assert n <= 0 or (out.numel() * out.element_size() >= 64 * n and a.numel() >= n * fb and b.numel() >= n * fb)
-    hs = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
     if lib().h264mi_i420_quality_dev(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-                                     w, h, n, ctypes.c_void_p(hs)) != 0:
+                                     w, h, n, _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {w}x{h}, {n} pairs')
 
 

@@ -1,0 +1,266 @@
+// picture_host_san.hip -- the host rules of the picture calls (csrc/picture_host.h and the host halves of scale.hip,
+// compose.hip, overlay.hip, upscale.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
+// is loaded into Python, no kernel is launched, no device is needed.
+//
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
+//         -Xarch_host -fno-sanitize-recover=all tools/picture_host_san.hip openh264-wasm_amd/csrc/scale.hip \
+//         openh264-wasm_amd/csrc/compose.hip openh264-wasm_amd/csrc/overlay.hip openh264-wasm_amd/csrc/upscale.hip \
+//         -o picture_host_san && ./picture_host_san
+//
+// It runs, with every table in a heap block of exactly the size the call may touch:
+//   * cells_ok (both values of may_enlarge) on valid lists and on every field of a cell made odd, negative, one past the
+//     source or canvas, running over the edge, and larger than the crop on one axis and on both; on two cells touching,
+//     sharing one sample, and on different canvases; on null and out-of-range counts -- each verdict against a
+//     restatement in 64-bit arithmetic;
+//   * fill_cell_table and the 64-to-a-launch split on lists of 1, 64, 65 and 4096 cells, cell_kind's split of a mixed
+//     list, and overlay_launch_end on disjoint and on stacked placements of the same lengths;
+//   * mosaic_cells and speaker_cells for 1, 64, 65 and 4096 sources and the sizes of tests/test_compose_host.py, their
+//     cells checked by cells_ok, and their refusals;
+//   * the scalar checks (scale, upscale, fill, overlay, sprite conversion) at their limits, the byte counts and the
+//     range test.
+// Prints one line per group and "ok"; exits 1 at the first difference.
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <vector>
+#include "../openh264-wasm_amd/csrc/picture_host.h"
+
+using namespace h264mi;
+
+static int failures = 0;
+#define CHECK(x)                                                         \
+    do {                                                                 \
+        if (!(x)) {                                                      \
+            printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x);        \
+            failures++;                                                  \
+        }                                                                \
+    } while (0)
+
+// a list in a heap block of exactly n cells, so that a read past the end is the sanitizer's to see
+static std::unique_ptr<h264mi_cell[]> heap(const std::vector<h264mi_cell> &v) {
+    std::unique_ptr<h264mi_cell[]> p(new h264mi_cell[v.size()]);
+    for (size_t k = 0; k < v.size(); k++) p[k] = v[k];
+    return p;
+}
+
+// the rules of include/h264mi.h restated: 64-bit, one predicate per rule
+static bool ref_ok(long long cw, long long ch, long long ncanvas, long long sw, long long sh, long long nsrc, const std::vector<h264mi_cell> &cells,
+                   bool may_enlarge) {
+    auto even_in = [](long long v, long long lo, long long hi) { return v % 2 == 0 && v >= lo && v <= hi; };
+    if (ncanvas < 1 || nsrc < 1 || cells.empty() || cells.size() > 4096) return false;
+    if (!even_in(cw, 2, 8192) || !even_in(ch, 2, 8192) || !even_in(sw, 2, 4096) || !even_in(sh, 2, 4096)) return false;
+    for (const h264mi_cell &c : cells) {
+        if (c.src < 0 || c.src >= nsrc || c.canvas < 0 || c.canvas >= ncanvas) return false;
+        if (!even_in(c.sx, 0, sw) || !even_in(c.sy, 0, sh) || !even_in(c.sw, 2, sw) || !even_in(c.sh, 2, sh)) return false;
+        if ((long long)c.sx + c.sw > sw || (long long)c.sy + c.sh > sh) return false;
+        if (!even_in(c.dx, 0, cw) || !even_in(c.dy, 0, ch) || !even_in(c.dw, 2, cw) || !even_in(c.dh, 2, ch)) return false;
+        if ((long long)c.dx + c.dw > cw || (long long)c.dy + c.dh > ch) return false;
+        const bool wider = c.dw > c.sw, taller = c.dh > c.sh, narrower = c.dw < c.sw, shorter = c.dh < c.sh;
+        if ((wider && shorter) || (narrower && taller)) return false;
+        if ((wider || taller) && !may_enlarge) return false;
+    }
+    for (size_t i = 0; i < cells.size(); i++)
+        for (size_t j = i + 1; j < cells.size(); j++) {
+            const h264mi_cell &a = cells[i], &b = cells[j];
+            const long long x0 = std::max(a.dx, b.dx), x1 = std::min((long long)a.dx + a.dw, (long long)b.dx + b.dw);
+            const long long y0 = std::max(a.dy, b.dy), y1 = std::min((long long)a.dy + a.dh, (long long)b.dy + b.dh);
+            if (a.canvas == b.canvas && x0 < x1 && y0 < y1) return false;
+        }
+    return true;
+}
+
+static void verdicts(int cw, int ch, int ncanvas, int sw, int sh, int nsrc, const std::vector<h264mi_cell> &cells, int *refused) {
+    const auto p = heap(cells);
+    for (int e = 0; e < 2; e++) {
+        const bool got = cells_ok(cw, ch, ncanvas, sw, sh, nsrc, p.get(), (int)cells.size(), e != 0);
+        CHECK(got == ref_ok(cw, ch, ncanvas, sw, sh, nsrc, cells, e != 0));
+        if (!got) refused[e]++;
+    }
+}
+
+static int *field(h264mi_cell &c, int f) {
+    int *p[10] = {&c.src, &c.canvas, &c.sx, &c.sy, &c.sw, &c.sh, &c.dx, &c.dy, &c.dw, &c.dh};
+    return p[f];
+}
+
+static void check_cells() {
+    // the valid lists of tests/test_compose_host.py and tests/test_upscale_host.py, and one with room on every side
+    struct Base { int cw, ch, ncanvas, sw, sh, nsrc; std::vector<h264mi_cell> cells; };
+    const std::vector<Base> bases = {
+        {32, 32, 1, 32, 32, 1, {{0, 0, 0, 0, 32, 32, 0, 0, 16, 16}}},
+        {64, 64, 1, 32, 32, 1, {{0, 0, 0, 0, 16, 16, 0, 0, 32, 32}, {0, 0, 0, 0, 32, 32, 32, 32, 16, 16}}},
+        {64, 64, 2, 32, 32, 2, {{1, 1, 4, 4, 16, 16, 8, 8, 16, 16}, {0, 0, 2, 2, 8, 8, 4, 4, 16, 16}}},
+    };
+    int refused[2] = {0, 0}, cases = 0;
+    for (const Base &b : bases) {
+        verdicts(b.cw, b.ch, b.ncanvas, b.sw, b.sh, b.nsrc, b.cells, refused);
+        for (size_t k = 0; k < b.cells.size(); k++)
+            for (int f = 0; f < 10; f++) {
+                const h264mi_cell &c0 = b.cells[k];
+                const int lim[10] = {b.nsrc, b.ncanvas, b.sw, b.sh, b.sw, b.sh, b.cw, b.ch, b.cw, b.ch};
+                const int over[10] = {0, 0, b.sw - c0.sw + 2, b.sh - c0.sh + 2, b.sw - c0.sx + 2, b.sh - c0.sy + 2,
+                                      b.cw - c0.dw + 2, b.ch - c0.dh + 2, b.cw - c0.dx + 2, b.ch - c0.dy + 2};
+                const int values[] = {*field(const_cast<h264mi_cell &>(c0), f) + 1, -2, -1, lim[f], lim[f] + 2, over[f], 2147483646, 0};
+                for (int v : values) {
+                    Base m = b;
+                    *field(m.cells[k], f) = v;
+                    verdicts(m.cw, m.ch, m.ncanvas, m.sw, m.sh, m.nsrc, m.cells, refused);
+                    cases++;
+                }
+            }
+        // a rectangle larger than its crop on one axis, then on both
+        Base m = b;
+        m.cells[0] = {0, 0, 0, 0, 8, 8, m.cells[0].dx, m.cells[0].dy, 10, 8};
+        verdicts(m.cw, m.ch, m.ncanvas, m.sw, m.sh, m.nsrc, m.cells, refused);
+        m.cells[0].dw = 8; m.cells[0].dh = 10;
+        verdicts(m.cw, m.ch, m.ncanvas, m.sw, m.sh, m.nsrc, m.cells, refused);
+        m.cells[0].dw = 10;
+        verdicts(m.cw, m.ch, m.ncanvas, m.sw, m.sh, m.nsrc, m.cells, refused);
+        cases += 3;
+    }
+    // two cells of one canvas touching, sharing one sample (a 2 x 2 corner: fields are even), on different canvases
+    const h264mi_cell a{0, 0, 0, 0, 16, 16, 0, 0, 16, 16};
+    for (int dx : {16, 14, 0})
+        for (int dy : {16, 14, 0})
+            for (int canvas : {0, 1}) {
+                verdicts(64, 64, 2, 32, 32, 1, {a, {0, canvas, 0, 0, 16, 16, dx, dy, 16, 16}}, refused);
+                verdicts(64, 64, 2, 32, 32, 1, {{0, canvas, 0, 0, 16, 16, dx, dy, 16, 16}, a}, refused);
+                cases += 2;
+            }
+    const auto one = heap({a});
+    CHECK(!cells_ok(64, 64, 1, 32, 32, 1, nullptr, 1, true) && !cells_ok(64, 64, 1, 32, 32, 1, one.get(), 0, true));
+    CHECK(!cells_ok(64, 64, 1, 32, 32, 1, one.get(), -1, true) && !cells_ok(64, 64, 1, 32, 32, 1, one.get(), 4097, false));
+    CHECK(!cells_ok(64, 64, 0, 32, 32, 1, one.get(), 1, true) && !cells_ok(64, 64, 1, 32, 32, -1, one.get(), 1, true));
+    for (int bad : {0, -2, 31, 8194})
+        CHECK(!cells_ok(bad, 64, 1, 32, 32, 1, one.get(), 1, true) && !cells_ok(64, bad, 1, 32, 32, 1, one.get(), 1, true));
+    for (int bad : {0, -2, 31, 4098})
+        CHECK(!cells_ok(64, 64, 1, bad, 32, 1, one.get(), 1, true) && !cells_ok(64, 64, 1, 32, bad, 1, one.get(), 1, true));
+    CHECK(refused[0] > refused[1] && refused[1] > 0);  // the two rules differ, and both refuse
+    printf("cells_ok: %d lists, refused %d without enlarging, %d with\n", cases, refused[0], refused[1]);
+}
+
+static int waves_a(int dw, int dh) { return ((dw + 63) / 64) * ((dh + 15) / 16) + 2 * ((dw / 2 + 63) / 64) * ((dh / 2 + 15) / 16); }
+
+// n disjoint cells on one 256 x 512 canvas: 4 x 4 rectangles from 2 x 2 crops (enlarging) or 4 x 4 crops (not)
+static std::vector<h264mi_cell> grid(int n, bool enlarge) {
+    std::vector<h264mi_cell> v;
+    for (int k = 0; k < n; k++) v.push_back({k % 3, 0, 2 * (k % 5), 2 * (k % 7), enlarge ? 2 : 4, enlarge ? 2 : 4, 4 * (k % 64), 4 * (k / 64), 4, 4});
+    return v;
+}
+
+static void check_tables() {
+    for (int n : {1, 64, 65, 4096}) {
+        const std::vector<h264mi_cell> v = grid(n, false);
+        const auto cells = heap(v);
+        CHECK(cells_ok(256, 512, 1, 32, 32, 3, cells.get(), n, false) && ref_ok(256, 512, 1, 32, 32, 3, v, false));
+        int launches = 0, seen = 0;
+        for (int k0 = 0; k0 < n; k0 += 64) {  // the split of launch_compose_i420 and launch_upscale_cells
+            const int m = std::min(n - k0, 64);
+            std::unique_ptr<PictureCell[]> cell(new PictureCell[m]);
+            std::unique_ptr<int[]> first(new int[m + 1]);
+            CHECK(fill_cell_table(cell.get(), first.get(), cells.get() + k0, m, waves_a) == m);
+            int sum = 0;
+            for (int k = 0; k < m; k++) {
+                const h264mi_cell &c = v[k0 + k];
+                CHECK(first[k] == sum);
+                sum += waves_a(c.dw, c.dh);
+                CHECK(cell[k].src == c.src && cell[k].canvas == c.canvas && cell[k].sx == c.sx && cell[k].sy == c.sy && cell[k].sw == c.sw &&
+                      cell[k].sh == c.sh && cell[k].dx == c.dx && cell[k].dy == c.dy && cell[k].dw == c.dw && cell[k].dh == c.dh);
+            }
+            CHECK(first[m] == sum && launch_blocks(sum) == (unsigned)std::min((sum + 3) / 4, 2048));
+            launches++;
+            seen += m;
+        }
+        CHECK(launches == (n + 63) / 64 && seen == n);
+        // a list of both kinds, as launch_compose_any_i420 splits it
+        std::vector<h264mi_cell> mixed = grid(n, false), up = grid(n, true);
+        int kinds[2] = {0, 0};
+        for (int k = 0; k < n; k += 2) mixed[k] = up[k];
+        const auto mp = heap(mixed);
+        CHECK(cells_ok(256, 512, 1, 32, 32, 3, mp.get(), n, true) && cells_ok(256, 512, 1, 32, 32, 3, mp.get(), n, false) == false);
+        for (int k = 0; k < n; k++) kinds[cell_kind(mp[k])]++;
+        CHECK(kinds[1] == (n + 1) / 2 && kinds[0] == n / 2);
+        // placements: disjoint ones end a launch every 64, a stack of the same rectangle after every one
+        std::unique_ptr<h264mi_overlay[]> ov(new h264mi_overlay[n]);
+        for (int k = 0; k < n; k++) ov[k] = h264mi_overlay{0, 0, 0, 0, 4, 4, 4 * (k % 64), 4 * (k / 64), 256, 0};
+        CHECK(overlay_args_ok(256, 512, 1, 8, 8, 1, ov.get(), n));
+        int ends = 0;
+        for (int k0 = 0; k0 < n; ends++) {
+            const int k1 = overlay_launch_end(ov.get(), n, k0);
+            CHECK(k1 == std::min(k0 + 64, n));
+            k0 = k1;
+        }
+        CHECK(ends == (n + 63) / 64);
+        for (int k = 0; k < n; k++) { ov[k].dx = 8; ov[k].dy = 8; ov[k].canvas = k & 1; }  // two canvases: pairs are disjoint
+        for (int k0 = 0; k0 < n;) {
+            const int k1 = overlay_launch_end(ov.get(), n, k0);
+            CHECK(k1 == std::min(k0 + 2, n));
+            k0 = k1;
+        }
+    }
+    printf("tables and launch splits: lists of 1, 64, 65, 4096\n");
+}
+
+static void check_layouts() {
+    const int sizes[][4] = {{1920, 1080, 1920, 1080}, {64, 36, 48, 48}, {176, 144, 352, 288}, {4096, 2160, 640, 360}, {32, 32, 32, 32},
+                            {1280, 720, 854, 480}, {16, 16, 160, 112}, {36, 18, 50, 22}, {2, 2, 8192, 8192}, {4096, 4096, 8192, 8192}};
+    int made = 0, refused = 0;
+    for (const auto &s : sizes)
+        for (int n : {1, 2, 3, 9, 17, 64, 65, 4096}) {
+            std::unique_ptr<h264mi_cell[]> out(new h264mi_cell[n]);
+            const int r = mosaic_cells(out.get(), n, n, s[0], s[1], s[2], s[3]);
+            CHECK(r == n || r == -1);
+            if (r == n) CHECK(cells_ok(s[2], s[3], 1, s[0], s[1], n, out.get(), n, false));
+            r == n ? made++ : refused++;
+            for (int speaker : {0, n / 2, n - 1}) {
+                const int q = speaker_cells(out.get(), n, n, speaker, s[0], s[1], s[2], s[3]);
+                CHECK(q == n || q == -1);
+                if (q == n) CHECK(cells_ok(s[2], s[3], 1, s[0], s[1], n, out.get(), n, true));
+                q == n ? made++ : refused++;
+            }
+            CHECK(mosaic_cells(out.get(), n - 1, n, s[0], s[1], s[2], s[3]) == -1 && speaker_cells(out.get(), n - 1, n, 0, s[0], s[1], s[2], s[3]) == -1);
+            CHECK(speaker_cells(out.get(), n, n, n, s[0], s[1], s[2], s[3]) == -1 && speaker_cells(out.get(), n, n, -1, s[0], s[1], s[2], s[3]) == -1);
+        }
+    std::unique_ptr<h264mi_cell[]> out(new h264mi_cell[1]);
+    CHECK(mosaic_cells(nullptr, 1, 1, 64, 36, 48, 48) == -1 && mosaic_cells(out.get(), 4097, 4097, 64, 36, 48, 48) == -1);
+    CHECK(mosaic_cells(out.get(), 1, 0, 64, 36, 48, 48) == -1 && speaker_cells(nullptr, 1, 1, 0, 64, 36, 48, 48) == -1);
+    CHECK(speaker_cells(out.get(), 4097, 4097, 0, 64, 36, 48, 48) == -1 && mosaic_cells(out.get(), 1, 1, 63, 36, 48, 48) == -1);
+    CHECK(made > 0 && refused > 0);
+    printf("mosaic_cells, speaker_cells: %d layouts made and checked, %d refused\n", made, refused);
+}
+
+static void check_scalars() {
+    CHECK(i420_bytes(32, 32) == 1536 && i420_bytes(6, 4) == 36 && i420a_bytes(32, 32) == 2560 && i420_bytes(8192, 8192) == 100663296u);
+    char *base = (char *)0x10000000;
+    for (int off : {0, 1, 1535, -1, -1535}) CHECK(i420_ranges_overlap(base + off, 32, 32, 1, base, 32, 32, 1));
+    CHECK(!i420_ranges_overlap(base + 1536, 32, 32, 1, base, 32, 32, 1) && !i420_ranges_overlap(base - 1536, 32, 32, 1, base, 32, 32, 1));
+    CHECK(i420_ranges_overlap(base + 3 * 1536 - 1, 32, 32, 1, base, 32, 32, 3) && !i420_ranges_overlap(base + 3 * 1536, 32, 32, 1, base, 32, 32, 3));
+    CHECK(byte_ranges_overlap(base, 1, base, 1) && !byte_ranges_overlap(base, 1, base + 1, 1) && !byte_ranges_overlap(base, 0, base, 0));
+    CHECK(rects_share(0, 0, 2, 2, 0, 0, 2, 2) && !rects_share(0, 0, 2, 2, 2, 0, 2, 2) && !rects_share(0, 0, 2, 2, 0, 2, 2, 2));
+    CHECK(scale_args_ok(2, 2, 4096, 4096, 1) && !scale_args_ok(2, 2, 4098, 4096, 1) && !scale_args_ok(34, 32, 32, 32, 1) && !scale_args_ok(0, 2, 32, 32, 1));
+    CHECK(!scale_args_ok(16, 16, 32, 32, 0) && !scale_args_ok(15, 16, 32, 32, 1) && scale_args_ok(32, 32, 32, 32, 2147483647));
+    CHECK(upscale_args_ok(8192, 8192, 4096, 4096, 1, 0) && !upscale_args_ok(8194, 8192, 4096, 4096, 1, 0) && !upscale_args_ok(30, 32, 32, 32, 1, 1));
+    CHECK(!upscale_args_ok(64, 64, 32, 32, 1, 2) && !upscale_args_ok(64, 64, 32, 32, 0, 1) && !upscale_args_ok(8192, 8192, 4098, 32, 1, 1));
+    CHECK(fill_args_ok(8192, 2, 1, 0, 255, 0) && !fill_args_ok(8194, 2, 1, 0, 0, 0) && !fill_args_ok(0, 2, 1, 0, 0, 0) && !fill_args_ok(2, 2, 1, 256, 0, 0));
+    CHECK(!fill_args_ok(2, 2, 1, 0, -1, 0) && !fill_args_ok(2, 2, 0, 0, 0, 0) && !fill_args_ok(3, 2, 1, 0, 0, 0));
+    CHECK(rgba_to_i420a_args_ok(8192, 2, 1) && !rgba_to_i420a_args_ok(8194, 2, 1) && !rgba_to_i420a_args_ok(2, 2, 0) && !rgba_to_i420a_args_ok(2, 3, 1));
+    const h264mi_overlay good{0, 0, 0, 0, 4, 4, 4, 4, 256, 0};
+    CHECK(overlay_args_ok(8, 8, 1, 8192, 8192, 1, &good, 1) && !overlay_args_ok(8, 8, 1, 8194, 8, 1, &good, 1) && !overlay_args_ok(8, 8, 1, 8, 8, 1, nullptr, 1));
+    CHECK(!overlay_args_ok(8, 8, 1, 8, 8, 1, &good, 0) && !overlay_args_ok(8, 8, 1, 8, 8, 1, &good, 4097) && !overlay_args_ok(6, 8, 1, 8, 8, 1, &good, 1));
+    h264mi_overlay bad = good;
+    bad.dx = 2147483646;
+    CHECK(!overlay_args_ok(8, 8, 1, 8, 8, 1, &bad, 1));
+    bad = good; bad.opacity = 257;
+    CHECK(!overlay_args_ok(8, 8, 1, 8, 8, 1, &bad, 1));
+    CHECK(launch_blocks(0) == 0 && launch_blocks(1) == 1 && launch_blocks(8192) == 2048 && launch_blocks(1LL << 40) == 2048);
+    printf("scalar checks, byte counts, ranges\n");
+}
+
+int main() {
+    check_cells();
+    check_tables();
+    check_layouts();
+    check_scalars();
+    printf(failures ? "%d FAILED\n" : "ok\n", failures);
+    return failures ? 1 : 0;
+}
