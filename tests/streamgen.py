@@ -155,6 +155,10 @@ class SyntaxGen:
         self.poc_type, self.dpoaz = poc_type, dpoaz  # POC type 0 / 1 (delta_pic_order_always_zero_flag) / 2
         self.tc_choice = None  # TotalCoeff distribution of generated blocks (None: the default mix)
         self._spec = None      # the scripted macroblock being written (_slice's script=), else None
+        # hooks of the directed parse streams (tests/test_parse_reference.py); None leaves every stream as it was:
+        self.writer = None     # f(levels, nC, maxNumCoeff) -> '0' / '1' string: writes the residual blocks instead of the oracle's writer
+        self.block_hook = None  # f(what, maxNumCoeff, nC, qp) -> levels in scan order, or None to draw the block as usual
+        self.dq_hook = None    # f(qp) -> mb_qp_delta, or None to draw it as usual
         self._cur = {}         # the macroblock log entry being filled (mblog)
         self.frame_num = 0
         self.poc = 0
@@ -232,33 +236,53 @@ class SyntaxGen:
         return c
 
     def _block(self, w, coef, nc):
-        n = self.L.h264o_cavlc_bits(coef.ctypes.data, len(coef), nc, self._bits.ctypes.data, self._bits.size)
-        assert n > 0
-        w.raw(self._bits[:n].tobytes())
+        if self.writer is not None:
+            w.raw(bytes(int(ch) for ch in self.writer([int(v) for v in coef], nc, len(coef))))
+        else:
+            n = self.L.h264o_cavlc_bits(coef.ctypes.data, len(coef), nc, self._bits.ctypes.data, self._bits.size)
+            assert n > 0
+            w.raw(self._bits[:n].tobytes())
         self._cur.setdefault('blocks', []).append([int(v) for v in coef])
         return int(np.count_nonzero(coef))
+
+    def _draw(self, what, maxnum, nc, qp, lqp, big_ok=True):
+        """the levels of one block: the block hook's, else drawn (lqp: the QP that bounds them)"""
+        if self.block_hook is not None:
+            coef = self.block_hook(what, maxnum, nc, qp)
+            if coef is not None:
+                return np.asarray(coef, np.int16)
+        return self._levels(maxnum, lqp, big_ok=big_ok)
 
     def _residual(self, w, nn, mx, my, cur, mtype, cbp, qp, i16):
         qpc = _CHROMA_QP[min(51, max(0, qp + self.cqp))]
         if i16:
-            self._block(w, self._levels(16, qp - 6 if qp >= 6 else 0, big_ok=False), self._nc(nn, None, mx, my, cur, 0))
+            nc = self._nc(nn, None, mx, my, cur, 0)
+            self._block(w, self._draw('i16dc', 16, nc, qp, qp - 6 if qp >= 6 else 0, big_ok=False), nc)
         for k in range(16):
             ras = _BLK_ORDER[k]
             if not (cbp >> (k >> 2)) & 1:
                 continue
-            coef = self._levels(15 if i16 else 16, qp)
-            cur[ras] = self._block(w, coef, self._nc(nn, None, mx, my, cur, ras))
+            nc = self._nc(nn, None, mx, my, cur, ras)
+            coef = self._draw('i16ac' if i16 else 'luma', 15 if i16 else 16, nc, qp, qp)
+            cur[ras] = self._block(w, coef, nc)
         cbpc = cbp >> 4
         if cbpc:
             for pl in range(2):
-                self._block(w, self._levels(4, qpc + 6 if qpc + 6 <= 51 else 51, big_ok=False), -1)
+                self._block(w, self._draw('chroma_dc', 4, -1, qpc, qpc + 6 if qpc + 6 <= 51 else 51, big_ok=False), -1)
             if cbpc == 2:
                 for pl in range(2):
                     for blk in range(4):
-                        cur[16 + 4 * pl + blk] = self._block(w, self._levels(15, qpc), self._ncc(nn, mx, my, cur, pl, blk))
+                        nc = self._ncc(nn, mx, my, cur, pl, blk)
+                        cur[16 + 4 * pl + blk] = self._block(w, self._draw('chroma_ac', 15, nc, qpc, qpc), nc)
 
     def _qp_delta(self, w, qp):
         rng = self.rng
+        hooked = self.dq_hook(qp) if self.dq_hook is not None else None
+        if hooked is not None:
+            dq = int(hooked)
+            w.se(dq)
+            self._cur['dq'] = dq
+            return (qp + dq + 52) % 52
         r = rng.random()
         if r < 0.5:
             dq = 0
@@ -336,6 +360,8 @@ class SyntaxGen:
                 self._cur['rem'].append(0 if m == pm else (m if m < pm else m - 1))
             w.ue(cm)
             cbp = int(rng.integers(0, 48))
+            if self._spec is not None and 'cbp' in self._spec:   # scripted coded_block_pattern
+                cbp = int(self._spec['cbp'])
             self._last_cbp = cbp
             w.ue(self.L.h264o_cbp_code(cbp, 1))
             if cbp:
@@ -348,6 +374,8 @@ class SyntaxGen:
         cbpl = 15 if rng.random() < 0.5 else 0
         if getattr(self, 'i16_cbp', None) is not None:  # fixed I_16x16 coded_block_pattern (tools/parse_mix.py)
             cbpc, cbpl = self.i16_cbp >> 4, self.i16_cbp & 15
+        if self._spec is not None and 'cbp' in self._spec:   # scripted coded_block_pattern (0 or 15, chroma << 4)
+            cbpc, cbpl = int(self._spec['cbp']) >> 4, int(self._spec['cbp']) & 15
         self._last_cbp = cbpl | (cbpc << 4)
         w.ue(off + 1 + pm16 + 4 * cbpc + (12 if cbpl else 0))
         self._cur['mb_type'] = off + 1 + pm16 + 4 * cbpc + (12 if cbpl else 0)
@@ -432,7 +460,7 @@ class SyntaxGen:
                 self._spec = script.get(addr) if script else None
                 if self._spec is not None:
                     kind = self._spec['kind']
-                if islice and kind in ('skip', 'p16', 'p16x8', 'p8x16', 'p8x8'):
+                if islice and kind in ('skip', 'p16', 'p16x8', 'p8x16', 'p8x8', 'p8x8ref0'):
                     kind = 'i4'
                 self._cur = dict(mb_type=-1, slice_qp=slice_qp, first=self._first, cbp=0)
                 self.mblog.append(self._cur)
@@ -451,7 +479,7 @@ class SyntaxGen:
                     self._cur['cbp'] = self._last_cbp
                     continue
                 cur = [0] * 24
-                mt = {'p16': 0, 'p16x8': 1, 'p8x16': 2, 'p8x8': 3}[kind]
+                mt = {'p16': 0, 'p16x8': 1, 'p8x16': 2, 'p8x8': 3, 'p8x8ref0': 4}[kind]   # 4: only when scripted
                 w.ue(mt)
                 self._cur.update(mb_type=mt, subs=[0] * 4, mvd=[])
                 given = list(self._spec['mvd']) if self._spec is not None and 'mvd' in self._spec else None   # scripted mvd_l0
@@ -477,13 +505,15 @@ class SyntaxGen:
                 cbp = int(rng.integers(0, 48)) if rng.random() < 0.85 else 0
                 if cbp_fixed is not None:
                     cbp = cbp_fixed
+                if self._spec is not None and 'cbp' in self._spec:   # scripted coded_block_pattern
+                    cbp = int(self._spec['cbp'])
                 w.ue(self.L.h264o_cbp_code(cbp, 0))
                 self._cur['cbp'] = cbp
                 if cbp:
                     qp = self._qp_delta(w, qp)
                     self._residual(w, nn, mx, my, cur, kind, cbp, qp, False)
                 nn[my][mx] = cur
-                self.log.append(({'p16': 2, 'p16x8': 4, 'p8x16': 5, 'p8x8': 6}[kind], qp, cbp))
+                self.log.append(({'p16': 2, 'p16x8': 4, 'p8x16': 5, 'p8x8': 6, 'p8x8ref0': 6}[kind], qp, cbp))
         if run:
             w.ue(run)
         out.append(w.rbsp())

@@ -35,6 +35,7 @@ Where each fact was found (wasm function indices count imports; offsets are file
              rows at FF + 6 rows (345 @190274 load16_u off=96, 536 @283180 i32.const 38992)
 
   python tools/wasm_tables.py [--wasm PATH] [--out tests/golden/openh264_tables.json]
+                               [--vlc-out tests/golden/openh264_vlc_tables.json]
 """
 import argparse
 import hashlib
@@ -47,6 +48,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 DEFAULT_WASM = '/root/reference/scripts/h264.wasm'
 DEFAULT_OUT = os.path.join(ROOT, 'tests', 'golden', 'openh264_tables.json')
+DEFAULT_VLC_OUT = os.path.join(ROOT, 'tests', 'golden', 'openh264_vlc_tables.json')
 
 
 def uleb(b, i):
@@ -146,18 +148,22 @@ class Memory:
             return list(struct.unpack_from(f'<{count}{fmt}', self.b, fo)), fo
         except ValueError:
             pass
-        # a table whose tail is zero: the linker ends the data segment at its last non-zero byte and linear memory
-        # starts zeroed, so the bytes past the segment read 0 -- as long as no other segment covers them
+        # a table with runs of zeros: the linker ends a data segment at its last non-zero byte and starts the next at
+        # the next non-zero one, and linear memory starts zeroed. The image of [mem, mem + n) is therefore the bytes of
+        # every segment that overlaps it, each at its address, over zeros. The first byte has to lie in a segment (a
+        # table that starts with zeros is addressed by its first non-zero entry's row instead), and so has the last
+        # non-zero one by construction; the file offset reported is that of the first byte
+        raw, first = bytearray(n), None
         for k, (fo, sz) in enumerate(self.segs):
             a = self.addr[k]
-            if a <= mem < a + sz:
-                for k2, (_, sz2) in enumerate(self.segs):
-                    a2 = self.addr[k2]
-                    if k2 != k and a2 < mem + n and a + sz < a2 + sz2:
-                        raise ValueError(f'address {mem} (+{n}) spans two data segments')
-                raw = self.b[fo + (mem - a):fo + sz] + bytes(n - (a + sz - mem))
-                return list(struct.unpack_from(f'<{count}{fmt}', raw, 0)), fo + (mem - a)
-        raise ValueError(f'address {mem} (+{n}) is not inside a data segment')
+            lo, hi = max(a, mem), min(a + sz, mem + n)
+            if lo < hi:
+                raw[lo - mem:hi - mem] = self.b[fo + (lo - a):fo + (hi - a)]
+                if lo == mem:
+                    first = fo + (mem - a)
+        if first is None:
+            raise ValueError(f'address {mem} (+{n}) does not start inside a data segment')
+        return list(struct.unpack_from(f'<{count}{fmt}', bytes(raw), 0)), first
 
 
 # name: (linear-memory address, struct format, shape, meaning)
@@ -193,6 +199,22 @@ TABLES = {
     'chroma_qp': (55152, 'B', (52,), 'g_kuiChromaQpTable: chroma QP of min(51, luma QP + chroma_qp_index_offset) (func 534)'),
     'level_limits': (63120, 'i', (17, 8),'g_ksLevelLimits {level_idc, MaxMBPS, MaxFS, MaxDpbMbs, MaxBR, MaxCPB, MinVmv, MaxVmv} '
                      '(WelsInitSps, func 280, walks it in this order)'),
+}
+
+# OpenH264's *encoder* CAVLC tables (codec/encoder/core/src/svc_set_mb_syn_cavlc.cpp / wels_common_basis tables), every
+# entry a {code value, code length} byte pair; length 0: no such code. They lie back to back and span several data
+# segments (the linker elides their runs of zeros), so Memory.read stitches them. They go to a file of their own
+# (DEFAULT_VLC_OUT), which tests/test_parse_reference.py compares with the oracle's tables and with tests/parseref.py's
+# printed bit strings. OpenH264's decoder lookup tables in the same module are not read.
+VLC_TABLES = {
+    'coeff_token': (40992, 'B', (5, 17, 4, 2), 'g_kuiVlcCoeffToken[nC class: 0 <= nC < 2, 2 <= nC < 4, 4 <= nC < 8, 8 <= nC, '
+                    'chroma DC][TotalCoeff][TrailingOnes] = {code, length} (Table 9-5)'),
+    'total_zeros': (41712, 'B', (15, 16, 2), 'g_kuiVlcTotalZeros[TotalCoeff], rows 1..15 (row 0, at 41680, is unused and all '
+                    'zero)[total_zeros] = {code, length} (Tables 9-7, 9-8)'),
+    'total_zeros_chroma_dc': (42200, 'B', (3, 4, 2), 'g_kuiVlcTotalZerosChromaDc[TotalCoeff], rows 1..3 (row 0, at 42192, is '
+                              'unused)[total_zeros] = {code, length} (Table 9-9 (a))'),
+    'run_before': (42254, 'B', (7, 15, 2), 'g_kuiVlcRunBefore[min(zerosLeft, 7)], rows 1..7 (row 0, at 42224, is unused)'
+                   '[run_before] = {code, length} (Table 9-10)'),
 }
 
 # name: (file offset of the instruction, opcode, function, meaning)
@@ -328,12 +350,46 @@ def extract(path):
     return out
 
 
+def _nest(vals, shape):
+    if len(shape) == 1:
+        return vals
+    step = len(vals) // shape[0]
+    return [_nest(vals[k * step:(k + 1) * step], shape[1:]) for k in range(shape[0])]
+
+
+def extract_vlc(path):
+    """the VLC_TABLES, values only: nested lists by the shape, the innermost pair {code, length}"""
+    b = open(path, 'rb').read()
+    mem = Memory(b)
+    out = {'source': 'scripts/h264.wasm (reference, prebuilt OpenH264 + wrapper; parsed as bytes, never executed)',
+           'sha256': hashlib.sha256(b).hexdigest(), 'tables': {}}
+    for name, (addr, fmt, shape, meaning) in VLC_TABLES.items():
+        n = 1
+        for d in shape:
+            n *= d
+        vals, fo = mem.read(addr, fmt, n)
+        out['tables'][name] = {'address': addr, 'file_offset': fo, 'type': 'uint8', 'shape': list(shape), 'meaning': meaning,
+                               'values': _nest(vals, shape)}
+    return out
+
+
+def _dump_compact(d, path):
+    """json with one line per innermost table row"""
+    text = json.dumps(d, indent=1)
+    text = re.sub(r'\[\s+((?:\d+,\s+)*\d+)\s+\]', lambda m: '[' + re.sub(r'\s+', ' ', m.group(1)) + ']', text)
+    text = re.sub(r'\[\s+((?:\[[\d, ]*\],\s+)*\[[\d, ]*\])\s+\]', lambda m: '[' + re.sub(r'\s+', ' ', m.group(1)) + ']', text)
+    with open(path, 'w') as f:
+        f.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--wasm', default=DEFAULT_WASM)
     ap.add_argument('--out', default=DEFAULT_OUT)
+    ap.add_argument('--vlc-out', default=DEFAULT_VLC_OUT)
     a = ap.parse_args()
     d = extract(a.wasm)
+    _dump_compact(extract_vlc(a.wasm), a.vlc_out)
     with open(a.out, 'w') as f:
         json.dump(d, f, indent=1)
         f.write('\n')
