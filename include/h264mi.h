@@ -516,6 +516,54 @@ int h264mi_speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_
 int h264mi_enc_encode_composed_any(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc,
                                    const h264mi_cell *cells, int ncells, int filter, int bg_y, int bg_cb, int bg_cr);
 
+/* Turning a picture on the device: a phone's portrait frames with a rotation flag, a mirrored front
+   camera, a capture card's bottom-up rows. Every plane of a tight I420 frame (Y sw x sh; Cb, Cr sw/2 x sh/2) is turned
+   by itself; samples are moved, never interpolated. With S the pw x ph source plane, D[y][x] of the destination plane:
+     value  name                          destination   D[y][x] =
+     0      H264MI_ORIENT_IDENTITY        pw x ph       S[y][x]
+     1      H264MI_ORIENT_ROT90           ph x pw       S[ph-1-x][y]          a quarter turn clockwise
+     2      H264MI_ORIENT_ROT180          pw x ph       S[ph-1-y][pw-1-x]
+     3      H264MI_ORIENT_ROT270          ph x pw       S[x][pw-1-y]          three quarter turns clockwise
+     4      H264MI_ORIENT_MIRROR          pw x ph       S[y][pw-1-x]          left-right
+     5      H264MI_ORIENT_FLIP            pw x ph       S[ph-1-y][x]          top-bottom
+     6      H264MI_ORIENT_TRANSPOSE       ph x pw       S[x][y]
+     7      H264MI_ORIENT_TRANSVERSE      ph x pw       S[ph-1-x][pw-1-y] */
+#define H264MI_ORIENT_IDENTITY 0
+#define H264MI_ORIENT_ROT90 1
+#define H264MI_ORIENT_ROT180 2
+#define H264MI_ORIENT_ROT270 3
+#define H264MI_ORIENT_MIRROR 4
+#define H264MI_ORIENT_FLIP 5
+#define H264MI_ORIENT_TRANSPOSE 6
+#define H264MI_ORIENT_TRANSVERSE 7
+/* host only: the size *dw x *dh of a sw x sh frame turned by orient (sh x sw for 1, 3, 6, 7). Returns 0, or -1 -- with
+   nothing written -- on an orientation outside 0..7, a side that is odd or outside 2..8192, or a null pointer */
+int h264mi_orient_size(int orient, int sw, int sh, int *dw, int *dh);
+/* host only: the one orientation that equals turning by `first`, then turning the result by `then`; -1 if either is
+   outside 0..7. The eight form a group (the symmetries of a rectangle's diagonals): ROT90 then ROT90 is ROT180, MIRROR
+   then ROT90 is TRANSVERSE, ROT90 then MIRROR is TRANSPOSE. */
+int h264mi_orient_compose(int first, int then);
+/* host only: the orientation that undoes orient (ROT90 <-> ROT270, every other is its own inverse); -1 outside 0..7 */
+int h264mi_orient_inverse(int orient);
+/* async on hip_stream: n tight sw x sh I420 frames back to back at d_src (any alignment) to n tight frames of the size
+   h264mi_orient_size gives at d_dst, one launch. A frame keeps its byte count. The same bytes from run to run, equal to
+   a restatement on any host; IDENTITY copies. No arithmetic is involved, so the sides go up to 8192 both ways.
+   Returns 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer, n <= 0, an
+   orientation outside 0..7, a side that is odd or outside 2..8192, or source and destination byte ranges that overlap
+   (turning in place is not provided). Orientation inside compose cells, turned sprites and RGBA frames are not
+   provided either: turn the I420 frames first. */
+int h264mi_i420_orient_dev(void *d_dst, const void *d_src, int sw, int sh, int n, int orient, void *hip_stream);
+/* async, as h264mi_enc_encode_scaled, from nstreams tight I420 frames back to back (device, any alignment) that orient
+   turns into the encoder's pictures: their size sw x sh is the one for which h264mi_orient_size(orient, sw, sh) is the
+   encoder's width x height -- height x width for the four transposing orientations, the encoder's own otherwise. One
+   batched launch (h264mi_i420_orient_dev) turns them into the encoder's input area on its stream; then an overlay list
+   in force is blended onto the turned pictures, then the same frame step -- rate control, slices, exact GOM,
+   inject_error and the quality records as in h264mi_enc_encode; the records compare the turned source with the
+   reconstruction. The source frames are read by the orient launch only. Returns -1 and enqueues nothing -- the
+   encoder's next step is as if the call had not happened -- on a null pointer, an orientation outside 0..7, an encoder
+   of odd width or height, or frames that overlap the encoder's input area. */
+int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orient);
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -258,6 +258,30 @@ int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w,
     if (launch_scale_i420(c->d_src, c->w, c->h, (const uint8_t *)d_frames, src_w, src_h, c->S, c->stream) != 0) return -1;
     return enc_code_input(c);
 }
+// Rotating and mirroring (DESIGN.md §5.9; orient.hip): n tight I420 frames of one geometry, one launch
+int h264mi_orient_size(int orient, int sw, int sh, int *dw, int *dh) { return orient_size(orient, sw, sh, dw, dh); }
+int h264mi_orient_compose(int first, int then) { return orient_compose(first, then); }
+int h264mi_orient_inverse(int orient) { return orient_inverse(orient); }
+int h264mi_i420_orient_dev(void *d_dst, const void *d_src, int sw, int sh, int n, int orient, void *hip_stream) {
+    int dw, dh;
+    if (!d_dst || !d_src || !orient_args_ok(orient, sw, sh, n) || orient_size(orient, sw, sh, &dw, &dh) != 0 ||
+        i420_ranges_overlap(d_dst, dw, dh, n, d_src, sw, sh, n))
+        return -1;
+    return launch_orient_i420((uint8_t *)d_dst, (const uint8_t *)d_src, sw, sh, n, orient, (hipStream_t)hip_stream);
+}
+// nstreams tight I420 frames back to back that orient turns into the encoder's pictures (h x w ones for a transposing
+// orientation): one batched launch into the encoder's own input area on its stream, then the frame step as
+// h264mi_enc_encode runs it. Every refusal comes before the first launch
+int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orient) {
+    if (!e || !d_frames) return -1;
+    EncCtx *c = e->c;
+    int sw, sh;  // the inverse turns a w x h picture back into the source's size
+    if (orient_size(orient_inverse(orient), c->w, c->h, &sw, &sh) != 0 || !orient_args_ok(orient, sw, sh, c->S) ||
+        i420_ranges_overlap(c->d_src, c->w, c->h, c->S, d_frames, sw, sh, c->S))
+        return -1;
+    if (launch_orient_i420(c->d_src, (const uint8_t *)d_frames, sw, sh, c->S, orient, c->stream) != 0) return -1;
+    return enc_code_input(c);
+}
 // Several pictures into one (DESIGN.md §5.4; compose.hip): every cell's crop of a source frame area-averaged into its
 // rectangle of a canvas, 64 cells to a launch
 int h264mi_i420_compose_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,

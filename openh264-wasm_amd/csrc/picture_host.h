@@ -1,4 +1,4 @@
-// picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip)
+// picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip)
 // and the runtime (runtime_enc.inc, capi_enc.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
@@ -150,4 +150,11 @@ bool upscale_args_ok(int dw, int dh, int sw, int sh, int n, int filter);
 int launch_compose_any_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,
                             int filter, hipStream_t s);
 int speaker_cells(h264mi_cell *out, int cap, int n, int speaker, int src_w, int src_h, int cw, int ch);
+// orient.hip
+int launch_orient_i420(uint8_t *dst, const uint8_t *src, int sw, int sh, int n, int orient, hipStream_t s);
+bool orient_args_ok(int orient, int sw, int sh, int n);
+int orient_size(int orient, int sw, int sh, int *dw, int *dh);
+int orient_compose(int first, int then);
+int orient_inverse(int orient);
+void orient_plane_host(int orient, const uint8_t *S, int pw, int ph, uint8_t *D);
 }  // namespace h264mi

@@ -144,6 +144,11 @@ def lib():
             'h264mi_i420_compose_any_dev': (i, [vp, i, i, i, vp, i, i, i, vp, i, i, vp]),
             'h264mi_speaker_cells': (i, [vp, i, i, i, i, i, i, i]),
             'h264mi_enc_encode_composed_any': (i, [vp, vp, i, i, i, vp, i, i, i, i, i]),
+            'h264mi_orient_size': (i, [i, i, i, vp, vp]),
+            'h264mi_orient_compose': (i, [i, i]),
+            'h264mi_orient_inverse': (i, [i]),
+            'h264mi_i420_orient_dev': (i, [vp, vp, i, i, i, i, vp]),
+            'h264mi_enc_encode_oriented': (i, [vp, vp, i]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -356,6 +361,16 @@ class BatchEncoder:
         assert frames.is_cuda and frames.numel() >= self.S * _i420_bytes(src_w, src_h)
         if self._L.h264mi_enc_encode_scaled(self._e, ctypes.c_void_p(frames.data_ptr()), int(src_w), int(src_h)) != 0:
             raise ValueError(f'h264mi_enc_encode_scaled refused {src_w}x{src_h} -> {self.w}x{self.h}')
+
+    def encode_oriented(self, frames, orient):
+        """frames: uint8 CUDA tensor holding S tight I420 frames back to back, any alignment, of the size that orient
+        (ORIENT_*) turns into the encoder's -- h x w for the four transposing orientations -- (async): one batched
+        turn (i420_orient) into the encoder's input area on its stream, then an overlay list in force and the frame
+        step of encode(); the quality records then compare the turned source with the reconstruction. ValueError,
+        with nothing enqueued, for an unknown orientation, an encoder of odd size or frames inside the input area."""
+        assert frames.is_cuda and frames.numel() >= self.S * _i420_bytes(self.w, self.h)
+        if self._L.h264mi_enc_encode_oriented(self._e, ctypes.c_void_p(frames.data_ptr()), int(orient)) != 0:
+            raise ValueError(f'h264mi_enc_encode_oriented refused orientation {orient} -> {self.w}x{self.h}')
 
     def encode_composed(self, src, src_w, src_h, nsrc, cells, bg=(16, 128, 128)):
         """src: uint8 CUDA tensor holding nsrc tight I420 frames of src_w x src_h back to back, any alignment; cells: a
@@ -889,6 +904,54 @@ def i420_compose_any(canvas, cw, ch, ncanvas, src, src_w, src_h, nsrc, cells, fi
     if lib().h264mi_i420_compose_any_dev(ctypes.c_void_p(canvas.data_ptr()), cw, ch, ncanvas, ctypes.c_void_p(src.data_ptr()), src_w, src_h,
                                          nsrc, arr, len(arr), int(filter), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {len(arr)} cells of {nsrc} sources {src_w}x{src_h} on {ncanvas} canvases {cw}x{ch}, filter {filter}')
+
+
+ORIENT_IDENTITY = 0    # H264MI_ORIENT_*: D[y][x] = S[y][x]
+ORIENT_ROT90 = 1       # a quarter turn clockwise, S[ph-1-x][y]
+ORIENT_ROT180 = 2      # S[ph-1-y][pw-1-x]
+ORIENT_ROT270 = 3      # three quarter turns clockwise, S[x][pw-1-y]
+ORIENT_MIRROR = 4      # left-right, S[y][pw-1-x]
+ORIENT_FLIP = 5        # top-bottom, S[ph-1-y][x]
+ORIENT_TRANSPOSE = 6   # S[x][y]
+ORIENT_TRANSVERSE = 7  # S[ph-1-x][pw-1-y]
+
+
+def orient_size(orient, w, h):
+    """(width, height) of a w x h frame turned by orient (h264mi_orient_size; host only): (h, w) for ROT90, ROT270,
+    TRANSPOSE and TRANSVERSE. ValueError on an unknown orientation or a side that is odd or outside 2..8192."""
+    dw, dh = ctypes.c_int(), ctypes.c_int()
+    if lib().h264mi_orient_size(int(orient), int(w), int(h), ctypes.byref(dw), ctypes.byref(dh)) != 0:
+        raise ValueError(f'bad arguments: orientation {orient} of {w}x{h}')
+    return dw.value, dh.value
+
+
+def orient_compose(first, then):
+    """the one orientation that equals turning by `first`, then by `then` (h264mi_orient_compose; host only)"""
+    r = lib().h264mi_orient_compose(int(first), int(then))
+    if r < 0:
+        raise ValueError(f'bad orientations: {first}, {then}')
+    return r
+
+
+def orient_inverse(orient):
+    """the orientation that undoes orient (h264mi_orient_inverse; host only)"""
+    r = lib().h264mi_orient_inverse(int(orient))
+    if r < 0:
+        raise ValueError(f'bad orientation: {orient}')
+    return r
+
+
+def i420_orient(dst, src, sw, sh, n, orient, stream=None):
+    """n tight sw x sh I420 frames (uint8 CUDA tensor src, any alignment) turned by orient (ORIENT_*) into n tight frames
+    of orient_size(orient, sw, sh) (dst, the same byte count), every plane on its own, one launch, async on stream
+    (default: the current one); h264mi_i420_orient_dev. Samples are moved, never interpolated: the bytes equal
+    tests/orientref.py's. ValueError on a bad argument (an unknown orientation, a side that is odd or outside 2..8192,
+    n <= 0, overlapping buffers)."""
+    _assert_dev_u8(dst, src)
+    assert n <= 0 or min(sw, sh) <= 0 or min(dst.numel(), src.numel()) >= n * _i420_bytes(sw, sh)
+    if lib().h264mi_i420_orient_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), sw, sh, n, int(orient),
+                                    _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: orientation {orient} of {n} frames {sw}x{sh}')
 
 
 class Overlay(ctypes.Structure):

@@ -1,11 +1,11 @@
 // picture_host_san.hip -- the host rules of the picture calls (csrc/picture_host.h and the host halves of scale.hip,
-// compose.hip, overlay.hip, upscale.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
+// compose.hip, overlay.hip, upscale.hip, orient.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
 // is loaded into Python, no kernel is launched, no device is needed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=all tools/picture_host_san.hip openh264-wasm_amd/csrc/scale.hip \
 //         openh264-wasm_amd/csrc/compose.hip openh264-wasm_amd/csrc/overlay.hip openh264-wasm_amd/csrc/upscale.hip \
-//         -o picture_host_san && ./picture_host_san
+//         openh264-wasm_amd/csrc/orient.hip -o picture_host_san && ./picture_host_san
 //
 // It runs, with every table in a heap block of exactly the size the call may touch:
 //   * cells_ok (both values of may_enlarge) on valid lists and on every field of a cell made odd, negative, one past the
@@ -17,7 +17,9 @@
 //   * mosaic_cells and speaker_cells for 1, 64, 65 and 4096 sources and the sizes of tests/test_compose_host.py, their
 //     cells checked by cells_ok, and their refusals;
 //   * the scalar checks (scale, upscale, fill, overlay, sprite conversion) at their limits, the byte counts and the
-//     range test.
+//     range test;
+//   * orient.hip's host restatement of a turned plane against the header's table, compose and inverse against planes
+//     turned twice, its sizes and scalar check at their limits.
 // Prints one line per group and "ok"; exits 1 at the first difference.
 #include <cstdio>
 #include <cstdlib>
@@ -256,7 +258,53 @@ static void check_scalars() {
     printf("scalar checks, byte counts, ranges\n");
 }
 
+// orient.hip's host half: the plane restatement in heap blocks of exactly pw * ph bytes against the header's table in
+// 64-bit indices, compose and inverse against planes turned twice, the sizes and the scalar check at their limits
+static void check_orient() {
+    const int sizes[][2] = {{1, 1}, {3, 2}, {2, 3}, {5, 7}, {64, 1}, {1, 64}, {18, 9}};
+    for (const auto &s : sizes) {
+        const int pw = s[0], ph = s[1];
+        std::unique_ptr<uint8_t[]> S(new uint8_t[pw * ph]), D(new uint8_t[pw * ph]), E(new uint8_t[pw * ph]), F(new uint8_t[pw * ph]);
+        for (int k = 0; k < pw * ph; k++) S[k] = (uint8_t)(k * 37 + 11);
+        for (int a = 0; a < 8; a++) {
+            const bool t = a == 1 || a == 3 || a == 6 || a == 7;
+            const long long qw = t ? ph : pw, qh = t ? pw : ph;
+            orient_plane_host(a, S.get(), pw, ph, D.get());
+            for (long long y = 0; y < qh; y++)
+                for (long long x = 0; x < qw; x++) {
+                    const long long sy[8] = {y, ph - 1 - x, ph - 1 - y, x, y, ph - 1 - y, x, ph - 1 - x};
+                    const long long sx[8] = {x, y, pw - 1 - x, pw - 1 - y, pw - 1 - x, x, y, pw - 1 - y};
+                    CHECK(D[y * qw + x] == S[sy[a] * pw + sx[a]]);
+                }
+            for (int b = 0; b < 8; b++) {  // a, then b, in one turn
+                const int c = orient_compose(a, b);
+                CHECK(c >= 0 && c < 8);
+                if (c < 0) continue;
+                orient_plane_host(b, D.get(), (int)qw, (int)qh, E.get());
+                orient_plane_host(c, S.get(), pw, ph, F.get());
+                CHECK(std::equal(E.get(), E.get() + pw * ph, F.get()));
+            }
+            orient_plane_host(orient_inverse(a), D.get(), (int)qw, (int)qh, E.get());
+            CHECK(std::equal(E.get(), E.get() + pw * ph, S.get()));
+        }
+    }
+    int dw = -7, dh = -7;
+    for (int bad : {-1, 8, 2147483647}) {
+        CHECK(orient_compose(bad, 0) == -1 && orient_compose(0, bad) == -1 && orient_inverse(bad) == -1);
+        CHECK(orient_size(bad, 16, 16, &dw, &dh) == -1 && !orient_args_ok(bad, 16, 16, 1));
+    }
+    for (int bad : {0, -2, 15, 8194, 2147483647}) {
+        CHECK(orient_size(1, bad, 16, &dw, &dh) == -1 && orient_size(1, 16, bad, &dw, &dh) == -1);
+        CHECK(!orient_args_ok(1, bad, 16, 1) && !orient_args_ok(0, 16, bad, 1));
+    }
+    CHECK(orient_size(1, 16, 16, nullptr, &dh) == -1 && orient_size(1, 16, 16, &dw, nullptr) == -1 && dw == -7 && dh == -7);
+    CHECK(orient_size(1, 8192, 2, &dw, &dh) == 0 && dw == 2 && dh == 8192 && orient_size(4, 8192, 2, &dw, &dh) == 0 && dw == 8192 && dh == 2);
+    CHECK(orient_args_ok(7, 8192, 8192, 2147483647) && !orient_args_ok(7, 16, 16, 0) && !orient_args_ok(7, 16, 16, -1));
+    printf("orient: the plane restatement, compose, inverse on 7 sizes, the scalar checks\n");
+}
+
 int main() {
+    check_orient();
     check_cells();
     check_tables();
     check_layouts();
