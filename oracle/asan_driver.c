@@ -68,6 +68,20 @@ static void round_trip(int w, int h, int br, int nf, int skip) {
     }
     int32_t st[6];
     h264o_enc_me_stats(e, st);
+    {   /* the branch audit's exports: every count is read, every MB record holds only classes of the table */
+        const int nc = h264o_enc_branch_classes(), nw = h264o_enc_branch_words();
+        const size_t nmb = (size_t)((w + 15) / 16) * ((h + 15) / 16);
+        int64_t *cnt = malloc((size_t)nc * sizeof(int64_t));
+        uint64_t *rec = malloc(nmb * (size_t)nw * sizeof(uint64_t));
+        h264o_enc_branch_counts(e, cnt);
+        h264o_enc_mb_branches(e, rec);
+        int64_t total = 0;
+        for (int c = 0; c < nc; c++) { CHECK(h264o_enc_branch_name(c) != NULL && cnt[c] >= 0, "branch class %d", c); total += cnt[c]; }
+        CHECK(total > 0 && h264o_enc_branch_name(nc) == NULL && h264o_enc_branch_name(-1) == NULL, "branch table %dx%d", w, h);
+        for (size_t m = 0; m < nmb; m++)
+            for (int c = nc; c < 64 * nw; c++) CHECK(!(rec[m * (size_t)nw + (c >> 6)] >> (c & 63) & 1), "MB %zu holds class %d", m, c);
+        free(cnt); free(rec);
+    }
     (void)h264o_enc_frames_skipped(e);
     (void)h264o_enc_last_qp(e);
     h264o_enc_destroy(e);

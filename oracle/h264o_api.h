@@ -35,6 +35,17 @@ int h264o_enc_frames_skipped(const H264OEnc *e);
 /* {cross searches, cross searches that moved, neighbour start points won, P_Skip judges run, double-check skips,
  * intra MBs in P slices} */
 void h264o_enc_me_stats(const H264OEnc *e, int32_t out[6]);
+/* Decision-branch audit: the encoder's forward decisions as named classes, one per outcome.
+ * h264o_enc_branch_classes: how many; h264o_enc_branch_name(c): class c's name (NULL outside the table);
+ * h264o_enc_branch_counts: how often each was taken since creation (one int64 per class);
+ * h264o_enc_mb_branches: beside h264o_enc_mbinfo, per MB of the last coded frame the classes it took, as
+ * h264o_enc_branch_words() uint64 (bit c & 63 of word c >> 6); a row's QP classes stand in its first MB's record.
+ * Counting reads decisions and makes none: no output byte depends on it. */
+int h264o_enc_branch_classes(void);
+const char *h264o_enc_branch_name(int c);
+int h264o_enc_branch_words(void);
+void h264o_enc_branch_counts(const H264OEnc *e, int64_t *out);
+void h264o_enc_mb_branches(const H264OEnc *e, uint64_t *out);
 /* WelsCalculateSingleCtr4x4 (h264.wasm func 1011) over 16 levels in scan order */
 int h264o_single_ctr(const int16_t lv[16]);
 /* PredictSadSkip (h264.wasm func 331) over the neighbour cache {top-left, top, top-right, left}: reference index (-2

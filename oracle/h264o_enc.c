@@ -98,6 +98,7 @@ typedef struct {
     uint32_t *gom_sad;      /* rc+132 pCurrentFrameGomSad: the frame's complexity per GOM */
     int mb_seen, last_coded; /* this frame's MBs counted so far, the last one with bits (-1: none) */
     int32_t *gom_trace;     /* per GOM of the last P frame {QP, slice bits before it, target bits, last coded MB + 1} */
+    int gom_step, gom_unclipped;  /* branch audit: the last rc_mb_init_gom call's QP step (99: it made none) and QP before the clip */
 } Rc;
 
 struct H264OEnc {
@@ -119,7 +120,74 @@ struct H264OEnc {
      * vector) of a skipped MB, -1 for any other; this frame's and the reference picture's (last coded frame) */
     int32_t *sksad_cur, *sksad_ref;
     int stat_cross, stat_cross_moved, stat_nb_start, stat_skip_tried, stat_skip_double, stat_intra_p;  /* ME path counters (tests: coverage of the search stages) */
+    /* decision-branch audit: how often each class of BRANCH_CLASSES was taken since creation, and per
+     * MB of the last coded frame the classes it took (BR_WORDS x 64 bits). Counting reads decisions, it makes none. */
+    int64_t *br;
+    uint64_t *mbbr;
+    int br_mb;        /* the MB the next hits belong to */
+    int br_pslice;    /* the intra decision's classes: II_* in I slices, IP_* in P slices */
 };
+
+/* ---------------- decision-branch classes ---------------- */
+/* One class per outcome of each forward decision below. G_<family>_<position>: a P-slice family taken on a one-MB-wide
+ * picture, a one-MB-high picture, in the first / last MB column, in the first MB row. */
+#define BR_GEO(X, F) X(G_##F##_MBW1) X(G_##F##_MBH1) X(G_##F##_COL_FIRST) X(G_##F##_COL_LAST) X(G_##F##_ROW_FIRST)
+#define BR_INTRA(X, P) X(P##_VAA_BELOW) X(P##_VAA_ABOVE) X(P##_I4_EARLY_STOP) X(P##_I4_LOST_OVERHEAD) X(P##_I4) X(P##_I16)
+#define BR_NB9(X, P) X(P##_NONE) X(P##_UP) X(P##_DOWN) X(P##_LEFT) X(P##_RIGHT) X(P##_UP_LEFT) X(P##_UP_RIGHT) X(P##_DOWN_LEFT) X(P##_DOWN_RIGHT)
+#define BR_QUAD(X, P) X(P##_Y0_SET) X(P##_Y1_SET) X(P##_Y2_SET) X(P##_Y3_SET) X(P##_Y0_CLEAR) X(P##_Y1_CLEAR) X(P##_Y2_CLEAR) X(P##_Y3_CLEAR)
+#define BRANCH_CLASSES(X) \
+    /* P_Skip judge */ \
+    X(J_TRY_LEFT) X(J_TRY_TOP) X(J_TRY_TOPLEFT) X(J_TRY_TOPRIGHT) X(J_TRY_COLOC) X(J_NOT_TRIED) \
+    X(J_MV_BELOW_XMIN) X(J_MV_ABOVE_XMAX) X(J_MV_BELOW_YMIN) X(J_MV_ABOVE_YMAX) \
+    X(J_TAKE_SAD_ZERO) X(J_TAKE_BELOW_PRED_SAD) X(J_TAKE_BELOW_COLOC_SAD) X(J_TAKE_RESIDUAL) X(J_NOT_TAKEN) \
+    X(J_REJ_LUMA_LEVEL) X(J_REJ_LUMA_CTR) X(J_REJ_CHROMA_DC) X(J_REJ_CHROMA_LEVEL) X(J_REJ_CHROMA_CTR) \
+    X(J_KEEP) X(J_NOKEEP_PICTURE_EDGE) X(J_NOKEEP_LEFT) X(J_NOKEEP_TOP) X(J_NOKEEP_TOPRIGHT) \
+    X(J_DOUBLE_CHECK) \
+    /* intra alternative in P slices; the intra decision itself in I and in P slices */ \
+    X(IA_AFTER_SKIP_WON) X(IA_AFTER_SKIP_LOST) X(IA_AFTER_SEARCH_WON) X(IA_AFTER_SEARCH_LOST) \
+    BR_INTRA(X, II) BR_INTRA(X, IP) \
+    /* integer search */ \
+    X(S_START_MVP) X(S_START_ZERO) X(S_START_A) X(S_START_B) X(S_START_C) X(S_START_C_TOPLEFT) X(S_CAND_CLIPPED) \
+    X(S_DIA_0) X(S_DIA_1) X(S_DIA_2_7) X(S_DIA_8_31) X(S_DIA_CAP) \
+    X(S_DIA_EDGE_XMIN) X(S_DIA_EDGE_XMAX) X(S_DIA_EDGE_YMIN) X(S_DIA_EDGE_YMAX) \
+    X(S_CROSS_OFF) X(S_CROSS_STAYED) X(S_CROSS_MOVED_H) X(S_CROSS_MOVED_V) \
+    X(S_FINAL_XMIN) X(S_FINAL_XMAX) X(S_FINAL_YMIN) X(S_FINAL_YMAX) \
+    X(S_REF_OUT_LEFT) X(S_REF_OUT_RIGHT) X(S_REF_OUT_TOP) X(S_REF_OUT_BOTTOM) \
+    /* sub-pel refinement: the last neighbour to improve the cost at each step */ \
+    BR_NB9(X, SP_HALF) BR_NB9(X, SP_QUARTER) \
+    /* residual */ \
+    X(R_QUANT_INTER) X(R_QUANT_INTRA) X(R_I16_LUMA_DC) X(R_CHROMA_DC_INTER) X(R_CHROMA_DC_INTRA) \
+    BR_QUAD(X, R_P) BR_QUAD(X, R_I4) X(R_I16_AC_SET) X(R_I16_AC_CLEAR) X(R_P16_CBP_ZERO_KEPT) \
+    X(R_CBPC_0_INTER) X(R_CBPC_1_INTER) X(R_CBPC_2_INTER) X(R_CBPC_0_INTRA) X(R_CBPC_1_INTRA) X(R_CBPC_2_INTRA) \
+    /* QP inside a P frame: this project's row plan, then OpenH264's GOM rule (exact mode) */ \
+    X(Q_ROW_PLUS2) X(Q_ROW_PLUS1) X(Q_ROW_ZERO) X(Q_ROW_MINUS1) X(Q_ROW_CLIP_MAX) X(Q_ROW_CLIP_MIN) \
+    X(Q_ROW_FIRST_MB_CARRIES) X(Q_ROW_LATER_MB_CARRIES) X(Q_ROW_NO_CARRIER) \
+    X(Q_GOM_PLUS2) X(Q_GOM_PLUS1) X(Q_GOM_ZERO) X(Q_GOM_MINUS1) X(Q_GOM_CLIP_MAX) X(Q_GOM_CLIP_MIN) \
+    /* geometry */ \
+    BR_GEO(X, JUDGE) BR_GEO(X, SKIP) BR_GEO(X, DOUBLE) BR_GEO(X, INTRA) BR_GEO(X, SEARCH) BR_GEO(X, SUBPEL) BR_GEO(X, CODED)
+#define BR_ENUM(n) BR_##n,
+enum { BRANCH_CLASSES(BR_ENUM) BR_COUNT };
+#define BR_NAME(n) #n,
+static const char *const BR_NAMES[BR_COUNT] = {BRANCH_CLASSES(BR_NAME)};
+#define BR_WORDS ((BR_COUNT + 63) / 64)
+static void br_hit(H264OEnc *e, int c) {
+    e->br[c]++;
+    e->mbbr[(size_t)e->br_mb * BR_WORDS + (c >> 6)] |= (uint64_t)1 << (c & 63);
+}
+static void br_geo(H264OEnc *e, int family_first, int mbx, int mby) {
+    if (e->mbw == 1) br_hit(e, family_first);
+    if (e->mbh == 1) br_hit(e, family_first + 1);
+    if (mbx == 0) br_hit(e, family_first + 2);
+    if (mbx == e->mbw - 1) br_hit(e, family_first + 3);
+    if (mby == 0) br_hit(e, family_first + 4);
+}
+int h264o_enc_branch_classes(void) { return BR_COUNT; }
+const char *h264o_enc_branch_name(int c) { return c >= 0 && c < BR_COUNT ? BR_NAMES[c] : NULL; }
+int h264o_enc_branch_words(void) { return BR_WORDS; }
+void h264o_enc_branch_counts(const H264OEnc *e, int64_t *out) { memcpy(out, e->br, BR_COUNT * sizeof(int64_t)); }
+void h264o_enc_mb_branches(const H264OEnc *e, uint64_t *out) {
+    memcpy(out, e->mbbr, (size_t)e->mbw * e->mbh * BR_WORDS * sizeof(uint64_t));
+}
 
 /* ---------------- rate control ---------------- */
 /* musl logf as h264.wasm func 483 computes it (RcConvertQStep2Qp's log): table-driven, in double, no FMA
@@ -335,6 +403,7 @@ static void rc_picture_init(Rc *rc, int idr, int w, int h) {
  * bits over the GOMs left by their complexity. Returns the MB's QP. I slices (bEnableGomQp 0 in RC_BITRATE_MODE,
  * 766730-766775): the frame QP. */
 static int rc_mb_init_gom(Rc *rc, int mb, int idr) {
+    rc->gom_step = 99;
     if (idr) return rc->global_qp;
     if (mb % rc->mb_per_gom == 0) {
         if (mb != 0) {  /* iStartMbSlice 0 */
@@ -348,6 +417,7 @@ static int rc_mb_init_gom(Rc *rc, int mb, int idr) {
                     if (ratio >= 8409) d = ratio < 9439 ? 1 : -(ratio > 10600);
                 }
             }
+            rc->gom_step = d; rc->gom_unclipped = rc->calc_qp + d;
             rc->calc_qp = clip3(rc->min_frame_qp, rc->max_frame_qp, rc->calc_qp + d);
             rc->gom_bits_slice = 0;
         }
@@ -693,6 +763,9 @@ static void encode_chroma(H264OEnc *e, MBInfo *mb, int mbx, int mby, uint8_t pre
     }
     int cbpc = any_ac ? 2 : (any_dc ? 1 : 0);
     mb->cbp = (mb->cbp & 15) | (cbpc << 4);
+    br_hit(e, intra ? BR_R_QUANT_INTRA : BR_R_QUANT_INTER);
+    br_hit(e, intra ? BR_R_CHROMA_DC_INTRA : BR_R_CHROMA_DC_INTER);
+    br_hit(e, (intra ? BR_R_CBPC_0_INTRA : BR_R_CBPC_0_INTER) + cbpc);
     for (int pl = 0; pl < 2; pl++) {
         int dc[4];
         chroma_dc_dequant(mb->cdc[pl], qpc, dc);
@@ -772,6 +845,9 @@ static void encode_i16(H264OEnc *e, MBInfo *mb, int mbx, int mby, int mode, cons
     }
     for (int k = 0; k < 16; k++) mb->lumadc[k] = (int16_t)quant_dc4(f[ZIGZAG4[k]], qp, 1);
     mb->cbp = any_ac ? 15 : 0;
+    br_hit(e, BR_R_QUANT_INTRA);
+    br_hit(e, BR_R_I16_LUMA_DC);
+    br_hit(e, any_ac ? BR_R_I16_AC_SET : BR_R_I16_AC_CLEAR);
     int dc[16];
     luma_dc_dequant(mb->lumadc, qp, dc);
     for (int ras = 0; ras < 16; ras++) {
@@ -871,9 +947,12 @@ static void encode_intra_mb(H264OEnc *e, MBInfo *mb, int mbx, int mby) {
     uint8_t *dst = e->rec[0] + mby * 16 * e->cw + mbx * 16;
     const int flags = mb_nb_flags(mbx, mby, e->mbw);
     int won = 0;
-    if (h264o_vaa_intra_var(src, e->cw) > OH_VAA_I4_THRESHOLD) {
+    const int ib = e->br_pslice ? BR_IP_VAA_BELOW : BR_II_VAA_BELOW;  /* the six BR_INTRA classes from here */
+    if (h264o_vaa_intra_var(src, e->cw) <= OH_VAA_I4_THRESHOLD) br_hit(e, ib);
+    else {
         int sum = 0;
         won = 1;
+        br_hit(e, ib + 1);
         for (int blk = 0; blk < 16; blk++) {
             int ras = BLK2RAS[blk], ox = (ras & 3) * 4, oy = (ras >> 2) * 4;
             IntraNb n4;
@@ -891,7 +970,7 @@ static void encode_intra_mb(H264OEnc *e, MBInfo *mb, int mbx, int mby) {
             int bc;
             const int best = h264o_i4_choose(c, ai, &bc);
             sum += bc;
-            if (sum >= c16) { won = 0; break; }
+            if (sum >= c16) { won = 0; br_hit(e, ib + 2); break; }
             pred4x4(&n4, best, p);
             t.i4mode[ras] = (int8_t)best;
             luma_block_levels(src + oy * e->cw + ox, e->cw, p, 4, mb->qp, 1, 0, t.luma[ras]);
@@ -900,14 +979,17 @@ static void encode_intra_mb(H264OEnc *e, MBInfo *mb, int mbx, int mby) {
             idct4_add(coef, dst + oy * e->cw + ox, e->cw, p, 4);
             t.nnz[ras] = (uint8_t)count_nz(t.luma[ras], 16);
         }
-        if (won && sum + OH_I4_MB_OVERHEAD * lam >= c16) won = 0;
+        if (won && sum + OH_I4_MB_OVERHEAD * lam >= c16) { won = 0; br_hit(e, ib + 3); }
     }
+    br_hit(e, won ? ib + 4 : ib + 5);
     if (won) {
         *mb = t;
         int cbp = 0;
         for (int i8 = 0; i8 < 4; i8++)
             for (int i4 = 0; i4 < 4; i4++) if (t.nnz[BLK2RAS[i8 * 4 + i4]]) cbp |= 1 << i8;
         mb->cbp = cbp;
+        br_hit(e, BR_R_QUANT_INTRA);
+        for (int i8 = 0; i8 < 4; i8++) br_hit(e, (cbp >> i8 & 1 ? BR_R_I4_Y0_SET : BR_R_I4_Y0_CLEAR) + i8);
     } else {
         encode_i16(e, mb, mbx, mby, m16, p16);
     }
@@ -945,6 +1027,7 @@ static int inter_levels(H264OEnc *e, MBInfo *mb, int mbx, int mby, const uint8_t
         if (mb->nnz[ras]) { any = 1; cbp |= 1 << (((ras >> 3) << 1) | ((ras & 3) >> 1)); }
     }
     mb->cbp = cbp;
+    for (int i8 = 0; i8 < 4; i8++) br_hit(e, (cbp >> i8 & 1 ? BR_R_P_Y0_SET : BR_R_P_Y0_CLEAR) + i8);
     /* chroma levels + chroma reconstruction with this prediction */
     encode_chroma(e, mb, mbx, mby, pc, 0);
     if (mb->cbp >> 4) any = 1;
@@ -981,9 +1064,9 @@ static int pskip_residual_ok(H264OEnc *e, int mbx, int mby, int qp, const uint8_
         for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) d[4 * y + x] = src[(oy + y) * e->cw + ox + x] - pl[(oy + y) * 16 + ox + x];
         fdct4(d, c);
         for (int k = 0; k < 16; k++) { lv[k] = (int16_t)quant4(c[ZIGZAG4[k]], qp, ZIGZAG4[k], 0); mx = imax(mx, iabs(lv[k])); }
-        if (mx > OH_PSKIP_MAX_LEVEL) return 0;
+        if (mx > OH_PSKIP_MAX_LEVEL) { br_hit(e, BR_J_REJ_LUMA_LEVEL); return 0; }
         if (mx == 1) ctr += h264o_single_ctr(lv);
-        if (ctr > OH_PSKIP_LUMA_CTR_MAX) return 0;
+        if (ctr > OH_PSKIP_LUMA_CTR_MAX) { br_hit(e, BR_J_REJ_LUMA_CTR); return 0; }
     }
     const int qpc = CHROMA_QP[qp], cs = e->cw / 2;
     for (int p = 0; p < 2; p++) {
@@ -997,19 +1080,21 @@ static int pskip_residual_ok(H264OEnc *e, int mbx, int mby, int qp, const uint8_
         }
         const int a = c4[0][0], b = c4[1][0], cc = c4[2][0], dd = c4[3][0];
         if (quant_dc4(a + b + cc + dd, qpc, 0) || quant_dc4(a - b + cc - dd, qpc, 0) || quant_dc4(a + b - cc - dd, qpc, 0) ||
-            quant_dc4(a - b - cc + dd, qpc, 0))
+            quant_dc4(a - b - cc + dd, qpc, 0)) {
+            br_hit(e, BR_J_REJ_CHROMA_DC);
             return 0;
+        }
         int pctr = 0;
         for (int blk = 0; blk < 4; blk++) {
             int16_t lv[16], ac[16];
             int mx = 0;
             for (int k = 0; k < 16; k++) { lv[k] = (int16_t)quant4(c4[blk][ZIGZAG4[k]], qpc, ZIGZAG4[k], 0); mx = imax(mx, iabs(lv[k])); }
-            if (mx > OH_PSKIP_MAX_LEVEL) return 0;
+            if (mx > OH_PSKIP_MAX_LEVEL) { br_hit(e, BR_J_REJ_CHROMA_LEVEL); return 0; }
             if (mx == 1) {
                 for (int k = 0; k < 15; k++) ac[k] = lv[k + 1];
                 ac[15] = 0;
                 pctr += h264o_single_ctr(ac);
-                if (pctr > OH_PSKIP_CHROMA_CTR_MAX) return 0;
+                if (pctr > OH_PSKIP_CHROMA_CTR_MAX) { br_hit(e, BR_J_REJ_CHROMA_CTR); return 0; }
             }
         }
     }
@@ -1086,28 +1171,53 @@ static void encode_p_mb(H264OEnc *e, MBInfo *mb, int mbx, int mby) {
                          (mby > 0 && mbx + 1 < mbw && e->mbs[n - mbw + 1].type == MBT_PSKIP) || ref_skip;
     const int sx = (skmv[0] >> 2) + 16 * mbx, sy = (skmv[1] >> 2) + 16 * mby;
     e->sksad_cur[n] = -1;
+    if (mbx > 0 && e->mbs[n - 1].type == MBT_PSKIP) br_hit(e, BR_J_TRY_LEFT);
+    if (mby > 0 && e->mbs[n - mbw].type == MBT_PSKIP) br_hit(e, BR_J_TRY_TOP);
+    if (mbx > 0 && mby > 0 && e->mbs[n - mbw - 1].type == MBT_PSKIP) br_hit(e, BR_J_TRY_TOPLEFT);
+    if (mby > 0 && mbx + 1 < mbw && e->mbs[n - mbw + 1].type == MBT_PSKIP) br_hit(e, BR_J_TRY_TOPRIGHT);
+    if (ref_skip) br_hit(e, BR_J_TRY_COLOC);
+    if (!try_skip) br_hit(e, BR_J_NOT_TRIED);
+    else {
+        if (sx < OH_PSKIP_MV_MIN) br_hit(e, BR_J_MV_BELOW_XMIN);
+        if (sx > ((16 * mbw) | OH_PSKIP_MV_MAX_LOW)) br_hit(e, BR_J_MV_ABOVE_XMAX);
+        if (sy < OH_PSKIP_MV_MIN) br_hit(e, BR_J_MV_BELOW_YMIN);
+        if (sy > ((16 * e->mbh) | OH_PSKIP_MV_MAX_LOW)) br_hit(e, BR_J_MV_ABOVE_YMAX);
+    }
     if (try_skip && sx >= OH_PSKIP_MV_MIN && sx <= ((16 * mbw) | OH_PSKIP_MV_MAX_LOW) && sy >= OH_PSKIP_MV_MIN &&
         sy <= ((16 * e->mbh) | OH_PSKIP_MV_MAX_LOW)) {
         mc_luma(&rp, mbx * 16, mby * 16, 16, 16, skmv[0], skmv[1], pl, 16);
         mc_chroma(e->ref[1], cs, e->ch / 2, cs, mbx * 8, mby * 8, 8, 8, skmv[0], skmv[1], pc[0], 8);
         mc_chroma(e->ref[2], cs, e->ch / 2, cs, mbx * 8, mby * 8, 8, 8, skmv[0], skmv[1], pc[1], 8);
         const int tsad = sad_mb_pred(e, mbx, mby, pl, pc);
-        const int take = tsad == 0 || tsad < predict_sad_skip(e, mbx, mby) || (ref_skip && tsad < e->sksad_ref[n]) ||
-                         pskip_residual_ok(e, mbx, mby, mb->qp, pl, pc);
+        /* the first reason that holds, in the order the judge asks them */
+        const int why = tsad == 0 ? BR_J_TAKE_SAD_ZERO : tsad < predict_sad_skip(e, mbx, mby) ? BR_J_TAKE_BELOW_PRED_SAD :
+                        (ref_skip && tsad < e->sksad_ref[n]) ? BR_J_TAKE_BELOW_COLOC_SAD :
+                        pskip_residual_ok(e, mbx, mby, mb->qp, pl, pc) ? BR_J_TAKE_RESIDUAL : BR_J_NOT_TAKEN;
+        const int take = why != BR_J_NOT_TAKEN;
+        br_hit(e, why);
+        br_geo(e, BR_G_JUDGE_MBW1, mbx, mby);
         e->stat_skip_tried++;
         if (take) e->sksad_cur[n] = tsad;
     }
     if (e->sksad_cur[n] >= 0) {
         const int keep = mbx > 0 && mby > 0 && mbx + 1 < mbw && e->mbs[n - 1].type == MBT_PSKIP && e->mbs[n - mbw].type == MBT_PSKIP &&
                          e->mbs[n - mbw + 1].type == MBT_PSKIP;
-        if (!keep && i16_cost_oh(e, mbx, mby, lam) < sad_blk(e->src[0] + mby * 16 * e->cw + mbx * 16, e->cw, pl, 16, 16, 16)) {
-            e->sksad_cur[n] = -1;
-            e->stat_intra_p++;
-            encode_intra_mb(e, mb, mbx, mby);
-            return;
+        br_hit(e, keep ? BR_J_KEEP : !(mbx > 0 && mby > 0 && mbx + 1 < mbw) ? BR_J_NOKEEP_PICTURE_EDGE :
+                  e->mbs[n - 1].type != MBT_PSKIP ? BR_J_NOKEEP_LEFT : e->mbs[n - mbw].type != MBT_PSKIP ? BR_J_NOKEEP_TOP : BR_J_NOKEEP_TOPRIGHT);
+        if (!keep) {
+            const int won = i16_cost_oh(e, mbx, mby, lam) < sad_blk(e->src[0] + mby * 16 * e->cw + mbx * 16, e->cw, pl, 16, 16, 16);
+            br_hit(e, won ? BR_IA_AFTER_SKIP_WON : BR_IA_AFTER_SKIP_LOST);
+            if (won) {
+                e->sksad_cur[n] = -1;
+                e->stat_intra_p++;
+                br_geo(e, BR_G_INTRA_MBW1, mbx, mby);
+                encode_intra_mb(e, mb, mbx, mby);
+                return;
+            }
         }
     }
     if (e->sksad_cur[n] >= 0) {  /* P_Skip: the reconstruction is the prediction */
+        br_geo(e, BR_G_SKIP_MBW1, mbx, mby);
         for (int p = 0; p < 2; p++)
             for (int y = 0; y < 8; y++) memcpy(e->rec[1 + p] + (mby * 8 + y) * cs + mbx * 8, pc[p] + 8 * y, 8);
         mb->type = MBT_PSKIP; mb->cbp = 0;
@@ -1123,37 +1233,48 @@ static void encode_p_mb(H264OEnc *e, MBInfo *mb, int mbx, int mby) {
      * a cross search along the full horizontal and vertical lines through the best point */
     /* integer search range: +-16 pel around (0,0) */
     const int xmin = -16, xmax = 16, ymin = -16, ymax = 16;
-    int cand[5][2], ncand = 0;
-    cand[ncand][0] = (mvp[0] + 2) >> 2; cand[ncand][1] = (mvp[1] + 2) >> 2; ncand++;
-    cand[ncand][0] = 0; cand[ncand][1] = 0; ncand++;
+    int cand[5][2], cand_class[5], ncand = 0;
+    cand[ncand][0] = (mvp[0] + 2) >> 2; cand[ncand][1] = (mvp[1] + 2) >> 2; cand_class[ncand] = BR_S_START_MVP; ncand++;
+    cand[ncand][0] = 0; cand[ncand][1] = 0; cand_class[ncand] = BR_S_START_ZERO; ncand++;
     {
         const MBInfo *nb[3] = {mbx > 0 ? &e->mbs[mby * e->mbw + mbx - 1] : NULL, mby > 0 ? &e->mbs[(mby - 1) * e->mbw + mbx] : NULL,
                                mby > 0 ? (mbx + 1 < e->mbw ? &e->mbs[(mby - 1) * e->mbw + mbx + 1]
                                                            : (mbx > 0 ? &e->mbs[(mby - 1) * e->mbw + mbx - 1] : NULL)) : NULL};
+        const int nb_class[3] = {BR_S_START_A, BR_S_START_B, mbx + 1 < e->mbw ? BR_S_START_C : BR_S_START_C_TOPLEFT};
         for (int i = 0; i < 3; i++) {
             const MBInfo *m = nb[i];
             if (m && !mb_is_intra(m->type)) {
-                cand[ncand][0] = (m->mv[0][0] + 2) >> 2; cand[ncand][1] = (m->mv[0][1] + 2) >> 2; ncand++;
+                cand[ncand][0] = (m->mv[0][0] + 2) >> 2; cand[ncand][1] = (m->mv[0][1] + 2) >> 2; cand_class[ncand] = nb_class[i]; ncand++;
             }
         }
     }
-    int bx = 0, by = 0, bc = -1;
+    br_geo(e, BR_G_SEARCH_MBW1, mbx, mby);
+    int bx = 0, by = 0, bc = -1, start = 0;
     for (int i = 0; i < ncand; i++) {
         int cx = clip3(xmin, xmax, cand[i][0]), cy = clip3(ymin, ymax, cand[i][1]);
         int c = sad16_int(e, mbx, mby, cx, cy) + lam * mvbits(4 * cx, 4 * cy, mvp);
-        if (bc < 0 || c < bc) { bc = c; bx = cx; by = cy; if (i >= 2) e->stat_nb_start++; }
+        if (cx != cand[i][0] || cy != cand[i][1]) br_hit(e, BR_S_CAND_CLIPPED);
+        if (bc < 0 || c < bc) { bc = c; bx = cx; by = cy; start = i; if (i >= 2) e->stat_nb_start++; }
     }
+    br_hit(e, cand_class[start]);
     static const int DIA[4][2] = {{0, -1}, {-1, 0}, {1, 0}, {0, 1}};
-    for (int it = 0; it < 32; it++) {
+    int it;
+    for (it = 0; it < 32; it++) {
         int nb = -1, nx = 0, ny = 0;
         for (int k = 0; k < 4; k++) {
             int cx = bx + DIA[k][0], cy = by + DIA[k][1];
+            if (cx < xmin) br_hit(e, BR_S_DIA_EDGE_XMIN);
+            if (cx > xmax) br_hit(e, BR_S_DIA_EDGE_XMAX);
+            if (cy < ymin) br_hit(e, BR_S_DIA_EDGE_YMIN);
+            if (cy > ymax) br_hit(e, BR_S_DIA_EDGE_YMAX);
             if (cx < xmin || cx > xmax || cy < ymin || cy > ymax) continue;
             int c = sad16_int(e, mbx, mby, cx, cy) + lam * mvbits(4 * cx, 4 * cy, mvp);
             if (nb < 0 || c < nb) { nb = c; nx = cx; ny = cy; }
         }
         if (nb >= 0 && nb < bc) { bc = nb; bx = nx; by = ny; } else break;
     }
+    /* it = the moves made; 32: the loop ended on its cap */
+    br_hit(e, it == 0 ? BR_S_DIA_0 : it == 1 ? BR_S_DIA_1 : it < 8 ? BR_S_DIA_2_7 : it < 32 ? BR_S_DIA_8_31 : BR_S_DIA_CAP);
     if (bc > CROSS_THR) {  /* horizontal line (x ascending), then vertical line (y ascending) */
         int cbx = bx, cby = by, cbc = bc;
         for (int k = 0; k < 66; k++) {
@@ -1163,27 +1284,44 @@ static void encode_p_mb(H264OEnc *e, MBInfo *mb, int mbx, int mby) {
         }
         e->stat_cross++;
         if (cbx != bx || cby != by) e->stat_cross_moved++;
+        br_hit(e, cbx != bx ? BR_S_CROSS_MOVED_H : cby != by ? BR_S_CROSS_MOVED_V : BR_S_CROSS_STAYED);
         bc = cbc; bx = cbx; by = cby;
-    }
+    } else br_hit(e, BR_S_CROSS_OFF);
+    if (bx == xmin) br_hit(e, BR_S_FINAL_XMIN);
+    if (bx == xmax) br_hit(e, BR_S_FINAL_XMAX);
+    if (by == ymin) br_hit(e, BR_S_FINAL_YMIN);
+    if (by == ymax) br_hit(e, BR_S_FINAL_YMAX);
     /* 3. WelsMdFirstIntraMode (func 747, called first by WelsMdInterSecondaryModesEnc, func 399): the MB is coded intra
      * when its I16x16 cost (pinned SAD rule) is below the integer search's cost (here this project's search: SAD +
      * lambda x mvd bits) -- I16x16, or Intra4x4 by the VAA-gated search; before the sub-pel refinement, as OpenH264 */
     if (i16_cost_oh(e, mbx, mby, lam) < bc) {
         e->stat_intra_p++;
+        br_hit(e, BR_IA_AFTER_SEARCH_WON);
+        br_geo(e, BR_G_INTRA_MBW1, mbx, mby);
         encode_intra_mb(e, mb, mbx, mby);
         return;
     }
+    br_hit(e, BR_IA_AFTER_SEARCH_LOST);
     /* 4. half then quarter refinement by SATD */
     static const int SUB[8][2] = {{0, -1}, {0, 1}, {-1, 0}, {1, 0}, {-1, -1}, {1, -1}, {-1, 1}, {1, 1}};
     int mx = 4 * bx, my = 4 * by;
     int sc = subpel_cost(e, mbx, mby, mx, my, mvp, lam);
     for (int step = 2; step >= 1; step--) {
-        int cx0 = mx, cy0 = my;
+        int cx0 = mx, cy0 = my, winner = 0;  /* 0 none, 1 + k: SUB[k], the order of BR_NB9 */
         for (int k = 0; k < 8; k++) {
             int cx = cx0 + step * SUB[k][0], cy = cy0 + step * SUB[k][1];
             int c = subpel_cost(e, mbx, mby, cx, cy, mvp, lam);
-            if (c < sc) { sc = c; mx = cx; my = cy; }
+            if (c < sc) { sc = c; mx = cx; my = cy; winner = 1 + k; }
         }
+        br_hit(e, (step == 2 ? BR_SP_HALF_NONE : BR_SP_QUARTER_NONE) + winner);
+    }
+    if (mx != 4 * bx || my != 4 * by) br_geo(e, BR_G_SUBPEL_MBW1, mbx, mby);
+    {   /* the prediction block (one more sample where the vector is fractional) against the picture */
+        const int x0 = mbx * 16 + (mx >> 2), y0 = mby * 16 + (my >> 2);
+        if (x0 < 0) br_hit(e, BR_S_REF_OUT_LEFT);
+        if (x0 + 15 + ((mx & 3) != 0) > e->cw - 1) br_hit(e, BR_S_REF_OUT_RIGHT);
+        if (y0 < 0) br_hit(e, BR_S_REF_OUT_TOP);
+        if (y0 + 15 + ((my & 3) != 0) > e->ch - 1) br_hit(e, BR_S_REF_OUT_BOTTOM);
     }
     /* 5. P16x16 */
     mb->type = MBT_P16x16;
@@ -1206,7 +1344,10 @@ static void encode_p_mb(H264OEnc *e, MBInfo *mb, int mbx, int mby) {
         mb->type = MBT_PSKIP;
         e->sksad_cur[n] = sad_mb_pred(e, mbx, mby, pl, pc);
         e->stat_skip_double++;
-    }
+        br_hit(e, BR_J_DOUBLE_CHECK);
+        br_geo(e, BR_G_DOUBLE_MBW1, mbx, mby);
+    } else if (mb->cbp == 0) br_hit(e, BR_R_P16_CBP_ZERO_KEPT);
+    else br_geo(e, BR_G_CODED_MBW1, mbx, mby);
 }
 
 /* ---------------- macroblock_layer() writer (7.3.5) ---------------- */
@@ -1288,6 +1429,8 @@ H264OEnc *h264o_enc_create(int w, int h, int bitrate) {
     e->sksad_cur = (int32_t *)malloc((size_t)e->mbw * e->mbh * sizeof(int32_t));
     e->sksad_ref = (int32_t *)malloc((size_t)e->mbw * e->mbh * sizeof(int32_t));
     for (int i = 0; i < e->mbw * e->mbh; i++) e->sksad_cur[i] = e->sksad_ref[i] = -1;
+    e->br = (int64_t *)calloc(BR_COUNT, sizeof(int64_t));
+    e->mbbr = (uint64_t *)calloc((size_t)e->mbw * e->mbh * BR_WORDS, sizeof(uint64_t));
     e->rc.gom_sad = (uint32_t *)calloc((size_t)e->mbw * e->mbh, sizeof(uint32_t));
     e->rc.gom_trace = (int32_t *)calloc(4 * (size_t)e->mbw * e->mbh, sizeof(int32_t));
     rc_init(&e->rc, w, h, bitrate);  /* frame skipping on: the wrapper leaves bEnableFrameSkip at its default */
@@ -1299,7 +1442,7 @@ void h264o_enc_destroy(H264OEnc *e) {
     if (!e) return;
     for (int p = 0; p < 3; p++) { free(e->src[p]); free(e->rec[p]); free(e->ref[p]); }
     free(e->prev_src); free(e->rc.gom_sad); free(e->rc.gom_trace);
-    free(e->mbs); free(e->rowqp); free(e->rowbits); free(e->sksad_cur); free(e->sksad_ref); free(e);
+    free(e->mbs); free(e->rowqp); free(e->rowbits); free(e->sksad_cur); free(e->sksad_ref); free(e->br); free(e->mbbr); free(e);
 }
 /* bEnableFrameSkip (on by default, as the wrapper leaves it): off, no frame is skipped, the VBV check is not
  * made, and an exhausted VGOP budget raises the QP instead (BITS_EXCEEDED) */
@@ -1395,14 +1538,29 @@ int h264o_enc_encode(H264OEnc *e, const uint8_t *yuv, uint8_t *out, int cap) {
      * mb_qp_delta (I16, or coded_block_pattern != 0) moves the running QP there; any other MB's
      * QPY is the running QP (7.4.5) */
     int skip_run = 0, running = qp;
+    memset(e->mbbr, 0, (size_t)e->mbw * e->mbh * BR_WORDS * sizeof(uint64_t));
+    e->br_pslice = !idr;
     for (int mby = 0; mby < e->mbh; mby++) {
         /* this project's row plan: P rows at the frame QP + the row's offset inside the frame's window; an IDR
          * is coded at the frame QP (OpenH264 turns the GOM QP off for I slices in RC_BITRATE_MODE) */
         const int qplan = idr ? qp : clip3(rc->min_frame_qp, rc->max_frame_qp, qp + e->rowqp[mby]);
         e->rowbits[mby] = 0;
+        int carrier = -1;  /* the row's first MB that carries mb_qp_delta */
+        e->br_mb = mby * e->mbw;
+        if (!idr && !e->gom_exact) {  /* the row's classes go to its first MB's record */
+            br_hit(e, e->rowqp[mby] == 2 ? BR_Q_ROW_PLUS2 : e->rowqp[mby] == 1 ? BR_Q_ROW_PLUS1 : e->rowqp[mby] == 0 ? BR_Q_ROW_ZERO : BR_Q_ROW_MINUS1);
+            if (qp + e->rowqp[mby] > rc->max_frame_qp) br_hit(e, BR_Q_ROW_CLIP_MAX);
+            if (qp + e->rowqp[mby] < rc->min_frame_qp) br_hit(e, BR_Q_ROW_CLIP_MIN);
+        }
         for (int mbx = 0; mbx < e->mbw; mbx++) {
             MBInfo *mb = &e->mbs[mby * e->mbw + mbx];
             const int qrow = e->gom_exact ? rc_mb_init_gom(rc, mby * e->mbw + mbx, idr) : qplan;
+            e->br_mb = mby * e->mbw + mbx;
+            if (e->gom_exact && rc->gom_step != 99) {
+                br_hit(e, rc->gom_step == 2 ? BR_Q_GOM_PLUS2 : rc->gom_step == 1 ? BR_Q_GOM_PLUS1 : rc->gom_step == 0 ? BR_Q_GOM_ZERO : BR_Q_GOM_MINUS1);
+                if (rc->gom_unclipped > rc->max_frame_qp) br_hit(e, BR_Q_GOM_CLIP_MAX);
+                if (rc->gom_unclipped < rc->min_frame_qp) br_hit(e, BR_Q_GOM_CLIP_MIN);
+            }
             memset(mb, 0, sizeof(*mb));
             mb->qp = qrow;
             for (int i = 0; i < 16; i++) mb->i4mode[i] = 2;
@@ -1412,6 +1570,7 @@ int h264o_enc_encode(H264OEnc *e, const uint8_t *yuv, uint8_t *out, int cap) {
             const int carries = mb->type == MBT_I16 || (mb->type != MBT_PSKIP && mb->cbp != 0);
             const int dqp = carries ? qp_delta_wrap(qrow, running) : 0;
             if (carries) running = qrow;
+            if (carries && carrier < 0) carrier = mbx;
             mb->qp = running;
             if (mb->type == MBT_PSKIP) { skip_run++; rc_mb_update(rc, 0, running); continue; }
             const int64_t bs = bw_bits(&b);
@@ -1420,6 +1579,10 @@ int h264o_enc_encode(H264OEnc *e, const uint8_t *yuv, uint8_t *out, int cap) {
             write_mb(&b, e, mb, mbx, mby, !idr, dqp);
             e->rowbits[mby] += bw_bits(&b) - b0;
             rc_mb_update(rc, (int)(bw_bits(&b) - bs), running);
+        }
+        if (!idr && !e->gom_exact) {
+            e->br_mb = mby * e->mbw;
+            br_hit(e, carrier == 0 ? BR_Q_ROW_FIRST_MB_CARRIES : carrier > 0 ? BR_Q_ROW_LATER_MB_CARRIES : BR_Q_ROW_NO_CARRIER);
         }
     }
     if (skip_run) bw_ue(&b, (uint32_t)skip_run);

@@ -19,6 +19,10 @@ class Oracle:
         L.h264o_enc_set_frame_skip.argtypes = [vp, ctypes.c_int]
         L.h264o_enc_frames_skipped.argtypes = [vp]
         L.h264o_enc_me_stats.argtypes = [vp, vp]
+        L.h264o_enc_branch_name.restype = ctypes.c_char_p
+        L.h264o_enc_branch_name.argtypes = [ctypes.c_int]
+        L.h264o_enc_branch_counts.argtypes = [vp, vp]
+        L.h264o_enc_mb_branches.argtypes = [vp, vp]
         L.h264o_rc_init_qp.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.h264o_rc_qstep2qp.argtypes = [ctypes.c_int32]
         L.h264o_logf.argtypes = [ctypes.c_float]
@@ -46,6 +50,10 @@ class Oracle:
 
     def encoder(self, w, h, br):
         return OEnc(self.L, w, h, br)
+
+    def branch_names(self):
+        """the encoder's decision-branch classes, in table order (h264o_enc_branch_name)"""
+        return [self.L.h264o_enc_branch_name(c).decode() for c in range(self.L.h264o_enc_branch_classes())]
 
     def decoder(self):
         return ODec(self.L)
@@ -100,6 +108,26 @@ class OEnc:
         out = (ctypes.c_int32 * (4 * max(G, 1)))()
         self.L.h264o_enc_gom_state(self.e, out, 4 * G)
         return [list(out[4 * g:4 * g + 4]) for g in range(G)]
+
+    def branch_counts(self):
+        """how often each decision-branch class was taken since creation (h264o_enc_branch_counts)"""
+        out = np.zeros(self.L.h264o_enc_branch_classes(), np.int64)
+        self.L.h264o_enc_branch_counts(self.e, out.ctypes.data)
+        return out
+
+    def mb_branches(self):
+        """per MB of the last coded frame, the indices of the classes it took (h264o_enc_mb_branches)"""
+        nw, nmb = self.L.h264o_enc_branch_words(), ((self.w + 15) // 16) * ((self.h + 15) // 16)
+        out = np.zeros(nmb * nw, np.uint64)
+        self.L.h264o_enc_mb_branches(self.e, out.ctypes.data)
+        bits = np.unpackbits(out.view(np.uint8).reshape(nmb, nw * 8), axis=1, bitorder='little')
+        return [np.flatnonzero(r).tolist() for r in bits]
+
+    def mbinfo(self):
+        """int32 [MBs, 8] of the last coded frame: type, QP, cbp, mvx, mvy, I16 mode, chroma mode, TotalCoeff sum"""
+        out = np.zeros(((self.w + 15) // 16) * ((self.h + 15) // 16) * 8, np.int32)
+        self.L.h264o_enc_mbinfo(self.e, out.ctypes.data)
+        return out.reshape(-1, 8)
 
     def recon(self):
         out = np.zeros(self.w * self.h * 3 // 2, np.uint8)

@@ -13,6 +13,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import encaudit
+
 W, H, N = 352, 288, 8
 
 # name, bitrate, content
@@ -100,11 +102,12 @@ def test_gpu_encode_decode_extremes(gpu_lib, oracle, case):
     sz = ctypes.c_int(0)
     out = np.zeros(W * H * 3 // 2, np.uint8)
     gw, gh = ctypes.c_int(-1), ctypes.c_int(-1)
+    ex = encaudit.Explainer(oracle, oe, name)  # a mismatch names the first differing macroblock
     for t, f in enumerate(content_frames(kind)):
         L.encode_frame_yuv_i420(f.ctypes.data, W, H, ctypes.byref(p), ctypes.byref(sz))
         got = ctypes.string_at(p, sz.value) if sz.value > 0 else b''
         ref = oe.encode(f)
-        assert got == ref, f'{name} frame {t}: GPU {len(got)} B vs oracle {len(ref)} B'
+        ex.check(t, got, ref)
         if not ref:  # frame skipped by both rate controls
             continue
         _, pic, _, _ = od.decode(ref)

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import encaudit
 from golden.make_golden import CASES, case_inputs
 
 pytestmark = pytest.mark.gpu
@@ -33,13 +34,14 @@ def test_encoder_matches_oracle_and_fixture(gpu_lib, oracle, case):
     frames, rgbas = case_inputs(oracle, w, h, n, kind)
     assert L.init_encoder(w, h, br) == 0
     oe = oracle.encoder(w, h, br)
+    ex = encaudit.Explainer(oracle, oe, name)  # a mismatch names the first differing macroblock
     for t in range(n):
         if force_every and t % force_every == 0 and t > 0:
             L.force_key_frame()
             oe.force_idr()
         got = gpu_encode(L, frames[t], w, h, rgbas[t] if rgbas is not None else None)
         ref = oe.encode(frames[t])
-        assert got == ref, f'{name} frame {t}: GPU {len(got)} B vs oracle {len(ref)} B'
+        ex.check(t, got, ref)
         if not ref:  # skipped by both rate controls
             assert FX[name]['nal_sha256'][t] is None
             continue
