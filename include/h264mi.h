@@ -564,6 +564,77 @@ int h264mi_i420_orient_dev(void *d_dst, const void *d_src, int sw, int sh, int n
    of odd width or height, or frames that overlap the encoder's input area. */
 int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orient);
 
+/* Pixel formats and pitched layouts on the device: frames as a hardware decoder or a capture card
+   leaves them (NV12 with a pitch wider than the picture and the chroma plane on an aligned row), a webcam (YUY2, UYVY),
+   an Android camera (NV21), or planar I420 with a linesize that is not the width. 8 bits a sample, w and h even.
+     pix   planes and rows (row bytes x rows)
+     I420  0: Y  w x h        1: Cb  w/2 x h/2      2: Cr  w/2 x h/2
+     NV12  0: Y  w x h        1: w x h/2, byte 2i = Cb[i], byte 2i+1 = Cr[i]
+     NV21  0: Y  w x h        1: w x h/2, byte 2i = Cr[i], byte 2i+1 = Cb[i]
+     YUY2  0: 2w x h, sample pair k of a row at bytes 4k .. 4k+3 = Y[2k] Cb[k] Y[2k+1] Cr[k]
+     UYVY  0: 2w x h, bytes 4k .. 4k+3 = Cb[k] Y[2k] Cr[k] Y[2k+1]
+   Row y of plane p of frame f starts at base + f * frame_stride + offset[p] + y * pitch[p].
+   The conversions, against tight I420 (what every other call of this library takes):
+     I420, NV12, NV21       samples are moved, never computed
+     YUY2, UYVY -> I420     luma is moved; C420[y][x] = (C422[2y][x] + C422[2y+1][x] + 1) >> 1 for Cb and for Cr
+     I420 -> YUY2, UYVY     luma is moved; C422[y][x] = C420[y >> 1][x]
+   so I420 -> any format -> I420 is the identity, and YUY2 -> I420 -> YUY2 is the identity exactly on frames whose chroma
+   rows 2y and 2y+1 are equal. No colour matrix, range change or chroma siting filter is involved. Bytes that the layout
+   does not name -- pitch padding, the gaps between planes and between frames -- are never written. */
+#define H264MI_PIX_I420 0   /* planes Y (w x h), Cb, Cr (w/2 x h/2) */
+#define H264MI_PIX_NV12 1   /* plane 0 Y; plane 1: h/2 rows of w bytes, byte 2i = Cb[i], 2i+1 = Cr[i] */
+#define H264MI_PIX_NV21 2   /* as NV12 with Cr first */
+#define H264MI_PIX_YUY2 3   /* one plane, h rows of 2w bytes: Y0 Cb Y1 Cr */
+#define H264MI_PIX_UYVY 4   /* one plane: Cb Y0 Cr Y1 */
+typedef struct h264mi_pix_layout {
+    int32_t pix;            /* H264MI_PIX_* */
+    int32_t pitch[3];       /* bytes between rows of plane p; entries of unused planes are 0 */
+    int64_t offset[3];      /* plane p of frame f starts at base + f * frame_stride + offset[p] */
+    int64_t frame_stride;   /* bytes between frames */
+} h264mi_pix_layout;
+/* host only: *out = the tight layout of a w x h frame: pitch = row bytes, the planes back to back from offset 0,
+   frame_stride = the span; for H264MI_PIX_I420 the library's tight I420. Returns 0, or -1 -- nothing written -- on a
+   null pointer, an unknown format, or a side that is odd or outside 2..8192 */
+int h264mi_pix_layout_tight(h264mi_pix_layout *out, int pix, int w, int h);
+/* host only: the bytes from a frame's base to one past the last byte the layout names, the largest
+   offset[p] + (rows - 1) * pitch[p] + row bytes. -1 on a layout that breaks any rule below but the frame_stride one
+   (which the span does not read) */
+int64_t h264mi_pix_span(const h264mi_pix_layout *layout, int w, int h);
+/* host only: 0 when the layout can hold w x h frames, else -1. All of: pix is a known format; w and h are even and
+   within 2..8192; every used plane has row bytes <= pitch <= 65536 and offset >= 0; every entry of an unused plane is
+   0; no two planes of a frame share a byte, a plane's bytes being offset .. offset + (rows - 1) * pitch + row bytes
+   (pitch padding between its rows included); the span fits int64 and frame_stride >= span. */
+int h264mi_pix_layout_ok(const h264mi_pix_layout *layout, int w, int h);
+/* async on hip_stream, one launch each: n frames in *src at d_src to n tight I420 frames at d_i420, and n tight I420
+   frames at d_i420 to n frames in *dst at d_dst (any alignment on both sides: 16-byte accesses where a plane's rows
+   allow them, bytes otherwise, the same result). The same bytes from run to run, equal to a restatement of the table
+   above on any host. Return 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer,
+   n <= 0, a layout that h264mi_pix_layout_ok refuses for w x h, or source and destination byte ranges that overlap
+   (n * frame_stride bytes on the layout's side, n tight frames on the other). */
+int h264mi_pix_to_i420_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, int w, int h, int n, void *hip_stream);
+int h264mi_i420_to_pix_dev(void *d_dst, const h264mi_pix_layout *dst, const void *d_i420, int w, int h, int n, void *hip_stream);
+/* async, as h264mi_enc_encode_oriented, from nstreams frames of the encoder's width x height in *layout at d_frames
+   (device; frame s at d_frames + s * frame_stride): one batched launch (h264mi_pix_to_i420_dev) into the encoder's
+   input area on its stream; then an overlay list in force is blended, then the same frame step -- rate control,
+   slices, exact GOM, inject_error and the quality records as in h264mi_enc_encode. With the tight I420 layout the NAL
+   bytes are those of h264mi_enc_encode on the same frames. Returns -1 and enqueues nothing on a null pointer, a layout
+   that h264mi_pix_layout_ok refuses for the encoder's size (an encoder of odd width or height included), or frames
+   whose nstreams * frame_stride bytes overlap the encoder's input area. */
+int h264mi_enc_encode_pix(h264mi_encoder *e, const void *d_frames, const h264mi_pix_layout *layout);
+/* what h264mi_dec_decode_frames_out writes to d_out, beyond the two formats: with a layout set, frame f's cropped
+   picture goes to d_out[f * nstreams + s] in that layout (frame_stride is checked but unused: every d_out entry is a
+   frame's base), converted straight from the deblocked picture; d_got, "left untouched when no picture" and "each
+   call captures its setting" are as for the formats. The layout is checked against the width x height the decoder
+   was created with when it is set (-1 and nothing changes on one that h264mi_pix_layout_ok refuses); a picture whose
+   cropped size differs from that is reported in d_got but not written. The last setter wins: a layout replaces the
+   format, h264mi_dec_set_output_format (which accepts H264MI_FMT_I420 and H264MI_FMT_RGBA only, as before) clears
+   the layout, and NULL clears it too, back to the format set last. h264mi_dec_output_format reports
+   H264MI_FMT_LAYOUT while a layout is in effect. h264mi_dec_output_layout: 1 and the layout copied to *out when one
+   is set, 0 when none is, -1 on a null pointer. */
+#define H264MI_FMT_LAYOUT 2   /* what h264mi_dec_output_format reports while a layout is in effect */
+int h264mi_dec_set_output_layout(h264mi_decoder *d, const h264mi_pix_layout *layout);  /* NULL: back to the format */
+int h264mi_dec_output_layout(h264mi_decoder *d, h264mi_pix_layout *out);              /* 1 set (copied to out), 0 not set, -1 bad d */
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -162,6 +162,7 @@ h264mi_decoder *h264mi_dec_create_ring(int width, int height, int nstreams, int 
                                        void *hip_stream) {
     if (width <= 0 || height <= 0 || groups < 0 || groups == 1) return nullptr;
     DecCtx *c = dec_create((width + 15) / 16, (height + 15) / 16, nstreams, (hipStream_t)hip_stream, max_frames, groups, parse_streams);
+    if (c) { c->w = width; c->h = height; }
     return c ? new h264mi_decoder{c} : nullptr;
 }
 static size_t dec_bytes(const DecCtx *c) { return c ? c->pool_bytes + c->nal_cap + c->rgba_cap + c->tight_cap : 0; }
@@ -176,12 +177,13 @@ int h264mi_dec_decode_frames_out(h264mi_decoder *d, int nframes, const void *con
     if (!d || !d_nal || (!nal_bytes && !d_sizes) || nframes <= 0 || nframes > d->c->B || nevents < 0 ||
         (nevents > 0 && !ready_events)) return -1;
     std::vector<DecInput> in((size_t)nframes * d->c->S);
+    const int fmt = d->c->out_lay_set ? H264MI_FMT_LAYOUT : d->c->out_fmt;
     for (size_t i = 0; i < in.size(); i++) {
-        if (d_out && d->c->out_fmt == H264MI_FMT_RGBA && ((uintptr_t)d_out[i] & 3)) return -1;  // RGBA pixels are stored as dwords
+        if (d_out && fmt == H264MI_FMT_RGBA && ((uintptr_t)d_out[i] & 3)) return -1;  // RGBA pixels are stored as dwords
         in[i].nal = (const uint8_t *)d_nal[i];
         in[i].size = nal_bytes ? nal_bytes[i] : 0;
         in[i].size_dev = d_sizes ? (const int32_t *)d_sizes[i] : nullptr;
-        in[i].fmt = d->c->out_fmt;
+        in[i].fmt = fmt;
         in[i].out = d_out ? (uint8_t *)d_out[i] : nullptr;
         in[i].got = d_got ? (int32_t *)d_got[i] : nullptr;
     }
@@ -221,9 +223,26 @@ int h264mi_dec_streamed(h264mi_decoder *d) { return d ? d->c->streamed : 0; }
 int h264mi_dec_set_output_format(h264mi_decoder *d, int fmt) {
     if (!d || (fmt != H264MI_FMT_I420 && fmt != H264MI_FMT_RGBA)) return -1;
     d->c->out_fmt = fmt;
+    d->c->out_lay_set = false;  // the last setter wins
     return 0;
 }
-int h264mi_dec_output_format(h264mi_decoder *d) { return d ? d->c->out_fmt : -1; }
+int h264mi_dec_output_format(h264mi_decoder *d) { return d ? (d->c->out_lay_set ? H264MI_FMT_LAYOUT : d->c->out_fmt) : -1; }
+// a layout instead of a format (DESIGN.md §5.10; pixfmt.hip dec_output_pix_kernel), checked here against the size the
+// decoder was created with; each call hands the layout in force to its read-out launches by value (dec_frames)
+int h264mi_dec_set_output_layout(h264mi_decoder *d, const h264mi_pix_layout *layout) {
+    if (!d) return -1;
+    if (!layout) { d->c->out_lay_set = false; return 0; }
+    if (!pix_layout_ok(layout, d->c->w, d->c->h)) return -1;
+    d->c->out_lay = *layout;
+    d->c->out_lay_set = true;
+    return 0;
+}
+int h264mi_dec_output_layout(h264mi_decoder *d, h264mi_pix_layout *out) {
+    if (!d) return -1;
+    if (!d->c->out_lay_set) return 0;
+    if (out) *out = d->c->out_lay;
+    return 1;
+}
 int h264mi_dec_set_recon_gate(h264mi_decoder *d, const uint32_t *d_counter, uint32_t target, uint32_t step, int count, int limit_us) {
     if (!d || count < 0 || limit_us < 0 || limit_us > 1000000) return -1;
     DecCtx *c = d->c;

@@ -282,6 +282,27 @@ int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orie
     if (launch_orient_i420(c->d_src, (const uint8_t *)d_frames, sw, sh, c->S, orient, c->stream) != 0) return -1;
     return enc_code_input(c);
 }
+// Pixel formats and pitched layouts (DESIGN.md §5.10; pixfmt.hip; the rules: picture_host.h): n frames, one launch
+int h264mi_pix_layout_tight(h264mi_pix_layout *out, int pix, int w, int h) { return pix_layout_tight(out, pix, w, h); }
+int64_t h264mi_pix_span(const h264mi_pix_layout *layout, int w, int h) { return pix_span(layout, w, h); }
+int h264mi_pix_layout_ok(const h264mi_pix_layout *layout, int w, int h) { return pix_layout_ok(layout, w, h) ? 0 : -1; }
+int h264mi_pix_to_i420_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, int w, int h, int n, void *hip_stream) {
+    if (!d_i420 || !d_src || !pix_args_ok(src, w, h, n) || pix_ranges_overlap(d_src, *src, d_i420, w, h, n)) return -1;
+    return launch_pix_to_i420((uint8_t *)d_i420, (const uint8_t *)d_src, *src, w, h, n, (hipStream_t)hip_stream);
+}
+int h264mi_i420_to_pix_dev(void *d_dst, const h264mi_pix_layout *dst, const void *d_i420, int w, int h, int n, void *hip_stream) {
+    if (!d_dst || !d_i420 || !pix_args_ok(dst, w, h, n) || pix_ranges_overlap(d_dst, *dst, d_i420, w, h, n)) return -1;
+    return launch_i420_to_pix((uint8_t *)d_dst, *dst, (const uint8_t *)d_i420, w, h, n, (hipStream_t)hip_stream);
+}
+// nstreams frames of the encoder's size in *layout: one batched launch into the encoder's own input area on its stream,
+// then the frame step as h264mi_enc_encode runs it. Every refusal comes before the first launch
+int h264mi_enc_encode_pix(h264mi_encoder *e, const void *d_frames, const h264mi_pix_layout *layout) {
+    if (!e || !d_frames) return -1;
+    EncCtx *c = e->c;
+    if (!pix_args_ok(layout, c->w, c->h, c->S) || pix_ranges_overlap(d_frames, *layout, c->d_src, c->w, c->h, c->S)) return -1;
+    if (launch_pix_to_i420(c->d_src, (const uint8_t *)d_frames, *layout, c->w, c->h, c->S, c->stream) != 0) return -1;
+    return enc_code_input(c);
+}
 // Several pictures into one (DESIGN.md §5.4; compose.hip): every cell's crop of a source frame area-averaged into its
 // rectangle of a canvas, 64 cells to a launch
 int h264mi_i420_compose_dev(void *d_canvas, int cw, int ch, int ncanvas, const void *d_src, int src_w, int src_h, int nsrc,

@@ -1,5 +1,5 @@
-// picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip)
-// and the runtime (runtime_enc.inc, capi_enc.inc) share: byte counts, the limits of a call, the checks of a cell
+// picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
+// pixfmt.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold. DESIGN.md §5.8.
@@ -11,6 +11,8 @@
 #include "../../include/h264mi.h"
 
 struct EncDesc;  // h264mi_types.h
+struct DecDesc;
+struct DecInput;
 
 namespace h264mi {
 
@@ -54,6 +56,82 @@ static inline bool rects_share(int ax, int ay, int aw, int ah, int bx, int by, i
 }
 // blocks of four waves for a launch's waves
 static inline unsigned launch_blocks(long long waves) { return (unsigned)std::min((waves + 3) / 4, (long long)PIC_MAX_BLOCKS); }
+
+// ---- pixel formats and pitched layouts (include/h264mi.h)
+constexpr int PIX_MAX_PITCH = 65536;
+// planes of a format, 0 for an unknown one
+static inline int pix_planes(int pix) {
+    switch (pix) {
+    case H264MI_PIX_I420: return 3;
+    case H264MI_PIX_NV12: case H264MI_PIX_NV21: return 2;
+    case H264MI_PIX_YUY2: case H264MI_PIX_UYVY: return 1;
+    default: return 0;
+    }
+}
+// row bytes and rows of plane p < pix_planes(pix) of a w x h frame
+static inline void pix_plane_size(int pix, int p, int w, int h, int *row_bytes, int *rows) {
+    if (pix == H264MI_PIX_YUY2 || pix == H264MI_PIX_UYVY) { *row_bytes = 2 * w; *rows = h; }
+    else if (p == 0) { *row_bytes = w; *rows = h; }
+    else if (pix == H264MI_PIX_I420) { *row_bytes = w / 2; *rows = h / 2; }
+    else { *row_bytes = w; *rows = h / 2; }
+}
+// the span of a layout for w x h frames -- every rule of h264mi_pix_layout_ok but the frame_stride one -- or -1. 64-bit
+// arithmetic that cannot overflow: a plane's extent is at most 8191 * 65536 + 16384 < 2^30, and an offset that would
+// carry its end past INT64_MAX is refused before the sum is formed
+static inline int64_t pix_span(const h264mi_pix_layout *L, int w, int h) {
+    if (!L || !canvas_ok(w, h)) return -1;
+    const int np = pix_planes(L->pix);
+    if (np == 0) return -1;
+    int64_t end[3] = {0, 0, 0}, span = 0;
+    for (int p = 0; p < 3; p++) {
+        if (p >= np) {
+            if (L->pitch[p] != 0 || L->offset[p] != 0) return -1;
+            continue;
+        }
+        int rb, rows;
+        pix_plane_size(L->pix, p, w, h, &rb, &rows);
+        if (L->pitch[p] < rb || L->pitch[p] > PIX_MAX_PITCH || L->offset[p] < 0) return -1;
+        const int64_t extent = (int64_t)(rows - 1) * L->pitch[p] + rb;
+        if (L->offset[p] > INT64_MAX - extent) return -1;
+        end[p] = L->offset[p] + extent;
+        span = std::max(span, end[p]);
+    }
+    for (int p = 1; p < np; p++)
+        for (int q = 0; q < p; q++)
+            if (L->offset[p] < end[q] && L->offset[q] < end[p]) return -1;
+    return span;
+}
+static inline bool pix_layout_ok(const h264mi_pix_layout *L, int w, int h) {
+    const int64_t span = pix_span(L, w, h);
+    return span >= 0 && L->frame_stride >= span;
+}
+static inline int pix_layout_tight(h264mi_pix_layout *out, int pix, int w, int h) {
+    const int np = pix_planes(pix);
+    if (!out || np == 0 || !canvas_ok(w, h)) return -1;
+    h264mi_pix_layout L{};
+    L.pix = pix;
+    int64_t at = 0;
+    for (int p = 0; p < np; p++) {
+        int rb, rows;
+        pix_plane_size(pix, p, w, h, &rb, &rows);
+        L.pitch[p] = rb;
+        L.offset[p] = at;
+        at += (int64_t)rb * rows;
+    }
+    L.frame_stride = at;
+    *out = L;
+    return 0;
+}
+// whether n frames of a good layout at a and n tight w x h I420 frames at b share a byte; a layout side too long for
+// any address space (n * frame_stride beyond 2^63) counts as overlapping
+static inline bool pix_ranges_overlap(const void *a, const h264mi_pix_layout &L, const void *b, int w, int h, int n) {
+    const unsigned __int128 abytes = (unsigned __int128)(uint64_t)L.frame_stride * (unsigned)n;
+    if (abytes >> 63) return true;
+    const unsigned __int128 a0 = (uintptr_t)a, b0 = (uintptr_t)b, bbytes = (unsigned __int128)i420_bytes(w, h) * (unsigned)n;
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+// arguments of a conversion call, everything but the pointers' values
+static inline bool pix_args_ok(const h264mi_pix_layout *L, int w, int h, int n) { return n > 0 && pix_layout_ok(L, w, h); }
 
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
@@ -157,4 +235,9 @@ int orient_size(int orient, int sw, int sh, int *dw, int *dh);
 int orient_compose(int first, int then);
 int orient_inverse(int orient);
 void orient_plane_host(int orient, const uint8_t *S, int pw, int ph, uint8_t *D);
+// pixfmt.hip
+int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
+int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);
+int launch_dec_output_pix(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in, const h264mi_pix_layout &L,
+                          hipStream_t s);
 }  // namespace h264mi

@@ -45,6 +45,9 @@ struct DecCtx {
     uint32_t rg_target = 0, rg_step = 0, rg_limit = 0;
     int rg_count = 0;
     int out_fmt = 0;                    // H264MI_FMT_*: what the next calls write to their d_out buffers
+    int w = 0, h = 0;                   // the size the batch decoder was created with (0: a C-ABI decoder)
+    bool out_lay_set = false;           // a layout instead (h264mi_dec_set_output_layout), good for w x h
+    h264mi_pix_layout out_lay = {};
     // C-ABI staging
     uint8_t *d_nal = nullptr;
     size_t nal_cap = 0;
@@ -297,7 +300,9 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
         if (dec_time_mark(c, 0, c->stream)) return -1;
         if (streamed && f == 0) HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_parsed[g], 0));
         hipLaunchKernelGGL(dec_end_kernel, dim3((S + 63) / 64), dim3(64), 0, c->stream, DecEndLaunch{S, df, streamed});
-        if (outputs && in[0].fmt == H264MI_FMT_RGBA) {  // every frame's picture to the caller (DecInput::out / got)
+        if (outputs && in[0].fmt == H264MI_FMT_LAYOUT) {  // the layout in force travels by value in the launch
+            if (launch_dec_output_pix(S, c->cw, c->ch, c->w, c->h, df, c->d_in + (size_t)(slot0 + f) * S, c->out_lay, c->stream) != 0) return -1;
+        } else if (outputs && in[0].fmt == H264MI_FMT_RGBA) {  // every frame's picture to the caller (DecInput::out / got)
             const dim3 cg = color_grid(c->cw, c->ch, S);
             hipLaunchKernelGGL(dec_output_rgba_kernel, dim3(cg.x, S), dim3(256), 0, c->stream,
                                DecOutLaunch{S, c->cw, c->ch, df, c->d_in + (size_t)(slot0 + f) * S});

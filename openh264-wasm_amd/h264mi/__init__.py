@@ -149,6 +149,14 @@ def lib():
             'h264mi_orient_inverse': (i, [i]),
             'h264mi_i420_orient_dev': (i, [vp, vp, i, i, i, i, vp]),
             'h264mi_enc_encode_oriented': (i, [vp, vp, i]),
+            'h264mi_pix_layout_tight': (i, [vp, i, i, i]),
+            'h264mi_pix_span': (ctypes.c_int64, [vp, i, i]),
+            'h264mi_pix_layout_ok': (i, [vp, i, i]),
+            'h264mi_pix_to_i420_dev': (i, [vp, vp, vp, i, i, i, vp]),
+            'h264mi_i420_to_pix_dev': (i, [vp, vp, vp, i, i, i, vp]),
+            'h264mi_enc_encode_pix': (i, [vp, vp, vp]),
+            'h264mi_dec_set_output_layout': (i, [vp, vp]),
+            'h264mi_dec_output_layout': (i, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -371,6 +379,17 @@ class BatchEncoder:
         assert frames.is_cuda and frames.numel() >= self.S * _i420_bytes(self.w, self.h)
         if self._L.h264mi_enc_encode_oriented(self._e, ctypes.c_void_p(frames.data_ptr()), int(orient)) != 0:
             raise ValueError(f'h264mi_enc_encode_oriented refused orientation {orient} -> {self.w}x{self.h}')
+
+    def encode_pix(self, frames, layout):
+        """frames: uint8 CUDA tensor holding S frames of the encoder's size in `layout` (a PixLayout: NV12, NV21, YUY2,
+        UYVY or pitched I420; frame s at s * layout.frame_stride), any alignment (async): one batched conversion
+        (pix_to_i420) into the encoder's input area on its stream, then an overlay list in force and the frame step
+        of encode(). With pix_layout_tight(PIX_I420, w, h) the NAL bytes are those of encode(). ValueError, with
+        nothing enqueued, for a layout that pix_layout_ok refuses for the encoder's size or frames inside the input area."""
+        _assert_dev_u8(frames)
+        assert pix_layout_ok(layout, self.w, self.h) != 0 or frames.numel() >= (self.S - 1) * layout.frame_stride + pix_span(layout, self.w, self.h)
+        if self._L.h264mi_enc_encode_pix(self._e, ctypes.c_void_p(frames.data_ptr()), ctypes.byref(layout)) != 0:
+            raise ValueError(f'h264mi_enc_encode_pix refused {layout!r} for {self.w}x{self.h}')
 
     def encode_composed(self, src, src_w, src_h, nsrc, cells, bg=(16, 128, 128)):
         """src: uint8 CUDA tensor holding nsrc tight I420 frames of src_w x src_h back to back, any alignment; cells: a
@@ -617,7 +636,8 @@ class BatchDecoder:
         list of them, one per producer stream) is given, after those events only. out_ptrs / got_ptrs
         (device addresses, same indexing): every frame's cropped picture and got flag. An out buffer holds
         w * h * 3 // 2 bytes (tight I420) with the output format 'i420', w * h * 4 bytes (tight RGBA8, 4-byte
-        aligned) with 'rgba' (set_output_format); it is left untouched when got is 0."""
+        aligned) with 'rgba' (set_output_format), pix_span(layout, w, h) bytes with a layout (set_output_layout); it
+        is left untouched when got is 0."""
         m = len(nal_ptrs)
         assert m % self.S == 0 and m // self.S <= self.B
         ptrs = (ctypes.c_void_p * m)(*nal_ptrs)
@@ -638,7 +658,22 @@ class BatchDecoder:
             raise ValueError(f'h264mi_dec_set_output_format({fmt!r}) refused')
 
     def output_format(self):
-        return {v: k for k, v in self.OUTPUT_FORMATS.items()}[self._L.h264mi_dec_output_format(self._d)]
+        """'i420', 'rgba', or 'layout' while a layout is in effect (set_output_layout)"""
+        fmt = self._L.h264mi_dec_output_format(self._d)
+        return 'layout' if fmt == FMT_LAYOUT else {v: k for k, v in self.OUTPUT_FORMATS.items()}[fmt]
+
+    def set_output_layout(self, layout):
+        """what decode_frames writes to out_ptrs from the next call on: every frame's cropped picture in `layout` (a
+        PixLayout checked against the decoder's width x height; frame_stride is unused, every out pointer is a frame's
+        base and must hold pix_span(layout, w, h) bytes), or None: back to the format set last. The last setter
+        wins: set_output_format clears a layout. ValueError, with nothing changed, on a layout pix_layout_ok refuses."""
+        if self._L.h264mi_dec_set_output_layout(self._d, ctypes.byref(layout) if layout is not None else None) != 0:
+            raise ValueError(f'h264mi_dec_set_output_layout refused {layout!r} for {self.w}x{self.h}')
+
+    def output_layout(self):
+        """the layout in effect (a copy), or None"""
+        out = PixLayout()
+        return out if self._L.h264mi_dec_output_layout(self._d, ctypes.byref(out)) == 1 else None
 
     def set_parse_cus(self, lo, hi):
         """entropy decoding on CU mask bits [lo, hi) (see h264mi_dec_set_parse_cus)"""
@@ -952,6 +987,79 @@ def i420_orient(dst, src, sw, sh, n, orient, stream=None):
     if lib().h264mi_i420_orient_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), sw, sh, n, int(orient),
                                     _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: orientation {orient} of {n} frames {sw}x{sh}')
+
+
+PIX_I420 = 0  # H264MI_PIX_*: planes Y (w x h), Cb, Cr (w/2 x h/2)
+PIX_NV12 = 1  # plane 0 Y; plane 1: h/2 rows of w bytes, byte 2i = Cb[i], 2i+1 = Cr[i]
+PIX_NV21 = 2  # as NV12 with Cr first
+PIX_YUY2 = 3  # one plane, h rows of 2w bytes: Y0 Cb Y1 Cr
+PIX_UYVY = 4  # one plane: Cb Y0 Cr Y1
+FMT_LAYOUT = 2  # H264MI_FMT_LAYOUT: what h264mi_dec_output_format reports while a layout is in effect
+
+
+class PixLayout(ctypes.Structure):
+    """h264mi_pix_layout (include/h264mi.h): row y of plane p of frame f starts at
+    base + f * frame_stride + offset[p] + y * pitch[p]; entries of unused planes are 0. 48 bytes"""
+    _fields_ = [('pix', ctypes.c_int32), ('pitch', ctypes.c_int32 * 3), ('offset', ctypes.c_int64 * 3), ('frame_stride', ctypes.c_int64)]
+
+    def __init__(self, pix=0, pitch=(), offset=(), frame_stride=0):
+        super().__init__()
+        self.pix, self.frame_stride = pix, frame_stride
+        for k, v in enumerate(pitch):
+            self.pitch[k] = v
+        for k, v in enumerate(offset):
+            self.offset[k] = v
+
+    def __repr__(self):
+        return f'PixLayout(pix={self.pix}, pitch={list(self.pitch)}, offset={list(self.offset)}, frame_stride={self.frame_stride})'
+
+
+def pix_layout_tight(pix, w, h):
+    """the tight layout of a w x h frame in format pix (PIX_*): pitch = row bytes, planes back to back, frame_stride =
+    the span (h264mi_pix_layout_tight; host only). ValueError on an unknown format or a side that is odd or outside 2..8192."""
+    out = PixLayout()
+    if lib().h264mi_pix_layout_tight(ctypes.byref(out), int(pix), int(w), int(h)) != 0:
+        raise ValueError(f'bad arguments: format {pix} of {w}x{h}')
+    return out
+
+
+def pix_span(layout, w, h):
+    """bytes from a frame's base to one past the last byte the layout names, -1 on a bad layout (h264mi_pix_span; host only)"""
+    return lib().h264mi_pix_span(ctypes.byref(layout), int(w), int(h))
+
+
+def pix_layout_ok(layout, w, h):
+    """0 when the layout can hold w x h frames, else -1 (h264mi_pix_layout_ok; host only)"""
+    return lib().h264mi_pix_layout_ok(ctypes.byref(layout), int(w), int(h))
+
+
+def _pix_fits(t, layout, w, h, n):
+    """tensor t holds n frames of a good layout (a bad one is left to the library to refuse)"""
+    return n <= 0 or pix_layout_ok(layout, w, h) != 0 or t.numel() >= (n - 1) * layout.frame_stride + pix_span(layout, w, h)
+
+
+def pix_to_i420(dst, src, layout, w, h, n, stream=None):
+    """n w x h frames in `layout` (a PixLayout; uint8 CUDA tensor src, frame f at f * layout.frame_stride, any
+    alignment) to n tight I420 frames (dst), one launch, async on stream (default: the current one);
+    h264mi_pix_to_i420_dev. I420, NV12 and NV21 samples are moved; YUY2 and UYVY chroma is (rows 2y + 2y+1 + 1) >> 1:
+    the bytes equal tests/pixref.py's. ValueError on a bad argument (a layout pix_layout_ok refuses, n <= 0,
+    overlapping buffers)."""
+    _assert_dev_u8(dst, src)
+    assert n <= 0 or min(w, h) <= 0 or (dst.numel() >= n * _i420_bytes(w, h) and _pix_fits(src, layout, w, h, n))
+    if lib().h264mi_pix_to_i420_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), ctypes.byref(layout), w, h, n,
+                                    _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {layout!r}, {n} frames {w}x{h}')
+
+
+def i420_to_pix(dst, layout, src, w, h, n, stream=None):
+    """n tight w x h I420 frames (uint8 CUDA tensor src) to n frames in `layout` (dst, any alignment), one launch, async
+    on stream; h264mi_i420_to_pix_dev. 4:2:2 chroma rows 2y and 2y+1 both take chroma row y. Bytes the layout does not
+    name (pitch padding, gaps between planes and frames) are not written. ValueError as pix_to_i420."""
+    _assert_dev_u8(dst, src)
+    assert n <= 0 or min(w, h) <= 0 or (src.numel() >= n * _i420_bytes(w, h) and _pix_fits(dst, layout, w, h, n))
+    if lib().h264mi_i420_to_pix_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.byref(layout), ctypes.c_void_p(src.data_ptr()), w, h, n,
+                                    _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {layout!r}, {n} frames {w}x{h}')
 
 
 class Overlay(ctypes.Structure):

@@ -20,6 +20,9 @@
 //     range test;
 //   * orient.hip's host restatement of a turned plane against the header's table, compose and inverse against planes
 //     turned twice, its sizes and scalar check at their limits.
+//   * the pixel-layout rules (pix_span, pix_layout_ok, pix_layout_tight, pix_ranges_overlap): every verdict and span
+//     against a restatement in 128-bit arithmetic over random fields and extreme ones (INT32_MAX pitches, INT64_MAX
+//     offsets and strides, negative values), and the tight layouts and spans of the five formats against their byte counts.
 // Prints one line per group and "ok"; exits 1 at the first difference.
 #include <cstdio>
 #include <cstdlib>
@@ -303,7 +306,112 @@ static void check_orient() {
     printf("orient: the plane restatement, compose, inverse on 7 sizes, the scalar checks\n");
 }
 
+// the layout rules of include/h264mi.h restated in 128-bit arithmetic, one predicate per rule; the span, or -1
+static __int128 ref_pix_span(const h264mi_pix_layout &L, long long w, long long h) {
+    if (w % 2 || h % 2 || w < 2 || h < 2 || w > 8192 || h > 8192) return -1;
+    __int128 rb[3], rows[3];
+    int np;
+    switch (L.pix) {
+    case 0: np = 3; rb[0] = w; rows[0] = h; rb[1] = rb[2] = w / 2; rows[1] = rows[2] = h / 2; break;
+    case 1: case 2: np = 2; rb[0] = w; rows[0] = h; rb[1] = w; rows[1] = h / 2; break;
+    case 3: case 4: np = 1; rb[0] = 2 * w; rows[0] = h; break;
+    default: return -1;
+    }
+    __int128 lo[3], hi[3], span = 0;
+    for (int p = 0; p < 3; p++) {
+        if (p >= np) {
+            if (L.pitch[p] != 0 || L.offset[p] != 0) return -1;
+            continue;
+        }
+        if (L.pitch[p] < rb[p] || L.pitch[p] > 65536 || L.offset[p] < 0) return -1;
+        lo[p] = L.offset[p];
+        hi[p] = lo[p] + (rows[p] - 1) * L.pitch[p] + rb[p];
+        if (hi[p] > span) span = hi[p];
+    }
+    for (int p = 0; p < np; p++)
+        for (int q = p + 1; q < np; q++)
+            if (lo[p] < hi[q] && lo[q] < hi[p]) return -1;
+    return span > (__int128)INT64_MAX ? (__int128)-1 : span;
+}
+
+static uint64_t pix_rng_state = 0x9E3779B97F4A7C15ull;
+static uint64_t pix_rng() {  // xorshift64
+    pix_rng_state ^= pix_rng_state << 13; pix_rng_state ^= pix_rng_state >> 7; pix_rng_state ^= pix_rng_state << 17;
+    return pix_rng_state;
+}
+
+static void check_pix() {
+    // tight layouts and spans of the five formats: bytes per frame 12 or 16 bits a sample, planes back to back
+    const int sizes[][2] = {{2, 2}, {36, 18}, {1280, 720}, {8192, 8192}, {8192, 2}, {2, 8192}};
+    for (const auto &s : sizes)
+        for (int pix = 0; pix < 5; pix++) {
+            std::unique_ptr<h264mi_pix_layout> L(new h264mi_pix_layout);
+            const long long w = s[0], h = s[1], bytes = pix >= 3 ? 2 * w * h : w * h + 2 * (w / 2) * (h / 2);
+            CHECK(pix_layout_tight(L.get(), pix, s[0], s[1]) == 0);
+            CHECK(L->pix == pix && L->frame_stride == bytes && pix_span(L.get(), s[0], s[1]) == bytes && pix_layout_ok(L.get(), s[0], s[1]));
+            CHECK(ref_pix_span(*L, w, h) == bytes && L->offset[0] == 0);
+            CHECK(L->pitch[0] == (pix >= 3 ? 2 * w : w) && L->offset[1] == (pix >= 3 ? 0 : w * h));
+            CHECK(L->pitch[1] == (pix == 0 ? w / 2 : pix >= 3 ? 0 : w) && L->pitch[2] == (pix == 0 ? w / 2 : 0));
+            CHECK(L->offset[2] == (pix == 0 ? w * h + (w / 2) * (h / 2) : 0));
+            CHECK(pix == 0 ? (size_t)bytes == i420_bytes(s[0], s[1]) : true);
+            h264mi_pix_layout m = *L;
+            m.frame_stride--;
+            CHECK(!pix_layout_ok(&m, s[0], s[1]) && pix_span(&m, s[0], s[1]) == bytes);
+            m = *L; m.pitch[0]--;
+            CHECK(!pix_layout_ok(&m, s[0], s[1]) && pix_span(&m, s[0], s[1]) == -1);
+        }
+    h264mi_pix_layout keep{7, {7, 7, 7}, {7, 7, 7}, 7};
+    for (int bad : {-1, 5, 2147483647}) CHECK(pix_layout_tight(&keep, bad, 16, 16) == -1);
+    for (int bad : {0, -2, 15, 8194, 2147483647}) CHECK(pix_layout_tight(&keep, 0, bad, 16) == -1 && pix_layout_tight(&keep, 3, 16, bad) == -1);
+    CHECK(pix_layout_tight(nullptr, 0, 16, 16) == -1 && keep.pix == 7 && keep.pitch[2] == 7 && keep.offset[0] == 7 && keep.frame_stride == 7);
+    CHECK(pix_span(nullptr, 16, 16) == -1 && !pix_layout_ok(nullptr, 16, 16) && !pix_args_ok(nullptr, 16, 16, 1));
+    // random and extreme fields against the restatement
+    const int32_t e32[] = {0, 1, -1, 2147483647, -2147483647 - 1, 65536, 65537, 16, 18, 36, 72};
+    const int64_t e64[] = {0, 1, -1, INT64_MAX, INT64_MIN, INT64_MAX - 1, INT64_MAX - 647, 1LL << 31, 1LL << 32, 648, 810, 972, 1296};
+    int good = 0, cases = 0;
+    for (int it = 0; it < 200000; it++) {
+        std::unique_ptr<h264mi_pix_layout> L(new h264mi_pix_layout);  // a heap block of exactly the struct
+        int w = 36, h = 18;
+        if (it % 2) {  // every field random, the extremes mixed in
+            L->pix = (int)(pix_rng() % 7) - 1;
+            for (int p = 0; p < 3; p++) {
+                L->pitch[p] = pix_rng() % 3 ? (int32_t)(pix_rng() % 200) : e32[pix_rng() % (sizeof e32 / sizeof *e32)];
+                L->offset[p] = pix_rng() % 3 ? (int64_t)(pix_rng() % 3000) : e64[pix_rng() % (sizeof e64 / sizeof *e64)];
+            }
+            L->frame_stride = pix_rng() % 3 ? (int64_t)(pix_rng() % 6000) : e64[pix_rng() % (sizeof e64 / sizeof *e64)];
+            if (pix_rng() % 8 == 0) w = e32[pix_rng() % (sizeof e32 / sizeof *e32)];
+            if (pix_rng() % 8 == 0) h = e32[pix_rng() % (sizeof e32 / sizeof *e32)];
+        } else {  // a tight layout with one field moved a little or to an extreme
+            CHECK(pix_layout_tight(L.get(), (int)(pix_rng() % 5), w, h) == 0);
+            const int f = (int)(pix_rng() % 8);
+            const bool ext = pix_rng() % 4 == 0;
+            const int d = (int)(pix_rng() % 81) - 40;
+            if (f < 3) L->pitch[f] = ext ? e32[pix_rng() % (sizeof e32 / sizeof *e32)] : L->pitch[f] + d;
+            else if (f < 6) L->offset[f - 3] = ext ? e64[pix_rng() % (sizeof e64 / sizeof *e64)] : L->offset[f - 3] + d;
+            else if (f == 6) L->frame_stride = ext ? e64[pix_rng() % (sizeof e64 / sizeof *e64)] : L->frame_stride + d;
+        }
+        const __int128 want = ref_pix_span(*L, w, h);
+        const int64_t got = pix_span(L.get(), w, h);
+        CHECK((__int128)got == want);
+        const bool ok = want >= 0 && (__int128)L->frame_stride >= want;
+        CHECK(pix_layout_ok(L.get(), w, h) == ok);
+        CHECK(pix_args_ok(L.get(), w, h, 1) == ok && !pix_args_ok(L.get(), w, h, 0) && !pix_args_ok(L.get(), w, h, -1));
+        if (ok) {  // the range test of a call: n frames of the layout against n tight frames, in 128 bits
+            const int n = 1 + (int)(pix_rng() % 3);
+            const uintptr_t a0 = 0x10000000u, b0 = pix_rng() % 2 ? a0 + (uintptr_t)(pix_rng() % 8000) : a0 - (uintptr_t)(pix_rng() % 8000);
+            const unsigned __int128 ab = (unsigned __int128)L->frame_stride * n, bb = (unsigned __int128)i420_bytes(w, h) * n;
+            const bool share = (ab >> 63) != 0 || ((unsigned __int128)a0 < b0 + bb && (unsigned __int128)b0 < a0 + ab);
+            CHECK(pix_ranges_overlap((const void *)a0, *L, (const void *)b0, w, h, n) == share);
+        }
+        good += ok;
+        cases++;
+    }
+    CHECK(good > cases / 20 && good < cases - cases / 20);
+    printf("pixel layouts: tight layouts of 5 formats x 6 sizes, %d random and extreme layouts (%d good)\n", cases, good);
+}
+
 int main() {
+    check_pix();
     check_orient();
     check_cells();
     check_tables();
