@@ -635,6 +635,69 @@ int h264mi_enc_encode_pix(h264mi_encoder *e, const void *d_frames, const h264mi_
 int h264mi_dec_set_output_layout(h264mi_decoder *d, const h264mi_pix_layout *layout);  /* NULL: back to the format */
 int h264mi_dec_output_layout(h264mi_decoder *d, h264mi_pix_layout *out);              /* 1 set (copied to out), 0 not set, -1 bad d */
 
+/* Colour specifications for the RGBA edges of the batch API: HD material is BT.709, screen and
+   camera RGB is often full range, and one-pixel-wide coloured detail (text, UI edges, labels) aliases when chroma is
+   picked from one pixel of four. A specification is the matrix, the range and how chroma is reduced (RGBA -> 4:2:0)
+   and restored (4:2:0 -> RGBA). All fields 0 is the reference wrapper's conversion -- what h264mi_rgba_to_i420_dev,
+   h264mi_i420_to_rgba_dev, h264mi_rgba_to_i420a_dev, h264mi_enc_encode_rgba and the H264MI_FMT_RGBA read-out do, and
+   keep doing -- and gives exactly their bytes. The drop-in functions (encode_frame, decode_frame_optimized, the
+   h264mi_i_* and _host variants) and those four _dev conversions never look at a specification.
+   Exact integers, int32; >> is an arithmetic shift, clamp is to 0..255; for a pixel or a sum of pixels p = (R, G, B),
+   F.p = F[0] R + F[1] G + F[2] B:
+     matrix, range   FY           FU            FV             yo  IY   RV   GU   GV   BU
+     601 limited     66 129 25    -38 -74 112   112 -94 -18    16  298  409  100  208  516
+     601 full        77 150 29    -43 -85 128   128 -107 -21    0  256  359   88  183  454
+     709 limited     47 157 16    -26 -86 112   112 -102 -10   16  298  459   55  136  541
+     709 full        54 183 19    -29 -99 128   128 -116 -12    0  256  403   48  120  475
+   RGBA -> 4:2:0: Y = clamp(((FY.p + 128) >> 8) + yo) for every pixel. TOPLEFT: Cb = clamp(((FU.p00 + 128) >> 8) + 128)
+   of the top-left pixel p00 of each 2x2, Cr likewise with FV. AVERAGE: with S = p00 + p01 + p10 + p11,
+   Cb = clamp(((FU.S + 512) >> 10) + 128), Cr likewise. (The clamp acts for full range only: a chroma of 256 becomes 255.)
+   4:2:0 -> RGBA: REPEAT: luma position (x, y) takes C[y >> 1][x >> 1]. BILINEAR (chroma sited at the centre of its
+   2x2): cx = x >> 1, nx = clamp(cx + (x & 1 ? 1 : -1), 0, w/2 - 1), cy and ny likewise from y and h/2, and
+   C = (9 C[cy][cx] + 3 C[cy][nx] + 3 C[ny][cx] + C[ny][nx] + 8) >> 4, for Cb and for Cr. Then with c = IY (Y - yo),
+   cb = Cb - 128, cr = Cr - 128 and sat(v) = min(max(v, 0), 65535) >> 8:
+     R = sat(c + RV cr + 128), G = sat(c - GU cb - GV cr + 128), B = sat(c + BU cb + 128), A = 255.
+   The stream does not say which specification made its pictures: the SPS stays the one OpenH264 writes
+   (video_signal_type_present_flag 0, no VUI colour description), so sender and receiver agree on it out of band. */
+#define H264MI_MATRIX_BT601 0
+#define H264MI_MATRIX_BT709 1
+#define H264MI_RANGE_LIMITED 0        /* Y 16..235, Cb/Cr 16..240 */
+#define H264MI_RANGE_FULL 1           /* 0..255 */
+#define H264MI_CHROMA_DOWN_TOPLEFT 0  /* RGBA -> 4:2:0: chroma of the top-left pixel of each 2x2 (the wrapper's) */
+#define H264MI_CHROMA_DOWN_AVERAGE 1  /* chroma of the sum of the four pixels */
+#define H264MI_CHROMA_UP_REPEAT 0     /* 4:2:0 -> RGBA: a chroma sample serves its 2x2 (the wrapper's) */
+#define H264MI_CHROMA_UP_BILINEAR 1   /* centre-sited 9-3-3-1 interpolation */
+typedef struct h264mi_colorspec { int32_t matrix, range, chroma_down, chroma_up; } h264mi_colorspec; /* 16 bytes; all 0 = today's */
+/* host only: 0, or -1 on NULL or a field outside {0, 1} */
+int h264mi_colorspec_ok(const h264mi_colorspec *spec);
+/* async on hip_stream, one launch each for n frames: h264mi_rgba_to_i420_dev, h264mi_i420_to_rgba_dev and
+   h264mi_rgba_to_i420a_dev under *spec, which is read before the call returns. Tight frames back to back; RGBA 4-byte
+   aligned, I420 and I420A at any alignment (16-byte RGBA accesses where w % 8 == 0 and the pointers allow, a 2x2 byte
+   path with the same bytes otherwise). rgba_to_i420_cs ignores chroma_up and i420_to_rgba_cs ignores chroma_down, but
+   both fields must be valid. rgba_to_i420a_cs writes Y, Cb and Cr as rgba_to_i420_cs does and A = the fourth byte;
+   AVERAGE sums the RGB of the four pixels whatever their alpha. Return 0, or -1 before the device is touched on a
+   null pointer, n <= 0, a side that is odd or outside 2..8192, a specification h264mi_colorspec_ok refuses, a
+   misaligned RGBA buffer, or source and destination byte ranges that overlap. */
+int h264mi_rgba_to_i420_cs_dev(void *d_i420, const void *d_rgba, int w, int h, int n, const h264mi_colorspec *spec, void *hip_stream);
+int h264mi_i420_to_rgba_cs_dev(void *d_rgba, const void *d_i420, int w, int h, int n, const h264mi_colorspec *spec, void *hip_stream);
+int h264mi_rgba_to_i420a_cs_dev(void *d_dst, const void *d_rgba, int w, int h, int n, const h264mi_colorspec *spec, void *hip_stream);
+/* the specification h264mi_enc_encode_rgba converts under, from its next call on (chroma_up is checked and kept but
+   unused). No other input path changes; an overlay list, the quality records, slices, exact GOM and inject_error
+   behave as before. With the default in force the call enqueues exactly what it did before. Returns 0, or -1 -- the
+   previous specification stays in force -- on a null encoder or a specification h264mi_colorspec_ok refuses. Under
+   a non-default specification h264mi_enc_encode_rgba returns -1 and enqueues nothing for an encoder whose width or
+   height is odd or above 8192. h264mi_enc_colorspec copies the one in force to *out (0, or -1 on a null pointer). */
+int h264mi_enc_set_colorspec(h264mi_encoder *e, const h264mi_colorspec *spec);       /* NULL: the default */
+int h264mi_enc_colorspec(h264mi_encoder *e, h264mi_colorspec *out);
+/* the specification of the H264MI_FMT_RGBA output of the calls enqueued after it (each call captures its setting, as
+   for the format; chroma_down is checked and kept but unused). It does nothing for I420 or layout output and is kept
+   across format changes. BILINEAR clamps to the cropped picture, never to coded samples outside the crop: the bytes
+   equal h264mi_i420_to_rgba_cs_dev on the cropped tight I420 picture. d_got and "left untouched when no picture" are
+   as before; with the default in force the call enqueues exactly what it did before. Returns 0, or -1 with nothing
+   changed on a null decoder or a specification h264mi_colorspec_ok refuses. */
+int h264mi_dec_set_output_colorspec(h264mi_decoder *d, const h264mi_colorspec *spec); /* NULL: the default */
+int h264mi_dec_output_colorspec(h264mi_decoder *d, h264mi_colorspec *out);
+
 /* library self-description */
 const char *h264mi_version(void);
 

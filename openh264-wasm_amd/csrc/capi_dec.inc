@@ -243,6 +243,18 @@ int h264mi_dec_output_layout(h264mi_decoder *d, h264mi_pix_layout *out) {
     if (out) *out = d->c->out_lay;
     return 1;
 }
+// the specification of RGBA output (DESIGN.md §5.11; colorspace.hip dec_output_rgba_cs_kernel): kept whatever the format
+// is; each call hands the one in force to its read-out launches by value (dec_frames)
+int h264mi_dec_set_output_colorspec(h264mi_decoder *d, const h264mi_colorspec *spec) {
+    if (!d || (spec && !colorspec_ok(spec))) return -1;
+    d->c->out_cs = spec ? *spec : h264mi_colorspec{};
+    return 0;
+}
+int h264mi_dec_output_colorspec(h264mi_decoder *d, h264mi_colorspec *out) {
+    if (!d || !out) return -1;
+    *out = d->c->out_cs;
+    return 0;
+}
 int h264mi_dec_set_recon_gate(h264mi_decoder *d, const uint32_t *d_counter, uint32_t target, uint32_t step, int count, int limit_us) {
     if (!d || count < 0 || limit_us < 0 || limit_us > 1000000) return -1;
     DecCtx *c = d->c;

@@ -239,8 +239,41 @@ int h264mi_i420_overlay_dev(void *d_canvas, int cw, int ch, int ncanvas, const v
 int h264mi_enc_encode_rgba(h264mi_encoder *e, const void *d_rgba_frames) {
     if (!e || !d_rgba_frames || ((uintptr_t)d_rgba_frames & 3)) return -1;
     EncCtx *c = e->c;
-    if (launch_rgba_to_i420((const uint8_t *)d_rgba_frames, c->w, c->h, c->S, c->d_src, c->stream) != 0) return -1;
+    if (colorspec_default(c->cs)) {
+        if (launch_rgba_to_i420((const uint8_t *)d_rgba_frames, c->w, c->h, c->S, c->d_src, c->stream) != 0) return -1;
+    } else if (!canvas_ok(c->w, c->h) ||
+               launch_rgba_to_i420_cs(c->d_src, (const uint8_t *)d_rgba_frames, c->w, c->h, c->S, c->cs, false, c->stream) != 0)
+        return -1;
     return enc_code_input(c);
+}
+// Colour specifications (DESIGN.md §5.11; colorspace.hip; the table and the checks: picture_host.h): n frames, one launch
+int h264mi_colorspec_ok(const h264mi_colorspec *spec) { return colorspec_ok(spec) ? 0 : -1; }
+static bool cs_rgba_call_ok(const void *d_yuv, size_t yuv_bytes, const void *d_rgba, int w, int h, int n, const h264mi_colorspec *spec) {
+    return d_yuv && d_rgba && cs_args_ok(w, h, n, spec) && !((uintptr_t)d_rgba & 3) &&
+           !byte_ranges_overlap(d_yuv, (size_t)n * yuv_bytes, d_rgba, (size_t)n * w * h * 4);
+}
+int h264mi_rgba_to_i420_cs_dev(void *d_i420, const void *d_rgba, int w, int h, int n, const h264mi_colorspec *spec, void *hip_stream) {
+    if (!cs_rgba_call_ok(d_i420, i420_bytes(w, h), d_rgba, w, h, n, spec)) return -1;
+    return launch_rgba_to_i420_cs((uint8_t *)d_i420, (const uint8_t *)d_rgba, w, h, n, *spec, false, (hipStream_t)hip_stream);
+}
+int h264mi_i420_to_rgba_cs_dev(void *d_rgba, const void *d_i420, int w, int h, int n, const h264mi_colorspec *spec, void *hip_stream) {
+    if (!cs_rgba_call_ok(d_i420, i420_bytes(w, h), d_rgba, w, h, n, spec)) return -1;
+    return launch_i420_to_rgba_cs((uint8_t *)d_rgba, (const uint8_t *)d_i420, w, h, n, *spec, (hipStream_t)hip_stream);
+}
+int h264mi_rgba_to_i420a_cs_dev(void *d_dst, const void *d_rgba, int w, int h, int n, const h264mi_colorspec *spec, void *hip_stream) {
+    if (!cs_rgba_call_ok(d_dst, i420a_bytes(w, h), d_rgba, w, h, n, spec)) return -1;
+    return launch_rgba_to_i420_cs((uint8_t *)d_dst, (const uint8_t *)d_rgba, w, h, n, *spec, true, (hipStream_t)hip_stream);
+}
+// what the next h264mi_enc_encode_rgba converts under; a refused one leaves the previous in force
+int h264mi_enc_set_colorspec(h264mi_encoder *e, const h264mi_colorspec *spec) {
+    if (!e || (spec && !colorspec_ok(spec))) return -1;
+    e->c->cs = spec ? *spec : h264mi_colorspec{};
+    return 0;
+}
+int h264mi_enc_colorspec(h264mi_encoder *e, h264mi_colorspec *out) {
+    if (!e || !out) return -1;
+    *out = e->c->cs;
+    return 0;
 }
 // Area-average downscaling (DESIGN.md §5.3; scale.hip): n tight I420 frames of one geometry pair, one launch
 int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, void *hip_stream) {

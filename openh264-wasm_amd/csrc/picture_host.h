@@ -1,8 +1,8 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, colorspace.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
-// and upscale launch structs hold. DESIGN.md §5.8.
+// and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -133,6 +133,31 @@ static inline bool pix_ranges_overlap(const void *a, const h264mi_pix_layout &L,
 // arguments of a conversion call, everything but the pointers' values
 static inline bool pix_args_ok(const h264mi_pix_layout *L, int w, int h, int n) { return n > 0 && pix_layout_ok(L, w, h); }
 
+// ---- colour specifications (include/h264mi.h)
+// one row of the header's table, as the kernels of colorspace.hip take it in their arguments
+struct CsCoef {
+    int32_t fy[3], fu[3], fv[3];  // RGB -> Y, Cb, Cr, 8 fractional bits
+    int32_t yo;                   // luma offset
+    int32_t iy, rv, gu, gv, bu;   // Y, Cb, Cr -> RGB, 8 fractional bits
+};
+static_assert(sizeof(CsCoef) == 60, "the launch structs count on it");
+static inline bool colorspec_ok(const h264mi_colorspec *s) {
+    return s && !((uint32_t)s->matrix > 1 || (uint32_t)s->range > 1 || (uint32_t)s->chroma_down > 1 || (uint32_t)s->chroma_up > 1);
+}
+static inline bool colorspec_default(const h264mi_colorspec &s) { return (s.matrix | s.range | s.chroma_down | s.chroma_up) == 0; }
+// the table: index matrix * 2 + range of a good specification. Every FU and FV row sums to 0, FY to 220 (limited) or 256 (full)
+static inline const CsCoef &cs_coef(int matrix, int range) {
+    static const CsCoef T[4] = {
+        {{66, 129, 25}, {-38, -74, 112}, {112, -94, -18}, 16, 298, 409, 100, 208, 516},   // 601 limited: the wrapper's
+        {{77, 150, 29}, {-43, -85, 128}, {128, -107, -21}, 0, 256, 359, 88, 183, 454},    // 601 full
+        {{47, 157, 16}, {-26, -86, 112}, {112, -102, -10}, 16, 298, 459, 55, 136, 541},   // 709 limited
+        {{54, 183, 19}, {-29, -99, 128}, {128, -116, -12}, 0, 256, 403, 48, 120, 475},    // 709 full
+    };
+    return T[(matrix & 1) * 2 + (range & 1)];
+}
+// arguments of a conversion call under a specification, everything but the pointers' values
+static inline bool cs_args_ok(int w, int h, int n, const h264mi_colorspec *s) { return n > 0 && canvas_ok(w, h) && colorspec_ok(s); }
+
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
 static inline int cell_kind(const h264mi_cell &c) {
@@ -240,4 +265,8 @@ int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_l
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);
 int launch_dec_output_pix(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in, const h264mi_pix_layout &L,
                           hipStream_t s);
+// colorspace.hip: a good specification, even sides within PIC_MAX_SIDE; alpha: I420A sprites out (A = the fourth byte)
+int launch_rgba_to_i420_cs(uint8_t *d_out, const uint8_t *d_rgba, int w, int h, int n, const h264mi_colorspec &spec, bool alpha, hipStream_t s);
+int launch_i420_to_rgba_cs(uint8_t *d_rgba, const uint8_t *d_i420, int w, int h, int n, const h264mi_colorspec &spec, hipStream_t s);
+int launch_dec_output_rgba_cs(int S, int cw, int ch, const DecDesc *desc, const DecInput *in, const h264mi_colorspec &spec, hipStream_t s);
 }  // namespace h264mi

@@ -48,6 +48,7 @@ struct DecCtx {
     int w = 0, h = 0;                   // the size the batch decoder was created with (0: a C-ABI decoder)
     bool out_lay_set = false;           // a layout instead (h264mi_dec_set_output_layout), good for w x h
     h264mi_pix_layout out_lay = {};
+    h264mi_colorspec out_cs = {};       // what H264MI_FMT_RGBA output converts under (h264mi_dec_set_output_colorspec); all 0: color.inc's kernel
     // C-ABI staging
     uint8_t *d_nal = nullptr;
     size_t nal_cap = 0;
@@ -302,6 +303,8 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
         hipLaunchKernelGGL(dec_end_kernel, dim3((S + 63) / 64), dim3(64), 0, c->stream, DecEndLaunch{S, df, streamed});
         if (outputs && in[0].fmt == H264MI_FMT_LAYOUT) {  // the layout in force travels by value in the launch
             if (launch_dec_output_pix(S, c->cw, c->ch, c->w, c->h, df, c->d_in + (size_t)(slot0 + f) * S, c->out_lay, c->stream) != 0) return -1;
+        } else if (outputs && in[0].fmt == H264MI_FMT_RGBA && !colorspec_default(c->out_cs)) {  // likewise the specification in force
+            if (launch_dec_output_rgba_cs(S, c->cw, c->ch, df, c->d_in + (size_t)(slot0 + f) * S, c->out_cs, c->stream) != 0) return -1;
         } else if (outputs && in[0].fmt == H264MI_FMT_RGBA) {  // every frame's picture to the caller (DecInput::out / got)
             const dim3 cg = color_grid(c->cw, c->ch, S);
             hipLaunchKernelGGL(dec_output_rgba_kernel, dim3(cg.x, S), dim3(256), 0, c->stream,

@@ -196,6 +196,9 @@ struct EncCtx {
     std::vector<h264mi_overlay> ov;
     const uint8_t *ov_sprites = nullptr;
     int ov_w = 0, ov_h = 0;
+    // what h264mi_enc_encode_rgba converts under (h264mi_enc_set_colorspec; colorspace.hip). All 0: the wrapper's
+    // conversion by color.inc's kernel, as before the specification existed
+    h264mi_colorspec cs = {};
 };
 
 struct EncMbLaunch {  // enc_mb_kernel reads the source frames through this launch-time base

@@ -157,6 +157,14 @@ def lib():
             'h264mi_enc_encode_pix': (i, [vp, vp, vp]),
             'h264mi_dec_set_output_layout': (i, [vp, vp]),
             'h264mi_dec_output_layout': (i, [vp, vp]),
+            'h264mi_colorspec_ok': (i, [vp]),
+            'h264mi_rgba_to_i420_cs_dev': (i, [vp, vp, i, i, i, vp, vp]),
+            'h264mi_i420_to_rgba_cs_dev': (i, [vp, vp, i, i, i, vp, vp]),
+            'h264mi_rgba_to_i420a_cs_dev': (i, [vp, vp, i, i, i, vp, vp]),
+            'h264mi_enc_set_colorspec': (i, [vp, vp]),
+            'h264mi_enc_colorspec': (i, [vp, vp]),
+            'h264mi_dec_set_output_colorspec': (i, [vp, vp]),
+            'h264mi_dec_output_colorspec': (i, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -360,6 +368,20 @@ class BatchEncoder:
         assert frames.is_cuda and frames.numel() >= self.S * self.rgba_frame_bytes
         if self._L.h264mi_enc_encode_rgba(self._e, ctypes.c_void_p(frames.data_ptr())) != 0:
             raise RuntimeError('h264mi_enc_encode_rgba failed')
+
+    def set_colorspec(self, spec):
+        """what encode_rgba converts under from its next call on: a ColorSpec, or None for the default (BT.601 limited
+        range, chroma of the top-left pixel: the bytes and the launch of before). No other input path changes.
+        ValueError, with the previous specification still in force, on one colorspec_ok refuses."""
+        if self._L.h264mi_enc_set_colorspec(self._e, ctypes.byref(spec) if spec is not None else None) != 0:
+            raise ValueError(f'h264mi_enc_set_colorspec refused {spec!r}')
+
+    def colorspec(self):
+        """the specification in force (a copy)"""
+        out = ColorSpec()
+        if self._L.h264mi_enc_colorspec(self._e, ctypes.byref(out)) != 0:
+            raise RuntimeError('h264mi_enc_colorspec failed')
+        return out
 
     def encode_scaled(self, frames, src_w, src_h):
         """frames: uint8 CUDA tensor holding S tight I420 frames of src_w x src_h back to back, any alignment
@@ -675,6 +697,22 @@ class BatchDecoder:
         out = PixLayout()
         return out if self._L.h264mi_dec_output_layout(self._d, ctypes.byref(out)) == 1 else None
 
+    def set_output_colorspec(self, spec):
+        """what 'rgba' output converts under from the next decode_frames call on (each call captures its setting): a
+        ColorSpec, or None for the default (BT.601 limited range, chroma repeated: the bytes and the launch of before).
+        Nothing changes for 'i420' or layout output; the setting is kept across format changes. BILINEAR clamps to the
+        cropped picture: the bytes equal i420_to_rgba(..., spec=spec) on the cropped I420 picture. ValueError, with
+        nothing changed, on one colorspec_ok refuses."""
+        if self._L.h264mi_dec_set_output_colorspec(self._d, ctypes.byref(spec) if spec is not None else None) != 0:
+            raise ValueError(f'h264mi_dec_set_output_colorspec refused {spec!r}')
+
+    def output_colorspec(self):
+        """the specification in force (a copy)"""
+        out = ColorSpec()
+        if self._L.h264mi_dec_output_colorspec(self._d, ctypes.byref(out)) != 0:
+            raise RuntimeError('h264mi_dec_output_colorspec failed')
+        return out
+
     def set_parse_cus(self, lo, hi):
         """entropy decoding on CU mask bits [lo, hi) (see h264mi_dec_set_parse_cus)"""
         if self._L.h264mi_dec_set_parse_cus(self._d, lo, hi) != 0:
@@ -836,15 +874,49 @@ def _convert_dev(fn, dst, src, dst_bytes, src_bytes, w, h, n, stream):
         raise ValueError(f'bad arguments: {w}x{h}, {n} frames')
 
 
-def rgba_to_i420(dst, src, w, h, n, stream=None):
+MATRIX_BT601, MATRIX_BT709 = 0, 1                # H264MI_MATRIX_*
+RANGE_LIMITED, RANGE_FULL = 0, 1                 # H264MI_RANGE_*: Y 16..235 and Cb/Cr 16..240, or 0..255
+CHROMA_DOWN_TOPLEFT, CHROMA_DOWN_AVERAGE = 0, 1  # H264MI_CHROMA_DOWN_*: RGBA -> 4:2:0 from the top-left pixel of each 2x2, or from the sum of the four
+CHROMA_UP_REPEAT, CHROMA_UP_BILINEAR = 0, 1      # H264MI_CHROMA_UP_*: 4:2:0 -> RGBA by repetition, or centre-sited 9-3-3-1 interpolation
+
+
+class ColorSpec(ctypes.Structure):
+    """h264mi_colorspec (include/h264mi.h): the matrix, the range and how chroma is reduced and restored at an RGBA
+    edge; all 0 is the reference wrapper's conversion. 16 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('matrix', 'range', 'chroma_down', 'chroma_up')]
+
+    def __repr__(self):
+        return 'ColorSpec(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
+
+
+def colorspec_ok(spec):
+    """0 when every field of spec is 0 or 1, else -1 (None included); h264mi_colorspec_ok, host only"""
+    return lib().h264mi_colorspec_ok(ctypes.byref(spec) if spec is not None else None)
+
+
+def _convert_cs_dev(fn, dst, src, dst_bytes, src_bytes, w, h, n, spec, stream):
+    _assert_dev_u8(dst, src)
+    assert n <= 0 or min(w, h) <= 0 or (dst.numel() >= n * dst_bytes and src.numel() >= n * src_bytes)
+    if fn(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, ctypes.byref(spec), _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {w}x{h}, {n} frames, {spec!r}')
+
+
+def rgba_to_i420(dst, src, w, h, n, stream=None, spec=None):
     """n tight RGBA8 frames (uint8 CUDA tensor src) to n tight I420 frames (dst), one launch, async on stream
-    (default: the current one); h264mi_rgba_to_i420_dev"""
-    _convert_dev(lib().h264mi_rgba_to_i420_dev, dst, src, w * h * 3 // 2, w * h * 4, w, h, n, stream)
+    (default: the current one); h264mi_rgba_to_i420_dev, or with spec (a ColorSpec) h264mi_rgba_to_i420_cs_dev: its
+    matrix, range and chroma_down; the bytes equal tests/csref.py's. That call also refuses (ValueError) a side outside
+    2..8192 and overlapping buffers."""
+    if spec is None:
+        return _convert_dev(lib().h264mi_rgba_to_i420_dev, dst, src, w * h * 3 // 2, w * h * 4, w, h, n, stream)
+    _convert_cs_dev(lib().h264mi_rgba_to_i420_cs_dev, dst, src, w * h * 3 // 2, w * h * 4, w, h, n, spec, stream)
 
 
-def i420_to_rgba(dst, src, w, h, n, stream=None):
-    """n tight I420 frames (uint8 CUDA tensor src) to n tight RGBA8 frames (dst, A = 255); h264mi_i420_to_rgba_dev"""
-    _convert_dev(lib().h264mi_i420_to_rgba_dev, dst, src, w * h * 4, w * h * 3 // 2, w, h, n, stream)
+def i420_to_rgba(dst, src, w, h, n, stream=None, spec=None):
+    """n tight I420 frames (uint8 CUDA tensor src) to n tight RGBA8 frames (dst, A = 255); h264mi_i420_to_rgba_dev, or
+    with spec (a ColorSpec) h264mi_i420_to_rgba_cs_dev: its matrix, range and chroma_up; ValueError as rgba_to_i420"""
+    if spec is None:
+        return _convert_dev(lib().h264mi_i420_to_rgba_dev, dst, src, w * h * 4, w * h * 3 // 2, w, h, n, stream)
+    _convert_cs_dev(lib().h264mi_i420_to_rgba_cs_dev, dst, src, w * h * 4, w * h * 3 // 2, w, h, n, spec, stream)
 
 
 def i420_scale(dst, src, sw, sh, dw, dh, n, stream=None):
@@ -1081,10 +1153,13 @@ def i420a_bytes(w, h):
     return 2 * w * h + 2 * (w // 2) * (h // 2)
 
 
-def rgba_to_i420a(dst, src, w, h, n, stream=None):
+def rgba_to_i420a(dst, src, w, h, n, stream=None, spec=None):
     """n tight RGBA8 frames (uint8 CUDA tensor src, 4-byte aligned) to n I420A sprites (dst, any alignment), one launch,
     async on stream (default: the current one); h264mi_rgba_to_i420a_dev. Y, Cb, Cr as rgba_to_i420, A the fourth byte.
-    ValueError on a bad argument (an odd side or one outside 2..8192, n <= 0, a misaligned source)."""
+    With spec (a ColorSpec) h264mi_rgba_to_i420a_cs_dev: Y, Cb, Cr as rgba_to_i420(..., spec=spec), which also refuses
+    overlapping buffers. ValueError on a bad argument (an odd side or one outside 2..8192, n <= 0, a misaligned source)."""
+    if spec is not None:
+        return _convert_cs_dev(lib().h264mi_rgba_to_i420a_cs_dev, dst, src, i420a_bytes(w, h), w * h * 4, w, h, n, spec, stream)
     _assert_dev_u8(dst, src)
     assert n <= 0 or min(w, h) <= 0 or (dst.numel() >= n * i420a_bytes(w, h) and src.numel() >= n * w * h * 4)
     if lib().h264mi_rgba_to_i420a_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), w, h, n, _hip_stream(stream)) != 0:
