@@ -221,6 +221,13 @@ int h264mi_dec_set_slice_waves(h264mi_decoder *d, int k);
    Returns 0, -1 on a bad argument. h264mi_dec_streamed: the mode in effect. */
 int h264mi_dec_set_streamed(h264mi_decoder *d, int mode);
 int h264mi_dec_streamed(h264mi_decoder *d);
+/* record resolution ahead of the reconstruction: a call that is not streamed resolves the motion
+   vectors and Intra4x4 modes of all its pictures in one light launch before any of them is reconstructed, and
+   reconstructs from resolved records. mode 1 (the default): that launch runs on the call's parse stream, behind
+   its slice data; 0: never -- every call resolves inside its reconstruction, as a streamed call always does. Applies to the calls enqueued after it. Returns 0, -1 on
+   a bad argument. h264mi_dec_resolve_launches: resolution launches enqueued so far (diagnostic). */
+int h264mi_dec_set_resolve(h264mi_decoder *d, int mode);
+long long h264mi_dec_resolve_launches(h264mi_decoder *d);
 /* reconstruction gate, for the next decode call only: frame f (< count) of that call is reconstructed once the
    device uint32 *d_counter has reached target + f * step (wrap-safe comparison), or after limit_us microseconds
    of waiting -- a scheduling hint, never a correctness condition. With an encoder's rows counter

@@ -218,6 +218,12 @@ int h264mi_dec_set_streamed(h264mi_decoder *d, int mode) {
     return dec_set_streamed(d->c, mode);
 }
 int h264mi_dec_streamed(h264mi_decoder *d) { return d ? d->c->streamed : 0; }
+int h264mi_dec_set_resolve(h264mi_decoder *d, int mode) {
+    if (!d || mode < 0 || mode > 1) return -1;
+    d->c->resolve = mode;  // each call captures it when it is enqueued (dec_frames)
+    return 0;
+}
+long long h264mi_dec_resolve_launches(h264mi_decoder *d) { return d ? d->c->resolve_launches : -1; }
 // what h264mi_dec_decode_frames_out writes to its d_out buffers; each call captures the format when it is
 // enqueued (DecInput::fmt), so a change needs no synchronisation
 int h264mi_dec_set_output_format(h264mi_decoder *d, int fmt) {

@@ -1175,6 +1175,7 @@ __global__ __launch_bounds__(64) void dec_hdr_kernel(DecParseLaunch a) {
         F->hdr_ok = (!fail && nsl > 0) ? 1 : 0;
         F->anyp = anyp; F->nonref = ref0 ? 0 : 1; F->cqp = ps.cqp;
         F->sdone = 0;
+        F->res_abort = 0;
         *(DecParams *)&F->ps = ps;
         if (fail && !F->err) F->err = 3;
         if (commit) st->psb[a.pin ^ 1] = ps;  // the next call's parameter sets
@@ -1292,13 +1293,13 @@ __global__ void dec_frame_begin_kernel(DecBeginLaunch a) {
     const DecFrame *F = D.frm;
     if (F->hdr_ok) st->ps = F->ps;
     bool ok = F->hdr_ok && !F->err;
-    if (ok && !a.provisional) ok = slices_cover(F);
+    if (ok && !a.provisional) ok = slices_cover(F) && !F->res_abort;
     // a P slice with no earlier decoded picture (no reference) yields no picture, like a parse error
     if (ok && F->anyp && !st->has_ref) ok = false;
     st->got_pic = ok ? 1 : 0;
     st->nonref = F->nonref;
     // per frame: a damaged access unit yields no picture, the next one decodes (no slices at all: no error)
-    st->err = ok ? 0 : (F->err ? F->err : (F->hdr_ok ? 3 : 0));
+    st->err = ok ? 0 : (F->err ? F->err : (F->hdr_ok ? (F->res_abort ? 1 : 3) : 0));
     if (ok) st->epoch = st->epoch + 1;
 }
 // Streamed reconstruction, after dec_recon_kernel (and after the slice data of the call is parsed): the

@@ -3,8 +3,13 @@
 // + dequantisation (8.5), from the per-MB records of dec_parse.inc.
 //
 // Replaces the reconstruction half of ISVCDecoder::DecodeFrameNoDelay (openh264_wrapper.cpp:435).
-// It also finishes the parse: motion vectors (8.4.1) and Intra4x4 modes (8.3.1.1) are resolved
-// here from the raw record, with the above row's bottom vectors/modes arriving as granules 8..12.
+// The parse is finished here too: motion vectors (8.4.1) and Intra4x4 modes (8.3.1.1) are resolved from the
+// raw record by one set of rule functions (rnb .. resolve_record), run in one of two places. A call whose
+// slice data is parsed before its reconstruction starts resolves every picture's records in dec_resolve_kernel,
+// a light row wavefront ahead of the reconstruction, and dec_recon_kernel<true> reads resolved records: its
+// inter macroblocks wait for nothing from their own picture. A streamed call (the reconstruction follows the
+// slice data row by row) keeps the resolution inside the reconstruction wavefront, dec_recon_kernel<false>,
+// with the above row's bottom vectors/modes arriving as granules 8..12.
 // Same MB-row wavefront as the encoder: one wave per (stream, MB row); the unfiltered bottom line
 // of each MB is handed to the row below as {epoch,payload} granules. Residuals of all 24 blocks
 // are computed in parallel (lane per block); the only serial chain is the Intra4x4 one (16 steps of
@@ -250,7 +255,7 @@ DEV uint32_t mb_nb_mask(int mbx, int mby, int mbw, int first) {
     return (mbx > 0 && mbi - 1 >= first ? NB_A : 0) | (mby > 0 && mbi - mbw >= first ? NB_B : 0) |
            (mby > 0 && mbx + 1 < mbw && mbi - mbw + 1 >= first ? NB_C : 0) | (mby > 0 && mbx > 0 && mbi - mbw - 1 >= first ? NB_D : 0);
 }
-DEV RNb rnb(const DecLds &S, int mbx, uint32_t nbm, uint32_t done, int x, int y) {
+template <class L> DEV RNb rnb(const L &S, int mbx, uint32_t nbm, uint32_t done, int x, int y) {
     RNb r = {0, -1, 0, 0};
     if (y < 0) {
         const uint32_t *g;
@@ -281,7 +286,7 @@ DEV RNb rnb(const DecLds &S, int mbx, uint32_t nbm, uint32_t done, int x, int y)
     return r;
 }
 // 8.4.1.3 (shape 0: median, 1: 16x8, 2: 8x16)
-DEV void rmvp(const DecLds &S, int mbx, uint32_t nbm, uint32_t done, int bx, int by, int pw, int shape, int &ox, int &oy) {
+template <class L> DEV void rmvp(const L &S, int mbx, uint32_t nbm, uint32_t done, int bx, int by, int pw, int shape, int &ox, int &oy) {
     RNb A = rnb(S, mbx, nbm, done, bx - 1, by), B = rnb(S, mbx, nbm, done, bx, by - 1);
     RNb C = rnb(S, mbx, nbm, done, bx + pw, by - 1);
     if (!C.avail) C = rnb(S, mbx, nbm, done, bx - 1, by - 1);
@@ -313,7 +318,7 @@ DEV void set_part_mv(MbInfo &I, uint32_t &done, int px, int py, int pw, int ph, 
 // P_Skip and P_L0_16x16 (most macroblocks of a P picture), wave-uniform: the neighbour words are read
 // into scalars (8.4.1.1 / 8.4.1.3, the same decisions as rnb / rmvp for a 16x16 partition) and the 16
 // block vectors are written by 16 lanes at once instead of one lane's loop.
-DEV uint32_t resolve_p16_uni(DecLds &S, int mbx, uint32_t nbm, bool skip) {
+template <class L> DEV uint32_t resolve_p16_uni(L &S, int mbx, uint32_t nbm, bool skip) {
     // every neighbour word first (one LDS round trip instead of one per neighbour behind its branch)
     const int sb = mbx % 3, sc = sb == 2 ? 0 : sb + 1, sd = sb == 0 ? 2 : sb - 1;
     const uint32_t wa_t = S.linfo.type, wa_mv = ((const uint32_t *)S.linfo.mv)[3];
@@ -355,7 +360,7 @@ DEV uint32_t resolve_p16_uni(DecLds &S, int mbx, uint32_t nbm, bool skip) {
     if (lane < 16) ((uint32_t *)S.info.mv)[lane] = mvw;
     return mvw;  // every block's vector (uniform)
 }
-DEV void resolve_record(DecLds &S, int mbx, uint32_t nbm) {
+template <class L> DEV void resolve_record(L &S, int mbx, uint32_t nbm) {
     MbInfo &I = S.info;
     const int type = I.type;
     uint32_t done = 0;
@@ -406,6 +411,96 @@ DEV void resolve_record(DecLds &S, int mbx, uint32_t nbm) {
     }
 }
 
+// what the row below needs of a resolved record besides its bottom vectors: type | bottom Intra4x4 modes << 8
+DEV uint32_t res_type_word(const MbInfo &R) {
+    return (uint32_t)R.type | ((uint32_t)(R.i4mode[12] & 15) << 8) | ((uint32_t)(R.i4mode[13] & 15) << 12) |
+           ((uint32_t)(R.i4mode[14] & 15) << 16) | ((uint32_t)(R.i4mode[15] & 15) << 20);
+}
+
+// ---------------------------------------------------------------- resolution pass
+// dec_resolve_kernel: the raw records of every picture of a call -> resolved records (mv[16], i4mode[16]), in
+// place, before any of the call's pictures is reconstructed. None of it depends on samples, and in Baseline on
+// no other picture, so all `np` pictures (frames x streams) resolve at once: one wave per (picture, MB row), in
+// ticket order rows-major, so a row waits only for lower tickets (the forward-progress argument of the other
+// wavefront kernels). Row y hands the vectors of its bottom blocks, its type and its bottom Intra4x4 modes to
+// row y + 1 as 5 {tag, payload} granules per MB (DecDesc::rgran, per frame slot; the tag is the call's, so a
+// slot's granules of an earlier call are stale), and keeps MBs x-1, x, x+1 of the row above in the three-slot
+// gm ring the rule functions read. Waits are gran_wait's: bounded by WaitClock, ended by the picture's abort
+// word (DecFrame::res_abort; dec_frame_begin_kernel then drops the picture). No samples, coefficients or
+// reference windows: 5 KB less LDS and a fifth of the reconstruction's registers.
+#define H264MI_RES_GRANULES_PER_MB 5
+struct DecResolveLaunch { int np, mbw, mbh; const DecDesc *desc; uint32_t *ticket; uint32_t base, tag; };
+struct ResLds {
+    uint32_t gm[3][5];         // above-row MBs, as DecLds::gm
+    int8_t modes[16];
+    alignas(16) MbInfo info;
+    alignas(16) MbInfo linfo;  // resolved record of the left MB
+};
+__global__ __launch_bounds__(64) void dec_resolve_kernel(DecResolveLaunch a) {
+    __shared__ ResLds S;
+    __shared__ int s_ticket;
+    const int lane = threadIdx.x;
+    // the counter is never reset: the host passes the value it had before this launch (launches that share a
+    // counter are ordered on one stream or by the slot group's events)
+    if (lane == 0) s_ticket = (int)(atomicAdd(a.ticket, 1u) - a.base);
+    wave_lds_sync();
+    const int t = uni(s_ticket);
+    if (t < 0 || t >= a.np * a.mbh) return;
+    const int mby = t / a.np, w = t - mby * a.np;
+    CONSTANT const DecDesc &D = cst(a.desc)[w];
+    DecFrame *F = D.frm;
+    // the pictures dec_frame_begin_kernel may accept (it also wants a reference for P slices, which only the
+    // reconstruction side knows: a picture resolved for nothing costs nothing else)
+    if (!uni(F->hdr_ok) || uni(F->err) || !uni((int)slices_cover(F))) return;
+    int32_t *abort_word = &F->res_abort;
+    const uint32_t tag = a.tag;
+    const int mbw = a.mbw;
+    GLOBAL uint32_t *info32 = gbl((uint32_t *)D.info) + (size_t)mby * mbw * 32;
+    GLOBAL uint64_t *grow = gbl(D.rgran) + (size_t)mby * mbw * H264MI_RES_GRANULES_PER_MB;
+    GLOBAL uint64_t *grow_prev = grow - (mby > 0 ? (size_t)mbw * H264MI_RES_GRANULES_PER_MB : 0);
+    const bool below = mby + 1 < a.mbh;
+    // one MB ahead: the raw record, and the row above's granules of MB x+2 (polled again only if still stale)
+    uint32_t pf_info = lane < 32 ? info32[lane] : 0;
+    uint64_t pf_g = 0;
+    auto gload = [&](int mx) {
+        if (lane < 5) pf_g = __hip_atomic_load(grow_prev + (size_t)mx * H264MI_RES_GRANULES_PER_MB + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    auto gtake = [&](int mx) -> bool {  // MB mx of the row above -> its gm slot
+        uint32_t v = (uint32_t)pf_g;
+        if (__ballot(lane < 5 && (uint32_t)(pf_g >> 32) != tag) != 0 &&
+            !gran_wait(grow_prev + (size_t)mx * H264MI_RES_GRANULES_PER_MB, 5, tag, &v, abort_word)) return false;
+        if (lane < 5) S.gm[mx % 3][lane] = v;
+        return true;
+    };
+    if (mby > 0) {
+        gload(0);
+        if (!gtake(0)) return;
+        if (mbw > 1) gload(1);
+    }
+    for (int mbx = 0; mbx < mbw; mbx++) {
+        if (lane < 32) ((uint32_t *)&S.info)[lane] = pf_info;
+        const uint32_t rw0 = __builtin_amdgcn_readfirstlane(pf_info), rw31 = __builtin_amdgcn_readlane(pf_info, 31);
+        const int rt = (int)(rw0 & 255);
+        if (mbx + 1 < mbw && lane < 32) pf_info = info32[(size_t)(mbx + 1) * 32 + lane];
+        if (mby > 0 && mbx + 1 < mbw) {
+            if (!gtake(mbx + 1)) return;
+            if (mbx + 2 < mbw) gload(mbx + 2);
+        }
+        wave_lds_sync();
+        const uint32_t nbm = uni(mb_nb_mask(mbx, mby, mbw, MB_SLICE_FIRST(rw31)));
+        if (rt == MI_PSKIP || rt == MI_P16x16) resolve_p16_uni(S, mbx, nbm, rt == MI_PSKIP);
+        else if (lane == 0) resolve_record(S, mbx, nbm);
+        wave_lds_sync();
+        const uint32_t rv = lane < 32 ? ((const uint32_t *)&S.info)[lane] : 0;
+        if (below && lane < 5) gran_store(grow + (size_t)mbx * H264MI_RES_GRANULES_PER_MB + lane, tag, lane < 4 ? ((const uint32_t *)S.info.mv)[12 + lane] : res_type_word(S.info));
+        // the resolved fields back into the record: i4mode (dwords 2..5) and mv (15..30)
+        static_assert(offsetof(MbInfo, i4mode) == 8 && offsetof(MbInfo, mv) == 60, "MbInfo dwords of the resolved fields");
+        if ((lane >= 2 && lane < 6) || (lane >= 15 && lane < 31)) info32[(size_t)mbx * 32 + lane] = rv;
+        if (lane < 32) ((uint32_t *)&S.linfo)[lane] = rv;
+        wave_lds_sync();
+    }
+}
+
 // Every sample the window paths read for the MB's 4x4 blocks lies inside the LDS windows: luma columns/rows
 // [DWIN_LO, DWIN_HI) = [-24, 40) and chroma [DWINC_LO, DWINC_HI) = [-12, 20) relative to the MB. Exact, per
 // block and per direction:
@@ -436,7 +531,9 @@ DEV bool mb_in_window(const MbInfo &I) {
 #else
 #define H264MI_REC_WPE_ATTR
 #endif
-__global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLaunch a) {
+// PRE: the records are resolved (dec_resolve_kernel ran over the call): the MB loop neither waits for nor
+// publishes granules 8..12 and calls no rule function; only an intra MB waits for the row above (its samples).
+template <bool PRE> DEV void dec_recon_body(const DecLaunch &a) {
     __shared__ union { DecLds r; DbkLds d; } SH;
     DecLds &S = SH.r;
     __shared__ int s_ticket;
@@ -473,7 +570,7 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
     GLOBAL const MbCoef *coefg = gbl((const MbCoef *)D.coef);
     GLOBAL uint64_t *egr = gbl(D.egran);
     int32_t *abort_word = &st->err;
-    if (a.streamed && !prog_wait(gbl(&D.frm->prog), a.tag, (uint32_t)mby + 1, abort_word)) return;
+    if (!PRE && a.streamed && !prog_wait(gbl(&D.frm->prog), a.tag, (uint32_t)mby + 1, abort_word)) return;
     const int mbw = a.mbw, cw = mbw * 16, ch = a.mbh * 16, ccw = cw / 2, cch = ch / 2;
     const int Y = mby * 16;
     GLOBAL uint64_t *grow_prev = gbl(D.gran) + (size_t)(mby > 0 ? mby - 1 : 0) * mbw * H264MI_GRANULES_PER_MB;
@@ -532,7 +629,7 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
         // reconstruction. Every MB needs the first group of (x+1, y-1) (vector and mode prediction); only
         // an intra MB needs the samples of (x-1..x+1, y-1), so inter MBs follow the row above at the
         // distance of its record resolution, not of its whole reconstruction.
-        if (mby > 0) {
+        if (!PRE && mby > 0) {
             uint32_t v;
             if (mbx == 0) {
                 if (!gran_wait(grow_prev + 8, 5, epoch, &v, abort_word)) return;
@@ -557,7 +654,8 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
         lap(2);
         // neighbour availability by slice: the record's slice word carries its slice's first MB
         const uint32_t nbm = uni(mb_nb_mask(mbx, mby, mbw, MB_SLICE_FIRST(rw31)));
-        if (rt == MI_PSKIP || rt == MI_P16x16) {
+        if (PRE) {
+        } else if (rt == MI_PSKIP || rt == MI_P16x16) {
             // one vector for the whole MB: the row below's granules straight from the scalar (record default
             // Intra4x4 modes 2, as the parse writes every non-I4 record), ahead of the LDS copy
             const uint32_t mvw = resolve_p16_uni(S, mbx, nbm, rt == MI_PSKIP);
@@ -568,11 +666,9 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
             if (lane == 0) resolve_record(S, mbx, nbm);
             wave_lds_sync();
         }
-        if (lane >= 8 && lane < 13 && !(rt == MI_PSKIP || rt == MI_P16x16)) {  // vectors of the bottom blocks, type and bottom Intra4x4 modes -> the row below
+        if (!PRE && lane >= 8 && lane < 13 && !(rt == MI_PSKIP || rt == MI_P16x16)) {  // vectors of the bottom blocks, type and bottom Intra4x4 modes -> the row below
             const MbInfo &R = S.info;
-            const uint32_t v = lane < 12 ? ((const uint32_t *)R.mv)[12 + lane - 8]
-                                         : (uint32_t)R.type | ((uint32_t)(R.i4mode[12] & 15) << 8) | ((uint32_t)(R.i4mode[13] & 15) << 12) |
-                                               ((uint32_t)(R.i4mode[14] & 15) << 16) | ((uint32_t)(R.i4mode[15] & 15) << 20);
+            const uint32_t v = lane < 12 ? ((const uint32_t *)R.mv)[12 + lane - 8] : res_type_word(R);
             gran_store(grow + (size_t)mbx * H264MI_GRANULES_PER_MB + lane, epoch, v);
         }
         if (lane < 32) gran_store(egr + (size_t)mbi * 128 + 96 + lane, epoch, ((const uint32_t *)&S.info)[lane]);  // -> deblocking row
@@ -770,7 +866,7 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
             gran_store(grow + (size_t)mbx * H264MI_GRANULES_PER_MB + lane, epoch, v);
         }
         if (lane < 16) { S.left[lane] = S.rec[lane * 16 + 15]; S.leftc[lane >> 3][lane & 7] = S.recc[lane >> 3][(lane & 7) * 8 + 7]; }
-        if (lane < 32) ((uint32_t *)&S.linfo)[lane] = ((const uint32_t *)&S.info)[lane];
+        if (!PRE && lane < 32) ((uint32_t *)&S.linfo)[lane] = ((const uint32_t *)&S.info)[lane];
         if (has_ref && mbx + 1 < mbw) {  // slide the window: MB x+1's new strip (columns X+40..X+55)
             const int nx = mbx + 1;
             *(u32x4 *)&S.win[lane * WIN_RING + ((16 * nx + 48) & 63)] = pf_w;
@@ -787,6 +883,8 @@ __global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLa
 #undef lane
 #endif
 }
+__global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_kernel(DecLaunch a) { dec_recon_body<false>(a); }
+__global__ __launch_bounds__(64) H264MI_REC_WPE_ATTR void dec_recon_pre_kernel(DecLaunch a) { dec_recon_body<true>(a); }
 
 // after reconstruction + loop filter: flip the picture ping-pong and mark a reference available
 // check: streamed reconstruction -- the picture's final decision first (dec_frame_check, dec_parse.inc)

@@ -25,7 +25,8 @@ enum { MI_I4 = 0, MI_I16 = 1, MI_P16x16 = 2, MI_PSKIP = 3, MI_P16x8 = 4, MI_P8x1
 // Per-macroblock side information (128 B). Written by the MB wavefront kernel (encoder) or the
 // parse kernel (decoder); read by CAVLC, reconstruction and deblocking. Decoder: the parse kernel
 // writes a raw record (i4mode = mode codes in decoding order, 0xff = predicted; mv = mvd at each
-// partition's first 4x4 block) and dec_recon_kernel rewrites it with resolved modes / vectors.
+// partition's first 4x4 block). dec_resolve_kernel rewrites it in place with resolved modes / vectors
+// before the reconstruction; in a streamed call dec_recon_kernel resolves its own copy instead.
 struct MbInfo {
     uint8_t type, qp, cbp, i16mode;
     uint8_t cmode, qpc, pad0, pad1;
@@ -191,7 +192,8 @@ struct DecFrame {          // per (frame slot, stream): written by dec_scan_kern
     int32_t hdr_ok;        // parameter sets and every slice header parsed, slice data to follow
     int32_t anyp;          // some slice is a P slice (needs a reference)
     int32_t cqp;           // chroma_qp_index_offset
-    int32_t pad_h[5];
+    int32_t res_abort;     // dec_resolve_kernel gave up on this picture (bounded wait): its records are not resolved
+    int32_t pad_h[4];
     DecParams ps;          // parameter sets in effect for this frame's slices (cropping for the output)
     NalEnt e[H264MI_MAX_NALS];
     SliceEnt sl[H264MI_MAX_SLICES];
@@ -230,4 +232,5 @@ struct DecDesc {
                             // H264MI_LPADX/Y margins, the encoder's geometry -- no half-sample planes: dec_recon.inc)
     uint8_t *plc[2];        // padded Cb, Cr
     int32_t ps, psc;
+    uint64_t *rgran;        // dec_resolve_kernel's row-to-row hand-off, 5 granules per MB (per frame slot)
 };

@@ -1,5 +1,6 @@
 // runtime_dec.inc -- host runtime of the decoder: HBM allocation and the per-call launch sequence
-//   dec_parse_kernel -> dec_recon_kernel -> deblock_kernel -> dec_end_kernel   (one stream order)
+//   dec_parse_kernel -> dec_resolve_kernel -> dec_recon_pre_kernel (+ deblocking rows) -> dec_end_kernel
+//   (a streamed call: dec_parse_kernel -> dec_recon_kernel, which resolves the records itself)
 namespace h264mi {
 
 constexpr int DEC_PSTREAMS = 3;      // default parse streams: consecutive calls rotate (each wants its own HW queue:
@@ -25,6 +26,14 @@ struct DecCtx {
     PlanesDesc *d_pd = nullptr;         // [S] reference planes of each stream
     DecInput *d_in = nullptr;           // [NG*B][S] access units (per slot)
     uint32_t *d_ticket = nullptr;       // 2 per frame slot (reconstruction, deblocking)
+    // record resolution ahead of the reconstruction (dec_resolve_kernel), for every call that is not streamed:
+    // one launch per call on its parse stream, behind the slice data (the reserved parse CUs; one launch per
+    // frame on the reconstruction stream gained nothing, profiles/dec_preresolve/placement_ab.txt). 0: never
+    // (the in-wavefront build, as a streamed call). Env H264MI_DEC_RESOLVE at creation, h264mi_dec_set_resolve.
+    int resolve = 1;
+    long long resolve_launches = 0;
+    uint32_t *d_rticket = nullptr;      // its ticket counters, never reset: one per slot group (a group's launches are
+    uint32_t rt_base[16] = {};          // ordered by ev_recon); the value each has before its next launch
     std::vector<DecDesc> h_desc;
     DecInput *h_in = nullptr;           // pinned: a pageable source would make hipMemcpyAsync block the
                                         // host until the parse stream reached the copy
@@ -58,7 +67,8 @@ struct DecCtx {
     size_t tight_cap = 0;
     uint64_t *d_prof = nullptr;  // parse section counters (env H264MI_PARSE_PROF=1), 16 per frame slot
     uint64_t *d_rprof = nullptr; // reconstruction section counters (env H264MI_RECON_PROF=1), 16 totals
-    // optional HIP-event timing for bench.py: [0] dec_recon_kernel (decoder stream), [1] dec_parse_kernel (parse streams)
+    // optional HIP-event timing for bench.py: [0] the reconstruction launch (decoder stream), [1] dec_parse_kernel and
+    // the resolution pass behind it (parse streams)
     bool timing = false;
     std::vector<hipEvent_t> tev[2];
     int tev_used[2] = {0, 0};
@@ -162,11 +172,12 @@ static DecCtx *dec_create(int mbw, int mbh, int S, hipStream_t stream, int B = 1
     const size_t off_pl = off_egr + al(8 * 128 * (size_t)c->nmb), off_plc = off_pl + al(lps * lph);
     const size_t per_stream = off_plc + 2 * al(cps * cph);
     const size_t off_coef = al(sizeof(MbInfo) * c->nmb), off_frm = off_coef + al(sizeof(MbCoef) * c->nmb);
-    const size_t per_slot = off_frm + al(sizeof(DecFrame));
+    const size_t off_rgr = off_frm + al(sizeof(DecFrame));
+    const size_t per_slot = off_rgr + al(8 * (size_t)H264MI_RES_GRANULES_PER_MB * c->nmb);
     const int NS = c->NG * B;  // frame slots: NG groups of B
     const size_t nsl = (size_t)S * NS;
     const size_t hdr = al(sizeof(DecState) * S) + al(sizeof(PlanesDesc) * S) + al(sizeof(DecDesc) * nsl) + al(sizeof(DbkDesc) * nsl) +
-                       al(sizeof(DecInput) * nsl) + al(sizeof(uint32_t) * 2 * NS);
+                       al(sizeof(DecInput) * nsl) + al(sizeof(uint32_t) * 2 * NS) + al(sizeof(uint32_t) * 16);
     const size_t total = hdr + per_stream * S + per_slot * nsl;
     if (hipMalloc(&c->d_pool, total) != hipSuccess) { if (c->own_stream) (void)hipStreamDestroy(c->stream); delete c; return nullptr; }
     c->pool_bytes = total;
@@ -178,6 +189,7 @@ static DecCtx *dec_create(int mbw, int mbh, int S, hipStream_t stream, int B = 1
     c->d_dbk = (DbkDesc *)p; p += al(sizeof(DbkDesc) * nsl);
     c->d_in = (DecInput *)p; p += al(sizeof(DecInput) * nsl);
     c->d_ticket = (uint32_t *)p; p += al(sizeof(uint32_t) * 2 * NS);
+    c->d_rticket = (uint32_t *)p; p += al(sizeof(uint32_t) * 16);
     uint8_t *streams = p, *slots = p + per_stream * S;
     c->h_desc.resize(nsl);
     if (hipHostMalloc((void **)&c->h_in, sizeof(DecInput) * nsl, hipHostMallocDefault) != hipSuccess) c->h_in = nullptr;
@@ -194,6 +206,7 @@ static DecCtx *dec_create(int mbw, int mbh, int S, hipStream_t stream, int B = 1
             d.gran = (uint64_t *)(b + off_gran); d.dgran = (uint64_t *)(b + off_dgran);
             d.info = (MbInfo *)q; d.coef = (MbCoef *)(q + off_coef); d.frm = (DecFrame *)(q + off_frm);
             d.st = c->d_st + s; d.cw = c->cw; d.ch = c->ch; d.egran = (uint64_t *)(b + off_egr);
+            d.rgran = (uint64_t *)(q + off_rgr);
             d.pl = b + off_pl + H264MI_LPADY * lps + H264MI_LPADX;
             for (int k = 0; k < 2; k++) d.plc[k] = b + off_plc + k * al(cps * cph) + H264MI_CPADY * cps + H264MI_CPADX;
             d.ps = (int)lps; d.psc = (int)cps;
@@ -234,6 +247,7 @@ static DecCtx *dec_create(int mbw, int mbh, int S, hipStream_t stream, int B = 1
         return nullptr;
     }
     dec_set_streamed(c, getenv("H264MI_DEC_STREAMED") ? atoi(getenv("H264MI_DEC_STREAMED")) : -1);
+    if (const char *e = getenv("H264MI_DEC_RESOLVE")) c->resolve = atoi(e) != 0;
     return c;
 }
 
@@ -258,6 +272,8 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
     const int S = c->S, ns = n * S, g = c->grp, slot0 = g * c->B;
     const uint32_t pin = c->calls & 1, tag = c->calls + 1;
     const int streamed = c->streamed;
+    // a streamed call reconstructs while its slice data is still being parsed: nothing can resolve ahead of it
+    const int pre = streamed ? 0 : c->resolve;
     hipStream_t ps = c->pst[c->calls % c->np];
     DecDesc *dd = c->d_desc + (size_t)slot0 * S;
     HIPCHECK(hipStreamWaitEvent(ps, c->ev_recon[g], 0));
@@ -278,6 +294,12 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
     hipLaunchKernelGGL(c->d_prof ? dec_parse_prof_kernel : dec_parse_kernel, dim3(ns * c->slice_waves), dim3(64), c->lds_bytes, ps,
                        DecParseLaunch{S, n, c->mbw, c->mbh, (int)pin, dd, c->d_prof ? c->d_prof + (size_t)slot0 * S * 16 : nullptr,
                                       c->slice_waves, tag, streamed});
+    if (pre) {  // every picture of the call, before ev_parsed
+        hipLaunchKernelGGL(dec_resolve_kernel, dim3(ns * c->mbh), dim3(64), 0, ps,
+                           DecResolveLaunch{ns, c->mbw, c->mbh, dd, c->d_rticket + g, c->rt_base[g], tag});
+        c->rt_base[g] += (uint32_t)(ns * c->mbh);
+        c->resolve_launches++;
+    }
     if (dec_time_mark(c, 1, ps)) return -1;
     HIPCHECK(hipEventRecord(c->ev_parsed[g], ps));
     // --- reconstruction (decoder stream), frames in order. Streamed: frame 0 starts once the headers are
@@ -295,7 +317,7 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
                                DecWaitLaunch{rg_counter, rg_target + (uint32_t)f * rg_step, rg_limit});
         // reconstruction rows and the deblocking rows that trail them, one launch
         if (dec_time_mark(c, 0, c->stream)) return -1;
-        hipLaunchKernelGGL(dec_recon_kernel, dim3(2 * S * c->mbh), dim3(64), 0, c->stream,
+        hipLaunchKernelGGL(pre ? dec_recon_pre_kernel : dec_recon_kernel, dim3(2 * S * c->mbh), dim3(64), 0, c->stream,
                            DecLaunch{S, c->mbw, c->mbh, df, c->d_ticket + 2 * (slot0 + f), c->d_dbk + (size_t)(slot0 + f) * S, c->d_rprof,
                                      tag, streamed});
         if (dec_time_mark(c, 0, c->stream)) return -1;

@@ -89,6 +89,8 @@ def lib():
             'h264mi_dec_set_slice_waves': (i, [vp, i]),
             'h264mi_dec_set_streamed': (i, [vp, i]),
             'h264mi_dec_streamed': (i, [vp]),
+            'h264mi_dec_set_resolve': (i, [vp, i]),
+            'h264mi_dec_resolve_launches': (ctypes.c_longlong, [vp]),
             'h264mi_dec_set_streamed_budget': (i, [i]),
             'h264mi_nal_pack': (i, [vp, vp, ctypes.c_size_t, vp, i, vp]),
             'h264mi_nal_unpack': (i, [vp, vp, ctypes.c_size_t, vp, i, vp]),
@@ -732,6 +734,15 @@ class BatchDecoder:
 
     def streamed(self):
         return self._L.h264mi_dec_streamed(self._d)
+
+    def set_resolve(self, mode):
+        """record resolution ahead of the reconstruction (h264mi_dec_set_resolve): 1 on the parse stream (default),
+        0 inside the reconstruction (what a streamed call always does)"""
+        if self._L.h264mi_dec_set_resolve(self._d, mode) != 0:
+            raise RuntimeError('h264mi_dec_set_resolve failed')
+
+    def resolve_launches(self):
+        return self._L.h264mi_dec_resolve_launches(self._d)
 
     def set_slice_waves(self, k):
         """slice-data waves per picture (h264mi_dec_set_slice_waves): a multi-slice picture's slices in parallel"""

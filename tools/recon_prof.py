@@ -1,6 +1,10 @@
 """dec_recon_kernel section profile (H264MI_RECON_PROF=1): S streams of 1080p IPPP encoded on the GPU and
 decoded one frame per call; prints the kernel's section cycles per reconstructed macroblock (summed over
-all row waves) and the launch time per frame.  usage: recon_prof.py [w h br S nf]"""
+all row waves) and the launch time per frame.  usage: recon_prof.py [w h br S nf resolve]
+resolve 1 (default): the records are resolved ahead (dec_resolve_kernel) and the pre-resolved build is profiled --
+its "row-above wait" is the intra macroblocks' sample wait alone and "record resolution" the hand-off to the
+deblocking row;
+0: the in-wavefront build, which a streamed call runs."""
 import os, sys
 os.environ['H264MI_RECON_PROF'] = '1'
 import numpy as np
@@ -11,7 +15,7 @@ NAMES = ['-', 'prefetch', 'row-above wait', 'record resolution', 'levels + neigh
          'luma prediction', 'chroma', 'outputs + window']
 
 
-def main(w=1920, h=1080, br=1000000, S=32, nf=8):
+def main(w=1920, h=1080, br=1000000, S=32, nf=8, resolve=1):
     import ctypes, time, torch
     import h264mi
     from h264mi.synth import SyntheticStream
@@ -19,6 +23,8 @@ def main(w=1920, h=1080, br=1000000, S=32, nf=8):
     enc = h264mi.BatchEncoder(w, h, br, S)
     enc.set_frame_skip(False)
     dec = h264mi.BatchDecoder(w, h, S, groups=2, parse_streams=1)
+    dec.set_streamed(0)  # (a small S would be streamed automatically: no resolution pass)
+    dec.set_resolve(resolve)
     dec.set_timing(True)
     L = h264mi.lib()
     prev = np.zeros(16, np.uint64)
@@ -39,7 +45,10 @@ def main(w=1920, h=1080, br=1000000, S=32, nf=8):
         print(f'frame {t}: rc={rc} call {dt * 1e3:.2f} ms; cycles per MB {tot / mbs:.0f}: ' +
               ', '.join(f'{NAMES[k]} {d[k] / mbs:.0f}' for k in range(1, 9)), flush=True)
     ms, n = dec.kernel_time(0)
-    print(f'dec_recon_kernel: {ms / max(n, 1):.3f} ms per launch over {n} launches ({S} streams)')
+    name = 'dec_recon_pre_kernel' if resolve else 'dec_recon_kernel'
+    print(f'{name}: {ms / max(n, 1):.3f} ms per launch over {n} launches ({S} streams)')
+    ms, n = dec.kernel_time(1)
+    print(f'dec_parse_kernel{" + dec_resolve_kernel" if resolve else ""}: {ms / max(n, 1):.3f} ms per launch over {n} launches')
 
 
 if __name__ == '__main__':
