@@ -705,6 +705,59 @@ int h264mi_enc_colorspec(h264mi_encoder *e, h264mi_colorspec *out);
 int h264mi_dec_set_output_colorspec(h264mi_decoder *d, const h264mi_colorspec *spec); /* NULL: the default */
 int h264mi_dec_output_colorspec(h264mi_decoder *d, h264mi_colorspec *out);
 
+/* Cleaning a picture on the device: a temporal denoiser for webcam-class streams, whose sensor noise
+   defeats the skip judge and fills P residuals. The library's own filter, exact integers, the same bytes on any host
+   (tests/denoiseref.py restates it in numpy). A frame is tight I420, w x h, both sides even, 2..8192. C is the current
+   frame, P the previous *filtered* frame, O the output.
+     strength_y, strength_c  0..224   the share of 256 of a vanishing difference that is removed; 0 leaves the luma
+                                      (chroma) planes as they are
+     reach                   1..32    differences of reach or more are kept
+     motion                  0..1020  the mean absolute luma difference of a block, in quarter levels, above which the
+                                      block counts as moving
+   Blocks: luma is cut into 8 x 8 blocks at multiples of 8; those at the right and lower edge are bw = min(8, w - 8bx) by
+   bh = min(8, h - 8by), both even. A block's chroma is the bw/2 x bh/2 rectangle at (4bx, 4by) of Cb and of Cr. Every
+   sample of the frame belongs to exactly one block.
+   Gate: sad = sum |C - P| over the block's luma samples, npix = bw * bh. The block is moving iff 4 * sad > motion * npix;
+   a moving block has O = C in all three planes.
+   A sample of a static block, K its plane's strength and T = reach: d = C - P, a = |d|. If a >= T then O = C. Otherwise
+   k = (K * (T - a)) / T (floor), m = (a * k + 128) >> 8, O = C - sign(d) * m.
+   Since k <= 224, a * k + 128 <= 224 a + 128 < 256 (a + 1), that is m <= a: O lies between P and C, and the rule has
+   no clamp.
+   Statistics, optional: four uint32_t per frame, {moving blocks, blocks, sum of m over luma, sum of m over both chroma
+   planes}; sums of integers, whatever the order (the largest is 31 * 8192 * 8192 < 2^32).
+   Not provided: spatial filtering, motion-compensated filtering, per-stream parameters, denoise inside compose cells,
+   decoder-side denoise. */
+typedef struct { int32_t strength_y, strength_c, reach, motion; } h264mi_denoise;
+/* host only: 0 when every field of *p is in its range, -1 otherwise (a null pointer included) */
+int h264mi_denoise_ok(const h264mi_denoise *p);
+/* async on hip_stream: n >= 1 frames at d_cur filtered against the n frames at d_prev into the n frames at d_dst, one
+   launch (and one memset when d_stats is given); no scratch memory. d_dst2, when not null, receives the same bytes as
+   d_dst; d_stats, when not null, is 4 n uint32_t on the device at a multiple of 4, zeroed by the call on the stream and
+   then accumulated. Any alignment of the frames. Each of d_dst and d_dst2 may be exactly d_cur or exactly d_prev;
+   otherwise it is disjoint from both sources, from d_stats and from the other destination (d_dst == d_dst2 is refused);
+   the sources are equal or disjoint. Returns 0, or -1 before anything is enqueued on: a null d_dst, d_cur, d_prev or p, an
+   odd side or one outside 2..8192, n < 1, a parameter out of range, d_stats at no multiple of 4, any other overlap. */
+int h264mi_i420_denoise_dev(void *d_dst, void *d_dst2, const void *d_cur, const void *d_prev, int w, int h, int n,
+                            const h264mi_denoise *p, void *d_stats, void *hip_stream);
+/* the encoder's pre-filter. With parameters set (NULL, or both strengths 0: off) the encoder owns a state of nstreams
+   frames -- device memory allocated when the filter is first turned on, freed when it is turned off and at destroy --
+   and every entry point that codes the input area (h264mi_enc_encode, which then copies the caller's frames into the
+   input area as with an overlay list, _rgba, _scaled, _oriented, _pix, _composed, _composed_any) runs, on the
+   encoder's stream and in this order: the denoiser, the overlay list in force, the frame step. The denoiser: with no
+   state yet the input area is copied to the state and coded as it is; otherwise one launch with cur = the input area,
+   prev = the state, dst = the input area, dst2 = the state. The state therefore never holds a sprite.
+     * The state advances on every submitted frame: also on one the rate control skips and on a frame step that fails.
+     * h264mi_enc_force_idr does not reset it.
+     * Turning the filter off drops the state: on again, the first frame is coded unfiltered. Setting other parameters
+       while it is on keeps the state.
+     * With quality records on, "source" is the input area as coded -- denoised, then blended --, as with overlays.
+     * Off (the default) nothing changes: no launch, no allocation. The drop-in functions (encode_frame ...) never filter.
+   h264mi_enc_set_denoise returns 0, or -1 with the setting in force unchanged on a null encoder, parameters
+   h264mi_denoise_ok refuses, or a failed allocation. h264mi_enc_denoise returns 1 (on, *out filled when out is not
+   null), 0 (off, *out untouched) or -1 (a null encoder). */
+int h264mi_enc_set_denoise(h264mi_encoder *e, const h264mi_denoise *p);
+int h264mi_enc_denoise(h264mi_encoder *e, h264mi_denoise *out);
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -190,19 +190,30 @@ int h264mi_enc_frames_skipped(h264mi_encoder *e, int stream) {
     if (hipMemcpy(&st, e->c->d_st + stream, sizeof(EncState), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return st.skipped;
 }
-// the tail of every entry point that codes the input area: the overlay list in force blended into it (DESIGN.md §5.6;
-// overlay.hip; nothing without a list), then the frame step
+// the tail of every entry point that codes the input area: the pre-filter in force (DESIGN.md §5.13; denoise.hip;
+// nothing when off) -- the first frame only copied to the state, every later one filtered in place against the state,
+// which receives the same bytes --, the overlay list in force blended into it (DESIGN.md §5.6; overlay.hip; nothing
+// without a list), then the frame step
 static int enc_code_input(EncCtx *c) {
+    if (c->dn_on) {
+        if (!c->dn_has) {
+            if (hipMemcpyAsync(c->d_dn, c->d_src, (size_t)c->S * c->fbytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
+            c->dn_has = true;
+        } else if (launch_denoise_i420(c->d_src, c->d_dn, c->d_src, c->d_dn, c->w, c->h, c->S, c->dn, nullptr, c->stream) != 0) {
+            return -1;
+        }
+    }
     if (!c->ov.empty() &&
         launch_overlay_i420(c->d_src, c->w, c->h, c->ov_sprites, c->ov_w, c->ov_h, c->ov.data(), (int)c->ov.size(), c->stream) != 0)
         return -1;
     return enc_frame(c, c->d_src);
 }
-// with an overlay list in force the caller's frames are copied into the input area, blended there and coded from there
+// with the pre-filter on or an overlay list in force the caller's frames are copied into the input area, filtered and
+// blended there and coded from there
 int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
     if (!e || !d_frames) return -1;
     EncCtx *c = e->c;
-    if (c->ov.empty()) return enc_frame(c, (const uint8_t *)d_frames);
+    if (c->ov.empty() && !c->dn_on) return enc_frame(c, (const uint8_t *)d_frames);
     if (d_frames != (const void *)c->d_src) {
         const size_t nb = (size_t)c->S * c->fbytes;
         if (byte_ranges_overlap(d_frames, nb, c->d_src, nb)) return -1;  // partly inside the input area
@@ -222,6 +233,42 @@ int h264mi_enc_set_overlays(h264mi_encoder *e, const void *d_sprites, int ow, in
     return 0;
 }
 int h264mi_enc_overlays(h264mi_encoder *e) { return e ? (int)e->c->ov.size() : -1; }
+// The temporal denoiser (DESIGN.md §5.13; denoise.hip; the checks: picture_host.h): n frames, one launch
+int h264mi_denoise_ok(const h264mi_denoise *p) { return denoise_ok(p) ? 0 : -1; }
+int h264mi_i420_denoise_dev(void *d_dst, void *d_dst2, const void *d_cur, const void *d_prev, int w, int h, int n, const h264mi_denoise *p,
+                            void *d_stats, void *hip_stream) {
+    if (!denoise_args_ok(d_dst, d_dst2, d_cur, d_prev, w, h, n, p, d_stats)) return -1;
+    return launch_denoise_i420((uint8_t *)d_dst, (uint8_t *)d_dst2, (const uint8_t *)d_cur, (const uint8_t *)d_prev, w, h, n, *p,
+                               (uint32_t *)d_stats, (hipStream_t)hip_stream);
+}
+// the encoder's pre-filter: NULL or both strengths 0 turn it off and free the state (after the stream has finished with
+// it); a refused call leaves the setting in force
+int h264mi_enc_set_denoise(h264mi_encoder *e, const h264mi_denoise *p) {
+    if (!e || (p && !denoise_ok(p))) return -1;
+    EncCtx *c = e->c;
+    if (!p || (p->strength_y == 0 && p->strength_c == 0)) {
+        if (c->d_dn) {
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipFree(c->d_dn);
+            c->d_dn = nullptr;
+        }
+        c->dn_on = c->dn_has = false;
+        return 0;
+    }
+    if (!canvas_ok(c->w, c->h)) return -1;
+    if (!c->d_dn) {
+        if (hipMalloc(&c->d_dn, (size_t)c->S * c->fbytes) != hipSuccess) { c->d_dn = nullptr; return -1; }
+        c->dn_has = false;
+    }
+    c->dn = *p;
+    c->dn_on = true;
+    return 0;
+}
+int h264mi_enc_denoise(h264mi_encoder *e, h264mi_denoise *out) {
+    if (!e) return -1;
+    if (e->c->dn_on && out) *out = e->c->dn;
+    return e->c->dn_on ? 1 : 0;
+}
 // Sprites from RGBA and the standalone blend (DESIGN.md §5.6; overlay.hip)
 int h264mi_rgba_to_i420a_dev(void *d_dst, const void *d_rgba, int w, int h, int n, void *hip_stream) {
     if (!d_dst || !d_rgba || ((uintptr_t)d_rgba & 3) || !rgba_to_i420a_args_ok(w, h, n)) return -1;

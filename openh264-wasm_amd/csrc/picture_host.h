@@ -1,5 +1,5 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip, colorspace.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, colorspace.hip, denoise.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
@@ -158,6 +158,45 @@ static inline const CsCoef &cs_coef(int matrix, int range) {
 // arguments of a conversion call under a specification, everything but the pointers' values
 static inline bool cs_args_ok(int w, int h, int n, const h264mi_colorspec *s) { return n > 0 && canvas_ok(w, h) && colorspec_ok(s); }
 
+// ---- the temporal denoiser (include/h264mi.h)
+constexpr int DENOISE_MAX_STRENGTH = 224, DENOISE_MAX_REACH = 32, DENOISE_MAX_MOTION = 1020;
+static inline bool denoise_ok(const h264mi_denoise *p) {
+    return p && p->strength_y >= 0 && p->strength_y <= DENOISE_MAX_STRENGTH && p->strength_c >= 0 && p->strength_c <= DENOISE_MAX_STRENGTH &&
+           p->reach >= 1 && p->reach <= DENOISE_MAX_REACH && p->motion >= 0 && p->motion <= DENOISE_MAX_MOTION;
+}
+// k of the sample rule for a difference a of good parameters: K (T - a) / T below the reach, 0 from it on
+static inline int denoise_k(int K, int T, int a) { return a < T ? K * (T - a) / T : 0; }
+// the tables of a launch: byte a of k[0..7] is luma's k[a], of k[8..15] chroma's, a = 0..31 (every a >= 32 has k = 0)
+struct DenoiseTables { uint32_t k[16]; };
+static_assert(sizeof(DenoiseTables) == 64, "the launch struct counts on it");
+static inline void denoise_tables(DenoiseTables *t, const h264mi_denoise &p) {
+    for (int pl = 0; pl < 2; pl++)
+        for (int w = 0; w < 8; w++) {
+            uint32_t v = 0;
+            for (int j = 0; j < 4; j++) v |= (uint32_t)denoise_k(pl ? p.strength_c : p.strength_y, p.reach, 4 * w + j) << (8 * j);
+            t->k[8 * pl + w] = v;
+        }
+}
+// arguments of a denoise call, the pointers' values included: good parameters, even sides from 2 within PIC_MAX_SIDE,
+// n >= 1, statistics at a multiple of 4; each destination exactly cur, exactly prev, or disjoint from both sources, the
+// statistics and the other destination; the sources equal or disjoint; the statistics disjoint from the sources
+static inline bool denoise_args_ok(const void *dst, const void *dst2, const void *cur, const void *prev, int w, int h, int n,
+                                   const h264mi_denoise *p, const void *stats) {
+    if (!dst || !cur || !prev || n < 1 || !canvas_ok(w, h) || !denoise_ok(p) || ((uintptr_t)stats & 3)) return false;
+    const size_t nb = (size_t)n * i420_bytes(w, h), sb = 16 * (size_t)n;
+    if (cur != prev && byte_ranges_overlap(cur, nb, prev, nb)) return false;
+    const void *d[2] = {dst, dst2};
+    for (int k = 0; k < 2; k++) {
+        if (!d[k]) continue;
+        if (d[k] != cur && byte_ranges_overlap(d[k], nb, cur, nb)) return false;
+        if (d[k] != prev && byte_ranges_overlap(d[k], nb, prev, nb)) return false;
+        if (stats && byte_ranges_overlap(d[k], nb, stats, sb)) return false;
+    }
+    if (dst2 && byte_ranges_overlap(dst, nb, dst2, nb)) return false;  // equal ones too
+    if (stats && (byte_ranges_overlap(cur, nb, stats, sb) || byte_ranges_overlap(prev, nb, stats, sb))) return false;
+    return true;
+}
+
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
 static inline int cell_kind(const h264mi_cell &c) {
@@ -260,6 +299,10 @@ int orient_size(int orient, int sw, int sh, int *dw, int *dh);
 int orient_compose(int first, int then);
 int orient_inverse(int orient);
 void orient_plane_host(int orient, const uint8_t *S, int pw, int ph, uint8_t *D);
+// denoise.hip: arguments as denoise_args_ok accepts them; stats: four words a frame, or null
+int launch_denoise_i420(uint8_t *dst, uint8_t *dst2, const uint8_t *cur, const uint8_t *prev, int w, int h, int n, const h264mi_denoise &p,
+                        uint32_t *stats, hipStream_t s);
+void denoise_frame_host(uint8_t *out, const uint8_t *cur, const uint8_t *prev, int w, int h, const h264mi_denoise &p, uint32_t *stats);
 // pixfmt.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);

@@ -199,6 +199,12 @@ struct EncCtx {
     // what h264mi_enc_encode_rgba converts under (h264mi_enc_set_colorspec; colorspace.hip). All 0: the wrapper's
     // conversion by color.inc's kernel, as before the specification existed
     h264mi_colorspec cs = {};
+    // the pre-filter in force (h264mi_enc_set_denoise; denoise.hip): its parameters, the S previous filtered frames
+    // (allocated when it is turned on, freed when it is turned off) and whether they hold a frame yet. Off: every
+    // frame step enqueues what it did before the filter existed
+    bool dn_on = false, dn_has = false;
+    h264mi_denoise dn = {};
+    uint8_t *d_dn = nullptr;
 };
 
 struct EncMbLaunch {  // enc_mb_kernel reads the source frames through this launch-time base
@@ -212,6 +218,7 @@ static void enc_free(EncCtx *c) {
     for (auto e : c->ev) (void)hipEventDestroy(e);
     (void)hipFree(c->d_pool);
     (void)hipFree(c->d_qual);
+    (void)hipFree(c->d_dn);
     (void)hipFree(c->d_prof);
     (void)hipFree(c->d_tl);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);

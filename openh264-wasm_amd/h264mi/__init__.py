@@ -167,6 +167,10 @@ def lib():
             'h264mi_enc_colorspec': (i, [vp, vp]),
             'h264mi_dec_set_output_colorspec': (i, [vp, vp]),
             'h264mi_dec_output_colorspec': (i, [vp, vp]),
+            'h264mi_denoise_ok': (i, [vp]),
+            'h264mi_i420_denoise_dev': (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp]),
+            'h264mi_enc_set_denoise': (i, [vp, vp]),
+            'h264mi_enc_denoise': (i, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -440,6 +444,25 @@ class BatchEncoder:
         if self._L.h264mi_enc_encode_composed_any(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
                                                   int(filter), y, cb, cr) != 0:
             raise ValueError(f'h264mi_enc_encode_composed_any refused {len(arr)} cells of {nsrc} sources {src_w}x{src_h} -> {self.w}x{self.h}')
+
+    def set_denoise(self, params):
+        """the pre-filter of every encode*() from its next call on (h264mi_enc_set_denoise): a Denoise, a
+        (strength_y, strength_c, reach, motion) tuple, or None for off (both strengths 0 are off too). On, the encoder
+        owns S frames of state -- the previous filtered frames --, filters the input area against them in front of
+        the overlay list and the frame step, and codes the first frame after it was turned on unfiltered; encode() then
+        codes a copy of the caller's frames, which stay as they are. Off drops the state. ValueError, with the setting
+        in force unchanged, on parameters denoise_ok refuses."""
+        d = _denoise_params(params)
+        if self._L.h264mi_enc_set_denoise(self._e, ctypes.byref(d) if d is not None else None) != 0:
+            raise ValueError(f'h264mi_enc_set_denoise refused {d!r}')
+
+    def denoise(self):
+        """the pre-filter in force: a Denoise (a copy), or None when it is off (h264mi_enc_denoise)"""
+        out = Denoise()
+        r = self._L.h264mi_enc_denoise(self._e, ctypes.byref(out))
+        if r < 0:
+            raise RuntimeError('h264mi_enc_denoise failed')
+        return out if r == 1 else None
 
     def set_overlays(self, sprites, ow, oh, nsprites, overlays):
         """sprites: uint8 CUDA tensor holding nsprites I420A sprites of ow x oh back to back (i420a_bytes each), any
@@ -1070,6 +1093,53 @@ def i420_orient(dst, src, sw, sh, n, orient, stream=None):
     if lib().h264mi_i420_orient_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), sw, sh, n, int(orient),
                                     _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: orientation {orient} of {n} frames {sw}x{sh}')
+
+
+class Denoise(ctypes.Structure):
+    """h264mi_denoise (include/h264mi.h): strength_y, strength_c 0..224 (the share of 256 of a vanishing difference that
+    is removed), reach 1..32 (differences of reach or more are kept), motion 0..1020 (the mean absolute luma difference
+    of an 8x8 block, in quarter levels, above which the block is left as it is). 16 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('strength_y', 'strength_c', 'reach', 'motion')]
+
+    def __repr__(self):
+        return 'Denoise(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
+
+
+def _denoise_params(params):
+    """None, a Denoise, or a Denoise from four integers"""
+    if params is None or isinstance(params, Denoise):
+        return params
+    return Denoise(*(int(v) for v in params))
+
+
+def denoise_ok(params):
+    """0 when every field of params (a Denoise or four integers) is in its range, else -1 (None included);
+    h264mi_denoise_ok, host only"""
+    d = _denoise_params(params)
+    return lib().h264mi_denoise_ok(ctypes.byref(d) if d is not None else None)
+
+
+def i420_denoise(dst, cur, prev, w, h, n, params, dst2=None, stats=None, stream=None):
+    """n tight w x h I420 frames (uint8 CUDA tensor cur, any alignment) filtered against the n previous filtered frames
+    (prev) into dst and, when given, the same bytes into dst2; one launch, async on stream (default: the current one);
+    h264mi_i420_denoise_dev. params: a Denoise or (strength_y, strength_c, reach, motion). stats, when given: a CUDA
+    tensor of 4 n 32-bit words, per frame {moving blocks, blocks, sum of m over luma, over both chroma planes}, zeroed
+    and then accumulated on the stream. dst and dst2 may each be exactly cur or exactly prev. The bytes equal
+    tests/denoiseref.py's. ValueError on a bad argument (a parameter out of range, a side that is odd or outside
+    2..8192, n < 1, any other overlap)."""
+    _assert_dev_u8(dst, cur, prev)
+    if dst2 is not None:
+        _assert_dev_u8(dst2)
+    need = 0 if n <= 0 or min(w, h) <= 0 else n * _i420_bytes(w, h)
+    assert all(t.numel() >= need for t in (dst, cur, prev) + ((dst2,) if dst2 is not None else ()))
+    if stats is not None:
+        assert stats.is_cuda and stats.is_contiguous() and stats.numel() * stats.element_size() >= 16 * max(n, 0)
+    d = _denoise_params(params)
+    if lib().h264mi_i420_denoise_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(dst2.data_ptr()) if dst2 is not None else None,
+                                     ctypes.c_void_p(cur.data_ptr()), ctypes.c_void_p(prev.data_ptr()), w, h, n,
+                                     ctypes.byref(d) if d is not None else None,
+                                     ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
 
 
 PIX_I420 = 0  # H264MI_PIX_*: planes Y (w x h), Cb, Cr (w/2 x h/2)

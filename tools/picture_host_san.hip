@@ -1,11 +1,11 @@
 // picture_host_san.hip -- the host rules of the picture calls (csrc/picture_host.h and the host halves of scale.hip,
-// compose.hip, overlay.hip, upscale.hip, orient.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
+// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
 // is loaded into Python, no kernel is launched, no device is needed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=all tools/picture_host_san.hip openh264-wasm_amd/csrc/scale.hip \
 //         openh264-wasm_amd/csrc/compose.hip openh264-wasm_amd/csrc/overlay.hip openh264-wasm_amd/csrc/upscale.hip \
-//         openh264-wasm_amd/csrc/orient.hip -o picture_host_san && ./picture_host_san
+//         openh264-wasm_amd/csrc/orient.hip openh264-wasm_amd/csrc/denoise.hip -o picture_host_san && ./picture_host_san
 //
 // It runs, with every table in a heap block of exactly the size the call may touch:
 //   * cells_ok (both values of may_enlarge) on valid lists and on every field of a cell made odd, negative, one past the
@@ -23,9 +23,13 @@
 //   * the pixel-layout rules (pix_span, pix_layout_ok, pix_layout_tight, pix_ranges_overlap): every verdict and span
 //     against a restatement in 128-bit arithmetic over random fields and extreme ones (INT32_MAX pitches, INT64_MAX
 //     offsets and strides, negative values), and the tight layouts and spans of the five formats against their byte counts.
+//   * denoise.hip's host restatement denoise_frame_host on heap blocks of exactly the frame's bytes at seven sizes (2x2
+//     and partial blocks among them), out of place and in place, against a per-sample restatement; the k tables at the
+//     limits of the parameters; denoise_ok and denoise_args_ok at their limits and one past each.
 // Prints one line per group and "ok"; exits 1 at the first difference.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <vector>
 #include "../openh264-wasm_amd/csrc/picture_host.h"
@@ -410,7 +414,105 @@ static void check_pix() {
     printf("pixel layouts: tight layouts of 5 formats x 6 sizes, %d random and extreme layouts (%d good)\n", cases, good);
 }
 
+// the sample rule and the gate restated sample by sample: every sample looks its own block up
+static void ref_denoise(std::vector<uint8_t> &out, const uint8_t *cur, const uint8_t *prev, int w, int h, const h264mi_denoise &p, uint32_t *st) {
+    const int nbx = (w + 7) / 8, nby = (h + 7) / 8;
+    std::vector<long long> sad((size_t)nbx * nby, 0);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) sad[(size_t)(y / 8) * nbx + x / 8] += llabs((long long)cur[(size_t)y * w + x] - prev[(size_t)y * w + x]);
+    st[0] = st[2] = st[3] = 0;
+    st[1] = (uint32_t)(nbx * nby);
+    auto moving = [&](int bx, int by) {
+        const long long bw = std::min(8, w - 8 * bx), bh = std::min(8, h - 8 * by);
+        return 4 * sad[(size_t)by * nbx + bx] > (long long)p.motion * bw * bh;
+    };
+    for (int by = 0; by < nby; by++)
+        for (int bx = 0; bx < nbx; bx++) st[0] += moving(bx, by);
+    const size_t ly = (size_t)w * h, lc = (size_t)(w / 2) * (h / 2);
+    for (size_t i = 0; i < ly + 2 * lc; i++) {
+        const int pl = i < ly ? 0 : i < ly + lc ? 1 : 2;
+        const size_t j = i - (pl == 0 ? 0 : pl == 1 ? ly : ly + lc);
+        const int pw = pl ? w / 2 : w, x = (int)(j % pw), y = (int)(j / pw);
+        const bool mv = pl ? moving(x / 4, y / 4) : moving(x / 8, y / 8);
+        const int K = pl ? p.strength_c : p.strength_y, c = cur[i], d = c - prev[i], a = d < 0 ? -d : d;
+        int m = 0;
+        if (!mv && a < p.reach) m = (a * ((K * (p.reach - a)) / p.reach) + 128) >> 8;
+        st[pl ? 3 : 2] += (uint32_t)m;
+        out[i] = (uint8_t)(d < 0 ? c + m : c - m);
+    }
+}
+
+static void check_denoise() {
+    const int sizes[][2] = {{2, 2}, {8, 8}, {10, 6}, {16, 16}, {36, 18}, {130, 66}, {264, 10}};
+    const h264mi_denoise sets[] = {{224, 224, 32, 1020}, {128, 64, 12, 24}, {224, 0, 12, 24}, {0, 0, 12, 24}, {128, 128, 1, 24}, {128, 128, 12, 0}};
+    int frames = 0;
+    for (const auto &s : sizes)
+        for (const h264mi_denoise &p : sets) {
+            const int w = s[0], h = s[1];
+            const size_t fb = i420_bytes(w, h);
+            std::unique_ptr<uint8_t[]> cur(new uint8_t[fb]), prev(new uint8_t[fb]), out(new uint8_t[fb]);  // exactly the frame's bytes
+            for (size_t i = 0; i < fb; i++) {
+                prev[i] = (uint8_t)pix_rng();
+                const int blk = (int)(i / 8) % 4;  // runs of 8 bytes: every fourth far from prev
+                cur[i] = blk == 3 ? (uint8_t)pix_rng() : (uint8_t)std::min(255, std::max(0, (int)prev[i] + (int)(pix_rng() % 11) - 5));
+            }
+            std::vector<uint8_t> want(fb);
+            uint32_t st_want[4], st[4] = {9, 9, 9, 9};
+            ref_denoise(want, cur.get(), prev.get(), w, h, p, st_want);
+            denoise_frame_host(out.get(), cur.get(), prev.get(), w, h, p, st);
+            CHECK(memcmp(out.get(), want.data(), fb) == 0);
+            CHECK(memcmp(st, st_want, sizeof st) == 0);
+            for (size_t i = 0; i < fb; i++) CHECK(std::min(cur[i], prev[i]) <= out[i] && out[i] <= std::max(cur[i], prev[i]));
+            denoise_frame_host(prev.get(), cur.get(), prev.get(), w, h, p, nullptr);  // in place over prev
+            CHECK(memcmp(prev.get(), want.data(), fb) == 0);
+            frames++;
+        }
+    // the tables: k at the limits, 0 from the reach on, m <= a for every entry
+    for (int K : {0, 1, 128, 224})
+        for (int T : {1, 2, 12, 31, 32}) {
+            std::unique_ptr<DenoiseTables> t(new DenoiseTables);
+            const h264mi_denoise p{K, 224 - K, T, 0};
+            denoise_tables(t.get(), p);
+            for (int a = 0; a < 32; a++) {
+                const int ky = (t->k[a / 4] >> (8 * (a % 4))) & 255, kc = (t->k[8 + a / 4] >> (8 * (a % 4))) & 255;
+                CHECK(ky == (a < T ? K * (T - a) / T : 0) && kc == (a < T ? (224 - K) * (T - a) / T : 0));
+                CHECK(ky <= 224 && kc <= 224 && ((a * ky + 128) >> 8) <= a && ((a * kc + 128) >> 8) <= a);
+            }
+            CHECK((t->k[0] & 255) == (uint32_t)K);
+        }
+    // the scalar checks at their limits and one past each
+    const h264mi_denoise lo{0, 0, 1, 0}, hi{224, 224, 32, 1020};
+    CHECK(denoise_ok(&lo) && denoise_ok(&hi) && !denoise_ok(nullptr));
+    for (int f = 0; f < 4; f++) {
+        h264mi_denoise a = lo, b = hi;
+        ((int32_t *)&a)[f]--; ((int32_t *)&b)[f]++;
+        CHECK(!denoise_ok(&a) && !denoise_ok(&b));
+        a = lo; ((int32_t *)&a)[f] = INT32_MIN; b = hi; ((int32_t *)&b)[f] = INT32_MAX;
+        CHECK(!denoise_ok(&a) && !denoise_ok(&b));
+    }
+    const uintptr_t D = 0x10000000u, D2 = 0x20000000u, C = 0x30000000u, P = 0x40000000u, S = 0x50000000u;
+    auto ok = [&](uintptr_t d, uintptr_t d2, uintptr_t c, uintptr_t p, int w, int h, int n, const h264mi_denoise *q, uintptr_t s) {
+        return denoise_args_ok((const void *)d, (const void *)d2, (const void *)c, (const void *)p, w, h, n, q, (const void *)s);
+    };
+    const size_t nb = 3 * i420_bytes(32, 16);
+    CHECK(ok(D, D2, C, P, 32, 16, 3, &hi, S) && ok(D, 0, C, P, 32, 16, 3, &hi, 0) && ok(D, D2, C, P, 8192, 8192, 1, &lo, S) && ok(D, 0, C, P, 2, 2, 1, &lo, 0));
+    CHECK(ok(C, 0, C, P, 32, 16, 3, &hi, S) && ok(P, 0, C, P, 32, 16, 3, &hi, S) && ok(C, P, C, P, 32, 16, 3, &hi, S) && ok(P, C, C, P, 32, 16, 3, &hi, S));
+    CHECK(ok(D, 0, C, C, 32, 16, 3, &hi, S) && ok(C, 0, C, C, 32, 16, 3, &hi, S));
+    CHECK(!ok(0, D2, C, P, 32, 16, 3, &hi, S) && !ok(D, D2, 0, P, 32, 16, 3, &hi, S) && !ok(D, D2, C, 0, 32, 16, 3, &hi, S) && !ok(D, D2, C, P, 32, 16, 3, nullptr, S));
+    CHECK(!ok(D, D2, C, P, 32, 16, 0, &hi, S) && !ok(D, D2, C, P, 31, 16, 3, &hi, S) && !ok(D, D2, C, P, 32, 8194, 3, &hi, S) && !ok(D, D2, C, P, 0, 16, 3, &hi, S));
+    CHECK(!ok(D, D, C, P, 32, 16, 3, &hi, S) && !ok(C, C, C, P, 32, 16, 3, &hi, S));
+    for (uintptr_t off : {(uintptr_t)1, (uintptr_t)(nb - 1), (uintptr_t)-1, (uintptr_t)-(intptr_t)(nb - 1)}) {
+        CHECK(!ok(C + off, D2, C, P, 32, 16, 3, &hi, S) && !ok(P + off, D2, C, P, 32, 16, 3, &hi, S) && !ok(D2 + off, D2, C, P, 32, 16, 3, &hi, S));
+        CHECK(!ok(D, C + off, C, P, 32, 16, 3, &hi, S) && !ok(D, P + off, C, P, 32, 16, 3, &hi, S) && !ok(D, D2, P + off, P, 32, 16, 3, &hi, S));
+    }
+    CHECK(ok(D, D2, C, P, 32, 16, 3, &hi, D + nb) && ok(D, D2, C, P, 32, 16, 3, &hi, D - 48));  // touching
+    for (uintptr_t b : {D, D2, C, P}) CHECK(!ok(D, D2, C, P, 32, 16, 3, &hi, b) && !ok(D, D2, C, P, 32, 16, 3, &hi, b + nb - 4) && !ok(D, D2, C, P, 32, 16, 3, &hi, b - 44));
+    for (uintptr_t off : {1, 2, 3}) CHECK(!ok(D, D2, C, P, 32, 16, 3, &hi, S + off));
+    printf("denoise: %d frames at 7 sizes x 6 parameter sets out of place and in place, tables, scalar and range checks\n", frames);
+}
+
 int main() {
+    check_denoise();
     check_pix();
     check_orient();
     check_cells();
