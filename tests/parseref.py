@@ -437,6 +437,13 @@ class Parsed:
         self.syntax, self.geometry, self.size, self.counts, self.ref_idc = pic.syntax, (pic.mbw, pic.mbh), size, counts, ref_idc
         self._words = pic.words
 
+    def words(self, mb):
+        """the logged code words of macroblock mb: (name, first bit, one past the last bit, value), positions in its
+        slice's RBSP, in stream order, an mb_skip_run in front of the macroblock included. tests/writeaudit.py cuts a
+        macroblock into its residual blocks by these names: a block opens with the word whose name holds 'coeff_token',
+        and the run is named 'mb_skip_run' (tests/test_enc_write_audit.py holds both names to a written block)"""
+        return list(self._words.get(mb, []))
+
     def explain(self, mb):
         """the code words of macroblock mb: 'bits a..b name = value', positions in its slice's RBSP"""
         return [f'bits {a}..{b - 1} {name} = {v}' for name, a, b, v in self._words.get(mb, [])]
