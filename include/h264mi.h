@@ -758,6 +758,82 @@ int h264mi_i420_denoise_dev(void *d_dst, void *d_dst2, const void *d_cur, const 
 int h264mi_enc_set_denoise(h264mi_encoder *e, const h264mi_denoise *p);
 int h264mi_enc_denoise(h264mi_encoder *e, h264mi_denoise *out);
 
+/* Scene cuts on the device and the encoder's key-frame policy. The library's own rule, exact
+   integers, the same words on any host (tests/scenecutref.py restates it in numpy). A frame is tight I420, w x h, both
+   sides even, 2..8192; only luma is read.
+   Thumbnail: luma is cut into 4 x 4 cells at multiples of 4; the cells at the right and lower edge are 2 or 4 wide and
+   high, so a cell holds npix = 4, 8 or 16 samples. T = (sum + npix / 2) / npix, a shift. The thumbnail is tw x th =
+   ceil(w / 4) x ceil(h / 4) bytes, tight (h264mi_thumb_size).
+   Blocks: the thumbnail is cut into blocks of 8 x 8 cells (32 x 32 luma) at multiples of 8; those at the edge are
+   bw = min(8, tw - 8bx) by bh = min(8, th - 8by) cells, ncell = bw * bh. Per block, Tc the current frame's thumbnail
+   and Tp the previous frame's: sad = sum |Tc - Tp|, dsum = |sum Tc - sum Tp|, so dsum <= sad.
+   Gate: m = compensate ? sad - dsum : sad; the block is changed iff 4 * m > level * ncell. With compensate on, a
+   uniform brightness step (a fade, a flash, an exposure change) changes no block.
+   Statistics: eight uint32_t per frame, {changed blocks, blocks, sum of sad, sum of Tc, sum of Tp, 0, 0, 0}; sums of
+   integers, whatever the order (the largest is 255 * 2048 * 2048 < 2^32).
+   Cut test: cut iff 256 * changed > share * blocks (h264mi_scenecut_is_cut; the device evaluates the same expression).
+     level       0..1020   the mean absolute thumbnail difference of a block, in quarter levels, above which it is changed
+     share       0..256    the share of 256 of the frame's blocks that must be changed; 0: detection off
+     min_gap     0..65535  no cut key frame nearer than this many frames to the last key frame
+     max_gap     0..65535  a key frame at the latest this many frames after the last one; 0: no period
+     compensate  0, 1
+   The documented default is {level 64, share 128, min_gap 4, max_gap 0, compensate 1}: on the clips of
+   tests/test_scenecut_host.py (a pan with noise of +-3, a fade of 4 levels a frame, content switches) it names exactly
+   the switches.
+   Not provided: per-stream parameters, chroma in the detector, motion-compensated detection, lookahead (moving the
+   IDR earlier), non-IDR I frames. */
+typedef struct { int32_t level, share, min_gap, max_gap, compensate; } h264mi_scenecut;
+/* host only: 0 when every field of *p is in its range, -1 otherwise (a null pointer included) */
+int h264mi_scenecut_ok(const h264mi_scenecut *p);
+/* host only: *tw, *th of a w x h frame; 0, or -1 (nothing written) on a null pointer, an odd side or one outside 2..8192 */
+int h264mi_thumb_size(int w, int h, int *tw, int *th);
+/* host only: 1 when the eight statistics words of a frame are a cut under *p, 0 when not (share 0 included), -1 on a
+   null pointer or parameters h264mi_scenecut_ok refuses */
+int h264mi_scenecut_is_cut(const h264mi_scenecut *p, const uint32_t stats[8]);
+/* async on hip_stream: the thumbnails of the n >= 1 frames at d_cur into d_thumb_out (n * tw * th bytes) and, against
+   the n thumbnails at d_thumb_prev, their statistics into d_stats (8 n uint32_t on the device at a multiple of 4, zeroed
+   by the call on the stream and then accumulated): one launch, plus one memset when d_stats is given; no scratch
+   memory. Any alignment of the frames and thumbnails. d_thumb_prev NULL: only thumbnails are written, and d_stats must
+   be NULL too. d_thumb_out may be exactly d_thumb_prev (the thumbnails advance in place), or NULL for statistics only;
+   with d_thumb_prev given, d_stats NULL computes the thumbnails only. Returns 0, or -1 before anything is enqueued on:
+   a null d_cur or p, both outputs null, d_stats without d_thumb_prev, an odd side or one outside 2..8192, n < 1, a
+   parameter out of range, d_stats at no multiple of 4, any overlap of two of the five ranges other than
+   d_thumb_out == d_thumb_prev. */
+int h264mi_i420_scenecut_dev(void *d_stats, void *d_thumb_out, const void *d_cur, const void *d_thumb_prev, int w, int h, int n,
+                             const h264mi_scenecut *p, void *hip_stream);
+/* the encoder's key-frame policy. With parameters set (NULL, or share == 0 and max_gap == 0: off) every entry point
+   that codes the input area (h264mi_enc_encode, which then copies the caller's frames into the input area as with an
+   overlay list, _rgba, _scaled, _oriented, _pix, _composed, _composed_any) runs, on the encoder's stream and in this
+   order: the denoiser, the detector and the decision, the overlay list in force, the frame step. A clock or label
+   sprite therefore never reaches the detector, and the denoised picture does. The decision is one thread per stream
+   on the device: no host round trip. dist is the number of frames submitted since the last key frame (0 on one):
+     other  = the stream's first frame, a pending h264mi_enc_force_idr, or the restart after a failed frame
+     period = max_gap > 0 && dist_prev + 1 >= max_gap
+     cut    = share > 0 && a previous thumbnail exists && is_cut(statistics) && dist_prev + 1 >= min_gap
+     key    = other || period || cut;  a key frame is coded as an IDR and has dist = 0, any other dist = dist_prev + 1
+     reason = other ? 3 : period ? 2 : cut ? 1 : 0
+   State per stream: one thumbnail and sixteen words, device memory allocated when the policy is first turned on, freed
+   when it is turned off and at destroy; with share == 0 (period only) there is no thumbnail (one held from an earlier
+   setting is freed) and no detector launch.
+     * The thumbnail state advances on every submitted frame: also on one the rate control skips and on a frame step
+       whose kernels report an error. An entry point that returns -1 has submitted no frame; whether the state has
+       advanced by then is unspecified.
+     * The first frame after the policy is turned on only stores a thumbnail: its statistics are 0 and it is no cut.
+     * A key frame is never skipped by the rate control.
+     * Setting other parameters while the policy is on keeps the state; changing share from or to 0 keeps the words and
+       starts the thumbnails afresh. Turning it off drops the state.
+     * Off (the default) nothing changes: no launch, no allocation. The drop-in functions (encode_frame ...) never
+       use the policy.
+   h264mi_enc_set_scenecut returns 0, or -1 with the setting in force unchanged on a null encoder, parameters
+   h264mi_scenecut_ok refuses, or a failed allocation. h264mi_enc_scenecut returns 1 (on, *out filled when out is not
+   null), 0 (off, *out untouched) or -1 (a null encoder). h264mi_enc_scenecut_state waits for the encoder's stream and
+   fills out16 with the last submitted frame's eight statistics words, then {cut, key, reason, dist, keys by cut, keys
+   by period, other keys, frames submitted} since the policy was turned on; 0, or -1 on a null pointer, a stream out
+   of range or the policy off. */
+int h264mi_enc_set_scenecut(h264mi_encoder *e, const h264mi_scenecut *p);
+int h264mi_enc_scenecut(h264mi_encoder *e, h264mi_scenecut *out);
+int h264mi_enc_scenecut_state(h264mi_encoder *e, int stream, uint32_t *out16);
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -192,8 +192,9 @@ int h264mi_enc_frames_skipped(h264mi_encoder *e, int stream) {
 }
 // the tail of every entry point that codes the input area: the pre-filter in force (DESIGN.md §5.13; denoise.hip;
 // nothing when off) -- the first frame only copied to the state, every later one filtered in place against the state,
-// which receives the same bytes --, the overlay list in force blended into it (DESIGN.md §5.6; overlay.hip; nothing
-// without a list), then the frame step
+// which receives the same bytes --, the key-frame policy in force (below), the overlay list in force blended into it
+// (DESIGN.md §5.6; overlay.hip; nothing without a list), then the frame step. A launch that fails ends the call with
+// -1 where it stands: no frame is submitted, and the states of the steps in front of it have advanced
 static int enc_code_input(EncCtx *c) {
     if (c->dn_on) {
         if (!c->dn_has) {
@@ -203,17 +204,31 @@ static int enc_code_input(EncCtx *c) {
             return -1;
         }
     }
+    // the key-frame policy in force (DESIGN.md §5.14; scenecut.hip; nothing when off): the detector -- the first frame
+    // only stores its thumbnails, every later one advances them in place and leaves its statistics; no launch with
+    // share == 0 --, then the decision, which sets EncState::force_idr in front of the frame step's begin kernel
+    if (c->sc_on) {
+        uint32_t *stats = nullptr;
+        if (c->sc.share > 0) {
+            const bool has = c->sc_has;
+            if (has) stats = c->d_sc + 16 * (size_t)c->S;
+            if (launch_scenecut_i420(stats, c->d_sc_thumb, c->d_src, has ? c->d_sc_thumb : nullptr, c->w, c->h, c->S, c->sc, c->stream) != 0)
+                return -1;
+            c->sc_has = true;
+        }
+        if (launch_scenecut_decide(c->d_st, c->d_sc, stats, c->S, c->sc, c->stream) != 0) return -1;
+    }
     if (!c->ov.empty() &&
         launch_overlay_i420(c->d_src, c->w, c->h, c->ov_sprites, c->ov_w, c->ov_h, c->ov.data(), (int)c->ov.size(), c->stream) != 0)
         return -1;
     return enc_frame(c, c->d_src);
 }
-// with the pre-filter on or an overlay list in force the caller's frames are copied into the input area, filtered and
-// blended there and coded from there
+// with the pre-filter or the key-frame policy on or an overlay list in force the caller's frames are copied into the
+// input area, filtered, looked at and blended there and coded from there
 int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
     if (!e || !d_frames) return -1;
     EncCtx *c = e->c;
-    if (c->ov.empty() && !c->dn_on) return enc_frame(c, (const uint8_t *)d_frames);
+    if (c->ov.empty() && !c->dn_on && !c->sc_on) return enc_frame(c, (const uint8_t *)d_frames);
     if (d_frames != (const void *)c->d_src) {
         const size_t nb = (size_t)c->S * c->fbytes;
         if (byte_ranges_overlap(d_frames, nb, c->d_src, nb)) return -1;  // partly inside the input area
@@ -268,6 +283,70 @@ int h264mi_enc_denoise(h264mi_encoder *e, h264mi_denoise *out) {
     if (!e) return -1;
     if (e->c->dn_on && out) *out = e->c->dn;
     return e->c->dn_on ? 1 : 0;
+}
+// The scene-cut detector (DESIGN.md §5.14; scenecut.hip; the checks: picture_host.h): n frames, one launch
+int h264mi_scenecut_ok(const h264mi_scenecut *p) { return scenecut_ok(p) ? 0 : -1; }
+int h264mi_thumb_size(int w, int h, int *tw, int *th) {
+    if (!tw || !th || !canvas_ok(w, h)) return -1;
+    *tw = thumb_side(w); *th = thumb_side(h);
+    return 0;
+}
+int h264mi_scenecut_is_cut(const h264mi_scenecut *p, const uint32_t stats[8]) {
+    if (!stats || !scenecut_ok(p)) return -1;
+    return scenecut_is_cut(p->share, stats[0], stats[1]) ? 1 : 0;
+}
+int h264mi_i420_scenecut_dev(void *d_stats, void *d_thumb_out, const void *d_cur, const void *d_thumb_prev, int w, int h, int n,
+                             const h264mi_scenecut *p, void *hip_stream) {
+    if (!scenecut_args_ok(d_stats, d_thumb_out, d_cur, d_thumb_prev, w, h, n, p)) return -1;
+    return launch_scenecut_i420((uint32_t *)d_stats, (uint8_t *)d_thumb_out, (const uint8_t *)d_cur, (const uint8_t *)d_thumb_prev, w, h, n, *p,
+                                (hipStream_t)hip_stream);
+}
+// the encoder's key-frame policy: NULL or share == 0 && max_gap == 0 turn it off and free the state (after the stream
+// has finished with it); a refused call leaves the setting in force
+int h264mi_enc_set_scenecut(h264mi_encoder *e, const h264mi_scenecut *p) {
+    if (!e || (p && !scenecut_ok(p))) return -1;
+    EncCtx *c = e->c;
+    if (!p || (p->share == 0 && p->max_gap == 0)) {
+        if (c->d_sc || c->d_sc_thumb) {
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipFree(c->d_sc);
+            (void)hipFree(c->d_sc_thumb);
+            c->d_sc = nullptr; c->d_sc_thumb = nullptr;
+        }
+        c->sc_on = c->sc_has = false;
+        return 0;
+    }
+    if (!canvas_ok(c->w, c->h)) return -1;
+    uint32_t *words = c->d_sc;
+    uint8_t *thumb = c->d_sc_thumb;
+    if (!words) {  // 16 words a stream, then 8 statistics words a stream
+        if (hipMalloc(&words, 24 * sizeof(uint32_t) * (size_t)c->S) != hipSuccess) return -1;
+        if (hipMemsetAsync(words, 0, 24 * sizeof(uint32_t) * (size_t)c->S, c->stream) != hipSuccess) { (void)hipFree(words); return -1; }
+    }
+    if (p->share > 0 && !thumb && hipMalloc(&thumb, (size_t)c->S * thumb_bytes(c->w, c->h)) != hipSuccess) {
+        if (!c->d_sc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(words); }
+        return -1;
+    }
+    if (p->share == 0 && thumb) {  // period only: no detector runs, the thumbnails of an earlier setting go
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(thumb);
+        thumb = nullptr;
+    }
+    if (!c->d_sc_thumb || !thumb) c->sc_has = false;
+    c->d_sc = words; c->d_sc_thumb = thumb;
+    c->sc = *p;
+    c->sc_on = true;
+    return 0;
+}
+int h264mi_enc_scenecut(h264mi_encoder *e, h264mi_scenecut *out) {
+    if (!e) return -1;
+    if (e->c->sc_on && out) *out = e->c->sc;
+    return e->c->sc_on ? 1 : 0;
+}
+int h264mi_enc_scenecut_state(h264mi_encoder *e, int stream, uint32_t *out16) {
+    if (!e || !out16 || !e->c->sc_on || stream < 0 || stream >= e->c->S) return -1;
+    if (hipMemcpyAsync(out16, e->c->d_sc + 16 * (size_t)stream, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->c->stream) != hipSuccess) return -1;
+    return hipStreamSynchronize(e->c->stream) == hipSuccess ? 0 : -1;
 }
 // Sprites from RGBA and the standalone blend (DESIGN.md §5.6; overlay.hip)
 int h264mi_rgba_to_i420a_dev(void *d_dst, const void *d_rgba, int w, int h, int n, void *hip_stream) {

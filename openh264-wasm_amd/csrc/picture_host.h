@@ -1,5 +1,5 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip, colorspace.hip, denoise.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, colorspace.hip, denoise.hip, scenecut.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
@@ -11,6 +11,7 @@
 #include "../../include/h264mi.h"
 
 struct EncDesc;  // h264mi_types.h
+struct EncState;
 struct DecDesc;
 struct DecInput;
 
@@ -197,6 +198,38 @@ static inline bool denoise_args_ok(const void *dst, const void *dst2, const void
     return true;
 }
 
+// ---- the scene-cut detector (include/h264mi.h)
+constexpr int SCENECUT_MAX_LEVEL = 1020, SCENECUT_MAX_SHARE = 256, SCENECUT_MAX_GAP = 65535;
+static inline bool scenecut_ok(const h264mi_scenecut *p) {
+    return p && p->level >= 0 && p->level <= SCENECUT_MAX_LEVEL && p->share >= 0 && p->share <= SCENECUT_MAX_SHARE && p->min_gap >= 0 &&
+           p->min_gap <= SCENECUT_MAX_GAP && p->max_gap >= 0 && p->max_gap <= SCENECUT_MAX_GAP && (uint32_t)p->compensate <= 1;
+}
+static inline int thumb_side(int v) { return (v + 3) / 4; }
+static inline size_t thumb_bytes(int w, int h) { return (size_t)thumb_side(w) * thumb_side(h); }
+// the cut test of a frame's statistics, the one expression of the host and of the decision kernel: changed <= 65536
+// blocks and share <= 256, so neither product leaves 32 bits
+__host__ __device__ static inline bool scenecut_is_cut(int share, uint32_t changed, uint32_t blocks) {
+    return share > 0 && 256u * changed > (uint32_t)share * blocks;
+}
+// arguments of a scene-cut call, the pointers' values included: good parameters, even sides from 2 within
+// PIC_MAX_SIDE, n >= 1, an output, statistics only with previous thumbnails and at a multiple of 4; of the frames, the
+// two thumbnail ranges and the statistics no two share a byte, but that thumb_out may be exactly thumb_prev
+static inline bool scenecut_args_ok(const void *stats, const void *thumb_out, const void *cur, const void *thumb_prev, int w, int h, int n,
+                                    const h264mi_scenecut *p) {
+    if (!cur || (!stats && !thumb_out) || (stats && !thumb_prev) || n < 1 || !canvas_ok(w, h) || !scenecut_ok(p) || ((uintptr_t)stats & 3))
+        return false;
+    const size_t fb = (size_t)n * i420_bytes(w, h), tb = (size_t)n * thumb_bytes(w, h), sb = 32 * (size_t)n;
+    const void *r[4] = {cur, thumb_out, thumb_prev, stats};
+    const size_t rb[4] = {fb, tb, tb, sb};
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++) {
+            if (!r[a] || !r[b]) continue;
+            if (a == 1 && b == 2 && r[a] == r[b]) continue;
+            if (byte_ranges_overlap(r[a], rb[a], r[b], rb[b])) return false;
+        }
+    return true;
+}
+
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
 static inline int cell_kind(const h264mi_cell &c) {
@@ -303,6 +336,14 @@ void orient_plane_host(int orient, const uint8_t *S, int pw, int ph, uint8_t *D)
 int launch_denoise_i420(uint8_t *dst, uint8_t *dst2, const uint8_t *cur, const uint8_t *prev, int w, int h, int n, const h264mi_denoise &p,
                         uint32_t *stats, hipStream_t s);
 void denoise_frame_host(uint8_t *out, const uint8_t *cur, const uint8_t *prev, int w, int h, const h264mi_denoise &p, uint32_t *stats);
+// scenecut.hip: arguments as scenecut_args_ok accepts them; stats: eight words a frame, or null. scenecut_frame_host:
+// one frame as plain loops, thumb_out (may be thumb_prev, or null) and stats (null without thumb_prev) as in the call
+int launch_scenecut_i420(uint32_t *stats, uint8_t *thumb_out, const uint8_t *cur, const uint8_t *thumb_prev, int w, int h, int n,
+                         const h264mi_scenecut &p, hipStream_t s);
+void scenecut_frame_host(uint32_t *stats, uint8_t *thumb_out, const uint8_t *cur, const uint8_t *thumb_prev, int w, int h, const h264mi_scenecut &p);
+// the decision of S streams, one thread each: st and words (16 a stream) on the device; stats eight words a stream
+// on the device, or null (no detector ran: no thumbnail yet, or share == 0)
+int launch_scenecut_decide(EncState *st, uint32_t *words, const uint32_t *stats, int S, const h264mi_scenecut &p, hipStream_t s);
 // pixfmt.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);

@@ -205,6 +205,14 @@ struct EncCtx {
     bool dn_on = false, dn_has = false;
     h264mi_denoise dn = {};
     uint8_t *d_dn = nullptr;
+    // the key-frame policy in force (h264mi_enc_set_scenecut; scenecut.hip): its parameters, per stream sixteen words
+    // and eight statistics words (d_sc, 24 S words, allocated when it is turned on, freed when it is turned off), the S
+    // thumbnails (d_sc_thumb, only with share > 0) and whether they hold a frame yet. Off: every frame step enqueues
+    // what it did before the policy existed
+    bool sc_on = false, sc_has = false;
+    h264mi_scenecut sc = {};
+    uint32_t *d_sc = nullptr;
+    uint8_t *d_sc_thumb = nullptr;
 };
 
 struct EncMbLaunch {  // enc_mb_kernel reads the source frames through this launch-time base
@@ -219,6 +227,8 @@ static void enc_free(EncCtx *c) {
     (void)hipFree(c->d_pool);
     (void)hipFree(c->d_qual);
     (void)hipFree(c->d_dn);
+    (void)hipFree(c->d_sc);
+    (void)hipFree(c->d_sc_thumb);
     (void)hipFree(c->d_prof);
     (void)hipFree(c->d_tl);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);

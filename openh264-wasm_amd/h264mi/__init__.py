@@ -171,6 +171,13 @@ def lib():
             'h264mi_i420_denoise_dev': (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp]),
             'h264mi_enc_set_denoise': (i, [vp, vp]),
             'h264mi_enc_denoise': (i, [vp, vp]),
+            'h264mi_scenecut_ok': (i, [vp]),
+            'h264mi_thumb_size': (i, [i, i, vp, vp]),
+            'h264mi_scenecut_is_cut': (i, [vp, vp]),
+            'h264mi_i420_scenecut_dev': (i, [vp, vp, vp, vp, i, i, i, vp, vp]),
+            'h264mi_enc_set_scenecut': (i, [vp, vp]),
+            'h264mi_enc_scenecut': (i, [vp, vp]),
+            'h264mi_enc_scenecut_state': (i, [vp, i, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -463,6 +470,35 @@ class BatchEncoder:
         if r < 0:
             raise RuntimeError('h264mi_enc_denoise failed')
         return out if r == 1 else None
+
+    def set_scenecut(self, params):
+        """the key-frame policy of every encode*() from its next call on (h264mi_enc_set_scenecut): a Scenecut, a
+        (level, share, min_gap, max_gap, compensate) tuple, or None for off (share 0 with max_gap 0 is off too). On, the
+        encoder owns a thumbnail and sixteen words per stream, runs the detector and a one-thread-per-stream decision
+        behind the denoiser and in front of the overlay list and the frame step, and codes an IDR at a cut, at the
+        period and whenever it would anyway; encode() then codes a copy of the caller's frames. Off drops the state.
+        ValueError, with the setting in force unchanged, on parameters scenecut_ok refuses."""
+        d = _scenecut_params(params)
+        if self._L.h264mi_enc_set_scenecut(self._e, ctypes.byref(d) if d is not None else None) != 0:
+            raise ValueError(f'h264mi_enc_set_scenecut refused {d!r}')
+
+    def scenecut(self):
+        """the key-frame policy in force: a Scenecut (a copy), or None when it is off (h264mi_enc_scenecut)"""
+        out = Scenecut()
+        r = self._L.h264mi_enc_scenecut(self._e, ctypes.byref(out))
+        if r < 0:
+            raise RuntimeError('h264mi_enc_scenecut failed')
+        return out if r == 1 else None
+
+    def scenecut_state(self, stream):
+        """stream's state after the last submitted frame (h264mi_enc_scenecut_state; waits for the encoder's stream): a
+        dict of 'stats' (the frame's eight statistics words) and cut, key, reason, dist, keys_by_cut, keys_by_period,
+        keys_other, frames"""
+        out = (ctypes.c_uint32 * 16)()
+        if self._L.h264mi_enc_scenecut_state(self._e, int(stream), out) != 0:
+            raise RuntimeError('h264mi_enc_scenecut_state failed')
+        v = list(out)
+        return dict(zip(SCENECUT_STATE, v[8:]), stats=v[:8])
 
     def set_overlays(self, sprites, ow, oh, nsprites, overlays):
         """sprites: uint8 CUDA tensor holding nsprites I420A sprites of ow x oh back to back (i420a_bytes each), any
@@ -1139,6 +1175,75 @@ def i420_denoise(dst, cur, prev, w, h, n, params, dst2=None, stats=None, stream=
                                      ctypes.c_void_p(cur.data_ptr()), ctypes.c_void_p(prev.data_ptr()), w, h, n,
                                      ctypes.byref(d) if d is not None else None,
                                      ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
+
+
+class Scenecut(ctypes.Structure):
+    """h264mi_scenecut (include/h264mi.h): level 0..1020 (the mean absolute thumbnail difference of a 32x32 block, in
+    quarter levels, above which the block is changed), share 0..256 (the share of 256 of the blocks that must be
+    changed; 0: detection off), min_gap, max_gap 0..65535 (frames between key frames; max_gap 0: no period),
+    compensate 0/1 (a uniform brightness step changes no block). 20 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('level', 'share', 'min_gap', 'max_gap', 'compensate')]
+
+    def __repr__(self):
+        return 'Scenecut(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
+
+
+SCENECUT_DEFAULT = (64, 128, 4, 0, 1)  # the header's documented default
+SCENECUT_STATE = ('cut', 'key', 'reason', 'dist', 'keys_by_cut', 'keys_by_period', 'keys_other', 'frames')
+
+
+def _scenecut_params(params):
+    """None, a Scenecut, or a Scenecut from five integers"""
+    if params is None or isinstance(params, Scenecut):
+        return params
+    return Scenecut(*(int(v) for v in params))
+
+
+def scenecut_ok(params):
+    """0 when every field of params (a Scenecut or five integers) is in its range, else -1 (None included);
+    h264mi_scenecut_ok, host only"""
+    d = _scenecut_params(params)
+    return lib().h264mi_scenecut_ok(ctypes.byref(d) if d is not None else None)
+
+
+def scenecut_is_cut(params, stats):
+    """1 when a frame's eight statistics words are a cut under params, 0 when not, -1 on bad parameters;
+    h264mi_scenecut_is_cut, host only"""
+    d = _scenecut_params(params)
+    words = (ctypes.c_uint32 * 8)(*(int(v) for v in stats))
+    return lib().h264mi_scenecut_is_cut(ctypes.byref(d) if d is not None else None, words)
+
+
+def thumb_size(w, h):
+    """(tw, th) = (ceil(w / 4), ceil(h / 4)) of a w x h frame (h264mi_thumb_size); ValueError on a bad side"""
+    tw, th = ctypes.c_int(0), ctypes.c_int(0)
+    if lib().h264mi_thumb_size(w, h, ctypes.byref(tw), ctypes.byref(th)) != 0:
+        raise ValueError(f'bad size {w}x{h}')
+    return tw.value, th.value
+
+
+def i420_scenecut(cur, w, h, n, params, thumb_out=None, thumb_prev=None, stats=None, stream=None):
+    """the thumbnails of n tight w x h I420 frames (uint8 CUDA tensor cur, any alignment) into thumb_out (n * tw * th
+    bytes, may be thumb_prev itself or None) and, against the n thumbnails thumb_prev, their statistics into stats (a
+    CUDA tensor of 8 n 32-bit words: {changed blocks, blocks, sum sad, sum Tc, sum Tp, 0, 0, 0}, zeroed and then
+    accumulated on the stream); one launch, async on stream (default: the current one); h264mi_i420_scenecut_dev.
+    params: a Scenecut or (level, share, min_gap, max_gap, compensate). The words and bytes equal tests/scenecutref.py's.
+    ValueError on a bad argument."""
+    _assert_dev_u8(cur)
+    ok = n > 0 and min(w, h) > 0
+    assert cur.numel() >= (n * _i420_bytes(w, h) if ok else 0)
+    tb = n * ((w + 3) // 4) * ((h + 3) // 4) if ok else 0
+    for t in (thumb_out, thumb_prev):
+        if t is not None:
+            _assert_dev_u8(t)
+            assert t.numel() >= tb
+    if stats is not None:
+        assert stats.is_cuda and stats.is_contiguous() and stats.numel() * stats.element_size() >= 32 * max(n, 0)
+    d = _scenecut_params(params)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    if lib().h264mi_i420_scenecut_dev(ptr(stats), ptr(thumb_out), ptr(cur), ptr(thumb_prev), w, h, n,
+                                      ctypes.byref(d) if d is not None else None, _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
 
 

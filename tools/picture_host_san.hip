@@ -1,11 +1,12 @@
 // picture_host_san.hip -- the host rules of the picture calls (csrc/picture_host.h and the host halves of scale.hip,
-// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
+// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip, scenecut.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
 // is loaded into Python, no kernel is launched, no device is needed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=all tools/picture_host_san.hip openh264-wasm_amd/csrc/scale.hip \
 //         openh264-wasm_amd/csrc/compose.hip openh264-wasm_amd/csrc/overlay.hip openh264-wasm_amd/csrc/upscale.hip \
-//         openh264-wasm_amd/csrc/orient.hip openh264-wasm_amd/csrc/denoise.hip -o picture_host_san && ./picture_host_san
+//         openh264-wasm_amd/csrc/orient.hip openh264-wasm_amd/csrc/denoise.hip openh264-wasm_amd/csrc/scenecut.hip \
+//         -o picture_host_san && ./picture_host_san
 //
 // It runs, with every table in a heap block of exactly the size the call may touch:
 //   * cells_ok (both values of may_enlarge) on valid lists and on every field of a cell made odd, negative, one past the
@@ -26,6 +27,10 @@
 //   * denoise.hip's host restatement denoise_frame_host on heap blocks of exactly the frame's bytes at seven sizes (2x2
 //     and partial blocks among them), out of place and in place, against a per-sample restatement; the k tables at the
 //     limits of the parameters; denoise_ok and denoise_args_ok at their limits and one past each.
+//   * scenecut.hip's host restatement scenecut_frame_host on heap blocks of exactly the frame's and the thumbnail's bytes
+//     at seven sizes (cells 2 wide and high, partial blocks, more than one strip and block row), with and without each
+//     output and in place, against a per-cell restatement; the cut test at its boundary; scenecut_ok and
+//     scenecut_args_ok at their limits and one past each.
 // Prints one line per group and "ok"; exits 1 at the first difference.
 #include <cstdio>
 #include <cstdlib>
@@ -511,7 +516,90 @@ static void check_denoise() {
     printf("denoise: %d frames at 7 sizes x 6 parameter sets out of place and in place, tables, scalar and range checks\n", frames);
 }
 
+// the thumbnail and the block rule restated cell by cell: every cell looks its own block up
+static void ref_scenecut(std::vector<uint8_t> &thumb, const uint8_t *cur, const uint8_t *tprev, int w, int h, const h264mi_scenecut &p, uint32_t *st) {
+    const int tw = (w + 3) / 4, th = (h + 3) / 4, nbx = (tw + 7) / 8, nby = (th + 7) / 8;
+    std::vector<long long> sad((size_t)nbx * nby, 0), sc(sad), sp(sad), nc(sad);
+    for (int cy = 0; cy < th; cy++)
+        for (int cx = 0; cx < tw; cx++) {
+            long long sum = 0, n = 0;
+            for (int y = 4 * cy; y < std::min(4 * cy + 4, h); y++)
+                for (int x = 4 * cx; x < std::min(4 * cx + 4, w); x++) { sum += cur[(size_t)y * w + x]; n++; }
+            const long long T = (sum + n / 2) / n, P = tprev[(size_t)cy * tw + cx];
+            const size_t b = (size_t)(cy / 8) * nbx + cx / 8;
+            thumb[(size_t)cy * tw + cx] = (uint8_t)T;
+            sad[b] += llabs(T - P); sc[b] += T; sp[b] += P; nc[b]++;
+        }
+    for (int k = 0; k < 8; k++) st[k] = 0;
+    for (size_t b = 0; b < sad.size(); b++) {
+        const long long m = p.compensate ? sad[b] - llabs(sc[b] - sp[b]) : sad[b];
+        st[0] += 4 * m > (long long)p.level * nc[b];
+        st[1]++;
+        st[2] += (uint32_t)sad[b]; st[3] += (uint32_t)sc[b]; st[4] += (uint32_t)sp[b];
+    }
+}
+
+static void check_scenecut() {
+    const int sizes[][2] = {{2, 2}, {6, 2}, {34, 18}, {66, 34}, {130, 70}, {514, 34}, {48, 66}};
+    const h264mi_scenecut sets[] = {{64, 128, 4, 0, 1}, {64, 128, 4, 0, 0}, {0, 1, 0, 0, 1}, {1020, 256, 0, 9, 0}, {24, 64, 0, 0, 1}};
+    int frames = 0;
+    for (const auto &s : sizes)
+        for (const h264mi_scenecut &p : sets) {
+            const int w = s[0], h = s[1];
+            const size_t fb = i420_bytes(w, h), tb = thumb_bytes(w, h);
+            CHECK(tb == (size_t)((w + 3) / 4) * ((h + 3) / 4));
+            std::unique_ptr<uint8_t[]> cur(new uint8_t[fb]), tp(new uint8_t[tb]), out(new uint8_t[tb]);  // exactly the bytes
+            for (size_t i = 0; i < fb; i++) cur[i] = (uint8_t)pix_rng();
+            for (size_t i = 0; i < tb; i++) tp[i] = (i / 3) % 2 ? (uint8_t)pix_rng() : (uint8_t)(120 + pix_rng() % 16);
+            std::vector<uint8_t> want(tb);
+            uint32_t st_want[8], st[8] = {9, 9, 9, 9, 9, 9, 9, 9};
+            ref_scenecut(want, cur.get(), tp.get(), w, h, p, st_want);
+            scenecut_frame_host(st, out.get(), cur.get(), tp.get(), w, h, p);
+            CHECK(memcmp(out.get(), want.data(), tb) == 0 && memcmp(st, st_want, sizeof st) == 0);
+            CHECK(st[0] <= st[1] && st[5] == 0 && st[6] == 0 && st[7] == 0);
+            uint32_t st2[8] = {9, 9, 9, 9, 9, 9, 9, 9};
+            scenecut_frame_host(st2, nullptr, cur.get(), tp.get(), w, h, p);  // statistics only
+            CHECK(memcmp(st2, st_want, sizeof st2) == 0);
+            memset(out.get(), 0, tb);
+            scenecut_frame_host(nullptr, out.get(), cur.get(), nullptr, w, h, p);  // thumbnails only
+            CHECK(memcmp(out.get(), want.data(), tb) == 0);
+            scenecut_frame_host(st2, tp.get(), cur.get(), tp.get(), w, h, p);  // in place over the previous thumbnail
+            CHECK(memcmp(tp.get(), want.data(), tb) == 0 && memcmp(st2, st_want, sizeof st2) == 0);
+            frames++;
+        }
+    // the cut test at its boundary and at the largest counts; the scalar checks at their limits and one past each
+    CHECK(!scenecut_is_cut(128, 4, 8) && scenecut_is_cut(128, 5, 8) && !scenecut_is_cut(0, 8, 8) && !scenecut_is_cut(256, 65536, 65536));
+    CHECK(scenecut_is_cut(255, 65536, 65536) && scenecut_is_cut(1, 1, 255) && !scenecut_is_cut(1, 1, 256));
+    const h264mi_scenecut lo{0, 0, 0, 0, 0}, hi{1020, 256, 65535, 65535, 1};
+    CHECK(scenecut_ok(&lo) && scenecut_ok(&hi) && !scenecut_ok(nullptr));
+    for (int f = 0; f < 5; f++) {
+        h264mi_scenecut a = lo, b = hi;
+        ((int32_t *)&a)[f]--; ((int32_t *)&b)[f]++;
+        CHECK(!scenecut_ok(&a) && !scenecut_ok(&b));
+        a = lo; ((int32_t *)&a)[f] = INT32_MIN; b = hi; ((int32_t *)&b)[f] = INT32_MAX;
+        CHECK(!scenecut_ok(&a) && !scenecut_ok(&b));
+    }
+    const uintptr_t S = 0x10000000u, O = 0x20000000u, C = 0x30000000u, P = 0x40000000u;
+    auto ok = [&](uintptr_t s, uintptr_t o, uintptr_t c, uintptr_t q, int w, int h, int n, const h264mi_scenecut *par) {
+        return scenecut_args_ok((const void *)s, (const void *)o, (const void *)c, (const void *)q, w, h, n, par);
+    };
+    const size_t fb = 3 * i420_bytes(32, 16), tb = 3 * thumb_bytes(32, 16), sb = 96;
+    CHECK(ok(S, O, C, P, 32, 16, 3, &hi) && ok(S, P, C, P, 32, 16, 3, &hi) && ok(S, 0, C, P, 32, 16, 3, &hi) && ok(0, O, C, 0, 32, 16, 3, &hi));
+    CHECK(ok(0, O, C, P, 32, 16, 3, &hi) && ok(S, O, C, P, 8192, 8192, 1, &lo) && ok(0, O, C, 0, 2, 2, 1, &lo));
+    CHECK(!ok(S, O, 0, P, 32, 16, 3, &hi) && !ok(0, 0, C, P, 32, 16, 3, &hi) && !ok(S, O, C, 0, 32, 16, 3, &hi) && !ok(S, O, C, P, 32, 16, 3, nullptr));
+    CHECK(!ok(S, O, C, P, 32, 16, 0, &hi) && !ok(S, O, C, P, 31, 16, 3, &hi) && !ok(S, O, C, P, 32, 8194, 3, &hi) && !ok(S, O, C, P, 0, 16, 3, &hi));
+    for (uintptr_t off : {(uintptr_t)1, (uintptr_t)(tb - 1), (uintptr_t)-1, (uintptr_t)-(intptr_t)(tb - 1)}) CHECK(!ok(S, P + off, C, P, 32, 16, 3, &hi));
+    for (uintptr_t off : {(uintptr_t)0, (uintptr_t)(fb - 1), (uintptr_t)-(intptr_t)(tb - 1)})
+        CHECK(!ok(S, C + off, C, P, 32, 16, 3, &hi) && !ok(S, O, C, C + off, 32, 16, 3, &hi));
+    CHECK(ok(S, C + fb, C, P, 32, 16, 3, &hi) && ok(S, C - tb, C, P, 32, 16, 3, &hi) && ok(C + fb, O, C, P, 32, 16, 3, &hi) && ok(C - sb, O, C, P, 32, 16, 3, &hi));  // touching
+    CHECK(!ok(C, O, C, P, 32, 16, 3, &hi) && !ok(C + fb - 4, O, C, P, 32, 16, 3, &hi) && !ok(C - sb + 4, O, C, P, 32, 16, 3, &hi));
+    for (uintptr_t b : {O, P}) CHECK(!ok(b, O, C, P, 32, 16, 3, &hi) && !ok(b + tb - 4, O, C, P, 32, 16, 3, &hi) && !ok(b - sb + 4, O, C, P, 32, 16, 3, &hi));
+    for (uintptr_t off : {1, 2, 3}) CHECK(!ok(S + off, O, C, P, 32, 16, 3, &hi));
+    printf("scenecut: %d frames at 7 sizes x 5 parameter sets (with and without outputs, in place), the cut test, scalar and range checks\n", frames);
+}
+
 int main() {
+    check_scenecut();
     check_denoise();
     check_pix();
     check_orient();
