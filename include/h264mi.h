@@ -834,6 +834,77 @@ int h264mi_enc_set_scenecut(h264mi_encoder *e, const h264mi_scenecut *p);
 int h264mi_enc_scenecut(h264mi_encoder *e, h264mi_scenecut *out);
 int h264mi_enc_scenecut_state(h264mi_encoder *e, int stream, uint32_t *out16);
 
+/* Deinterlacing a picture on the device: an interlaced frame (1080i, 576i, 480i) holds two fields from
+   two instants, woven line by line; coded as it stands every moving edge is a comb. Interlaced *coding* stays out of
+   scope: this keeps one field and rebuilds the lines of the other. The library's own rule, exact
+   integers, the same bytes on any host (tests/deintref.py restates it in numpy). A frame is tight I420, w x h, both
+   sides even, 2..8192.
+     parity      0, 1     0 keeps the even lines (the top field), 1 keeps the odd lines
+     spatial     0, 1     0 linear, 1 edge-directed
+     temporal    0, 1     1 weaves where the previous frame shows no motion
+     comb_level  0..255   used by the statistics only
+   The rule applies to each of the three planes on its own, with the plane's own pw x ph (luma w x h, chroma
+   w/2 x h/2) and the same parity. C is the current frame, P the previous *unfiltered* frame (optional), O the output.
+     Kept lines (y % 2 == parity): O = C.
+     A plane with no kept line (ph == 1, parity == 1): O = C.
+     Missing line y: up = C[y-1] and dn = C[y+1], both kept lines; v = C[y][x].
+       Only one neighbour inside the plane: s is that neighbour's sample at x.
+       Linear: s = (up[x] + dn[x] + 1) >> 1.
+       Edge-directed: for d in the order 0, -1, +1: score_d = sum over j = -1..1 of |up[cx(x+j+d)] - dn[cx(x+j-d)]|,
+         cx clamping to 0..pw-1. The smallest score wins, a tie goes to the earlier d in that order.
+         s = (up[cx(x+d)] + dn[cx(x-d)] + 1) >> 1.
+       temporal == 0 or no P: O = s.
+       temporal == 1 with P: k = y ^ 1, the kept line of the same line pair (k = y if that lies outside the plane).
+         m = max(|C[y][x] - P[y][x]|, |C[k][x] - P[k][x]|), O = min(max(s, v - m), v + m).
+         Where nothing moved (m == 0) the two fields are woven, where much moved the result is spatial, in between
+         it is continuous. O lies between s and v, so nothing is clipped to 0..255. m reads P only at the sample's
+         own line pair and column.
+   Statistics, optional: four uint32_t per frame, {missing luma samples, combed luma samples, sum of |O - v| over the
+   missing luma samples, the same sum over both chroma planes}. A missing sample is one on a missing line of a plane
+   that has a kept line. A luma sample on a missing line with both neighbours inside the plane is combed iff v - up[x]
+   and v - dn[x] are both positive or both negative and min(|v - up[x]|, |v - dn[x]|) > comb_level: a property of the
+   source, whatever the other parameters, that tells interlaced material from progressive material flagged as
+   interlaced. Sums of integers modulo 2^32, whatever the order; no frame of up to 8192 x 4096 samples can wrap.
+   Not provided: double-rate output in one call (call twice with the two parities), motion-compensated or wider
+   temporal tests, field-order detection beyond the combed count, inverse telecine, per-stream parameters,
+   decoder-side use. */
+typedef struct { int32_t parity, spatial, temporal, comb_level; } h264mi_deinterlace;
+/* host only: 0 when every field of *p is in its range, -1 otherwise (a null pointer included) */
+int h264mi_deinterlace_ok(const h264mi_deinterlace *p);
+/* async on hip_stream: n >= 1 frames at d_cur deinterlaced into the n frames at d_dst, one launch (and one memset when
+   d_stats is given); no scratch memory. d_prev, when not null, is the n previous unfiltered frames (without it the
+   result is spatial only, whatever p->temporal); d_prev_out, when not null, receives the unfiltered d_cur -- the next
+   call's d_prev; d_stats, when not null, is 4 n uint32_t on the device at a multiple of 4, zeroed by the call on the
+   stream and then accumulated. Any alignment of the frames. d_dst may be exactly d_cur (kept lines are then not
+   written), d_prev_out may be exactly d_prev; d_prev may overlap d_cur in any way when neither is written (the frames
+   of a clip in one buffer, d_prev = d_cur - one frame). Every other overlap of a written range with another range
+   is refused. Returns 0, or -1 before anything is enqueued on: a null d_dst, d_cur or p, an odd side or one outside
+   2..8192, n < 1, a parameter out of range, d_stats at no multiple of 4, an overlap as above. */
+int h264mi_i420_deinterlace_dev(void *d_dst, void *d_prev_out, const void *d_cur, const void *d_prev, int w, int h, int n,
+                                const h264mi_deinterlace *p, void *d_stats, void *hip_stream);
+/* host only: the same rule for one frame in host memory as plain loops, sample by sample (the restatement the device
+   is tested against). dst may be cur; prev and stats (four words) may be null. Returns 0, or -1 on a null dst, cur or
+   p, a bad side or parameter. */
+int h264mi_i420_deinterlace_host(void *dst, const void *cur, const void *prev, int w, int h, const h264mi_deinterlace *p,
+                                 uint32_t *stats);
+/* the encoder's first pre-filter. With parameters set (NULL: off) the encoder owns a state of nstreams frames -- the
+   previous unfiltered input, device memory allocated when the filter is turned on, freed when it is turned off and at
+   destroy -- and h264mi_enc_encode (which then copies the caller's frames into the input area as with an overlay
+   list), _encode_rgba and _encode_pix run, on the encoder's stream and in this order: the deinterlacer, the denoiser,
+   the key-frame policy, the overlay list, the frame step. The deinterlacer is one launch in place over the input area
+   with d_prev = d_prev_out = the state; the first frame after the filter was turned on has no d_prev: it is spatial
+   only and stores the state.
+     * The filter is only meaningful before any vertical resampling: while it is on, h264mi_enc_encode_scaled,
+       _composed, _composed_any and _oriented return -1 and submit nothing; their callers use the standalone call.
+     * The state advances on every submitted frame; h264mi_enc_force_idr does not reset it. Turning the filter off
+       drops the state; setting other parameters while it is on keeps it.
+     * Off (the default) nothing changes: no launch, no allocation. The drop-in functions never filter.
+   h264mi_enc_set_deinterlace returns 0, or -1 with the setting in force unchanged on a null encoder, parameters
+   h264mi_deinterlace_ok refuses, or a failed allocation. h264mi_enc_deinterlace returns 1 (on, *out filled when out is
+   not null), 0 (off, *out untouched) or -1 (a null encoder). */
+int h264mi_enc_set_deinterlace(h264mi_encoder *e, const h264mi_deinterlace *p);
+int h264mi_enc_deinterlace(h264mi_encoder *e, h264mi_deinterlace *out);
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -190,12 +190,19 @@ int h264mi_enc_frames_skipped(h264mi_encoder *e, int stream) {
     if (hipMemcpy(&st, e->c->d_st + stream, sizeof(EncState), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return st.skipped;
 }
-// the tail of every entry point that codes the input area: the pre-filter in force (DESIGN.md §5.13; denoise.hip;
+// the tail of every entry point that codes the input area: the deinterlacer in force (DESIGN.md §5.15;
+// deinterlace.hip; nothing when off) -- in place against the previous unfiltered frames, which the same launch
+// replaces; the first frame spatial only --, the pre-filter in force (DESIGN.md §5.13; denoise.hip;
 // nothing when off) -- the first frame only copied to the state, every later one filtered in place against the state,
 // which receives the same bytes --, the key-frame policy in force (below), the overlay list in force blended into it
 // (DESIGN.md §5.6; overlay.hip; nothing without a list), then the frame step. A launch that fails ends the call with
 // -1 where it stands: no frame is submitted, and the states of the steps in front of it have advanced
 static int enc_code_input(EncCtx *c) {
+    if (c->di_on) {
+        if (launch_deinterlace_i420(c->d_src, c->d_di, c->d_src, c->di_has ? c->d_di : nullptr, c->w, c->h, c->S, c->di, nullptr, c->stream) != 0)
+            return -1;
+        c->di_has = true;
+    }
     if (c->dn_on) {
         if (!c->dn_has) {
             if (hipMemcpyAsync(c->d_dn, c->d_src, (size_t)c->S * c->fbytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
@@ -223,12 +230,12 @@ static int enc_code_input(EncCtx *c) {
         return -1;
     return enc_frame(c, c->d_src);
 }
-// with the pre-filter or the key-frame policy on or an overlay list in force the caller's frames are copied into the
-// input area, filtered, looked at and blended there and coded from there
+// with the deinterlacer, the pre-filter or the key-frame policy on or an overlay list in force the caller's frames are
+// copied into the input area, filtered, looked at and blended there and coded from there
 int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
     if (!e || !d_frames) return -1;
     EncCtx *c = e->c;
-    if (c->ov.empty() && !c->dn_on && !c->sc_on) return enc_frame(c, (const uint8_t *)d_frames);
+    if (c->ov.empty() && !c->di_on && !c->dn_on && !c->sc_on) return enc_frame(c, (const uint8_t *)d_frames);
     if (d_frames != (const void *)c->d_src) {
         const size_t nb = (size_t)c->S * c->fbytes;
         if (byte_ranges_overlap(d_frames, nb, c->d_src, nb)) return -1;  // partly inside the input area
@@ -283,6 +290,47 @@ int h264mi_enc_denoise(h264mi_encoder *e, h264mi_denoise *out) {
     if (!e) return -1;
     if (e->c->dn_on && out) *out = e->c->dn;
     return e->c->dn_on ? 1 : 0;
+}
+// The deinterlacer (DESIGN.md §5.15; deinterlace.hip; the checks: picture_host.h): n frames, one launch
+int h264mi_deinterlace_ok(const h264mi_deinterlace *p) { return deinterlace_ok(p) ? 0 : -1; }
+int h264mi_i420_deinterlace_dev(void *d_dst, void *d_prev_out, const void *d_cur, const void *d_prev, int w, int h, int n,
+                                const h264mi_deinterlace *p, void *d_stats, void *hip_stream) {
+    if (!deinterlace_args_ok(d_dst, d_prev_out, d_cur, d_prev, w, h, n, p, d_stats)) return -1;
+    return launch_deinterlace_i420((uint8_t *)d_dst, (uint8_t *)d_prev_out, (const uint8_t *)d_cur, (const uint8_t *)d_prev, w, h, n, *p,
+                                   (uint32_t *)d_stats, (hipStream_t)hip_stream);
+}
+int h264mi_i420_deinterlace_host(void *dst, const void *cur, const void *prev, int w, int h, const h264mi_deinterlace *p, uint32_t *stats) {
+    if (!dst || !cur || !canvas_ok(w, h) || !deinterlace_ok(p)) return -1;
+    deinterlace_frame_host((uint8_t *)dst, (const uint8_t *)cur, (const uint8_t *)prev, w, h, *p, stats);
+    return 0;
+}
+// the encoder's deinterlacer: NULL turns it off and frees the state (after the stream has finished with it); a refused
+// call leaves the setting in force
+int h264mi_enc_set_deinterlace(h264mi_encoder *e, const h264mi_deinterlace *p) {
+    if (!e || (p && !deinterlace_ok(p))) return -1;
+    EncCtx *c = e->c;
+    if (!p) {
+        if (c->d_di) {
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipFree(c->d_di);
+            c->d_di = nullptr;
+        }
+        c->di_on = c->di_has = false;
+        return 0;
+    }
+    if (!canvas_ok(c->w, c->h)) return -1;
+    if (!c->d_di) {
+        if (hipMalloc(&c->d_di, (size_t)c->S * c->fbytes) != hipSuccess) { c->d_di = nullptr; return -1; }
+        c->di_has = false;
+    }
+    c->di = *p;
+    c->di_on = true;
+    return 0;
+}
+int h264mi_enc_deinterlace(h264mi_encoder *e, h264mi_deinterlace *out) {
+    if (!e) return -1;
+    if (e->c->di_on && out) *out = e->c->di;
+    return e->c->di_on ? 1 : 0;
 }
 // The scene-cut detector (DESIGN.md §5.14; scenecut.hip; the checks: picture_host.h): n frames, one launch
 int h264mi_scenecut_ok(const h264mi_scenecut *p) { return scenecut_ok(p) ? 0 : -1; }
@@ -410,7 +458,7 @@ int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw
 // its stream, then the frame step as h264mi_enc_encode runs it (the quality records then see the scaled source).
 // Every refusal comes before the first launch
 int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w, int src_h) {
-    if (!e || !d_frames) return -1;
+    if (!e || !d_frames || e->c->di_on) return -1;  // the deinterlacer belongs in front of a vertical resampling
     EncCtx *c = e->c;
     if (!scale_args_ok(c->w, c->h, src_w, src_h, c->S) || i420_ranges_overlap(c->d_src, c->w, c->h, c->S, d_frames, src_w, src_h, c->S))
         return -1;
@@ -432,7 +480,7 @@ int h264mi_i420_orient_dev(void *d_dst, const void *d_src, int sw, int sh, int n
 // orientation): one batched launch into the encoder's own input area on its stream, then the frame step as
 // h264mi_enc_encode runs it. Every refusal comes before the first launch
 int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orient) {
-    if (!e || !d_frames) return -1;
+    if (!e || !d_frames || e->c->di_on) return -1;  // as h264mi_enc_encode_scaled
     EncCtx *c = e->c;
     int sw, sh;  // the inverse turns a w x h picture back into the source's size
     if (orient_size(orient_inverse(orient), c->w, c->h, &sw, &sh) != 0 || !orient_args_ok(orient, sw, sh, c->S) ||
@@ -483,7 +531,7 @@ int h264mi_mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, 
 // Every refusal comes before the first launch
 static int enc_encode_cells(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
                             bool may_enlarge, int filter, int bg_y, int bg_cb, int bg_cr) {
-    if (!e || !d_src) return -1;
+    if (!e || !d_src || e->c->di_on) return -1;  // as h264mi_enc_encode_scaled
     EncCtx *c = e->c;
     if ((may_enlarge && !filter_ok(filter)) || !cells_ok(c->w, c->h, c->S, src_w, src_h, nsrc, cells, ncells, may_enlarge) ||
         i420_ranges_overlap(c->d_src, c->w, c->h, c->S, d_src, src_w, src_h, nsrc))

@@ -1,5 +1,5 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip, colorspace.hip, denoise.hip, scenecut.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip) and the runtime (runtime_enc.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
@@ -230,6 +230,31 @@ static inline bool scenecut_args_ok(const void *stats, const void *thumb_out, co
     return true;
 }
 
+// ---- the deinterlacer (include/h264mi.h)
+constexpr int DEINTERLACE_MAX_COMB = 255;
+static inline bool deinterlace_ok(const h264mi_deinterlace *p) {
+    return p && (uint32_t)p->parity <= 1 && (uint32_t)p->spatial <= 1 && (uint32_t)p->temporal <= 1 && p->comb_level >= 0 &&
+           p->comb_level <= DEINTERLACE_MAX_COMB;
+}
+// arguments of a deinterlace call, the pointers' values included: good parameters, the geometry limits of the denoiser,
+// n >= 1, statistics at a multiple of 4. Of the written ranges (dst, prev_out, the statistics) each is disjoint from
+// every other range, but that dst may be exactly cur and prev_out exactly prev; the two read ranges may overlap in
+// any way
+static inline bool deinterlace_args_ok(const void *dst, const void *prev_out, const void *cur, const void *prev, int w, int h, int n,
+                                       const h264mi_deinterlace *p, const void *stats) {
+    if (!dst || !cur || n < 1 || !canvas_ok(w, h) || !deinterlace_ok(p) || ((uintptr_t)stats & 3)) return false;
+    const size_t nb = (size_t)n * i420_bytes(w, h), sb = 16 * (size_t)n;
+    const void *r[5] = {dst, prev_out, stats, cur, prev};  // the first three are written
+    const size_t rb[5] = {nb, nb, sb, nb, nb};
+    for (int a = 0; a < 3; a++)
+        for (int b = a + 1; b < 5; b++) {
+            if (!r[a] || !r[b]) continue;
+            if (((a == 0 && b == 3) || (a == 1 && b == 4)) && r[a] == r[b]) continue;
+            if (byte_ranges_overlap(r[a], rb[a], r[b], rb[b])) return false;
+        }
+    return true;
+}
+
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
 static inline int cell_kind(const h264mi_cell &c) {
@@ -344,6 +369,11 @@ void scenecut_frame_host(uint32_t *stats, uint8_t *thumb_out, const uint8_t *cur
 // the decision of S streams, one thread each: st and words (16 a stream) on the device; stats eight words a stream
 // on the device, or null (no detector ran: no thumbnail yet, or share == 0)
 int launch_scenecut_decide(EncState *st, uint32_t *words, const uint32_t *stats, int S, const h264mi_scenecut &p, hipStream_t s);
+// deinterlace.hip: arguments as deinterlace_args_ok accepts them; prev_out, prev and stats (four words a frame) may be
+// null. deinterlace_frame_host: one frame sample by sample, out may be cur
+int launch_deinterlace_i420(uint8_t *dst, uint8_t *prev_out, const uint8_t *cur, const uint8_t *prev, int w, int h, int n,
+                            const h264mi_deinterlace &p, uint32_t *stats, hipStream_t s);
+void deinterlace_frame_host(uint8_t *out, const uint8_t *cur, const uint8_t *prev, int w, int h, const h264mi_deinterlace &p, uint32_t *stats);
 // pixfmt.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);

@@ -205,6 +205,12 @@ struct EncCtx {
     bool dn_on = false, dn_has = false;
     h264mi_denoise dn = {};
     uint8_t *d_dn = nullptr;
+    // the deinterlacer in force (h264mi_enc_set_deinterlace; deinterlace.hip): its parameters, the S previous unfiltered
+    // frames (allocated when it is turned on, freed when it is turned off) and whether they hold a frame yet. Off: every
+    // frame step enqueues what it did before the filter existed
+    bool di_on = false, di_has = false;
+    h264mi_deinterlace di = {};
+    uint8_t *d_di = nullptr;
     // the key-frame policy in force (h264mi_enc_set_scenecut; scenecut.hip): its parameters, per stream sixteen words
     // and eight statistics words (d_sc, 24 S words, allocated when it is turned on, freed when it is turned off), the S
     // thumbnails (d_sc_thumb, only with share > 0) and whether they hold a frame yet. Off: every frame step enqueues
@@ -227,6 +233,7 @@ static void enc_free(EncCtx *c) {
     (void)hipFree(c->d_pool);
     (void)hipFree(c->d_qual);
     (void)hipFree(c->d_dn);
+    (void)hipFree(c->d_di);
     (void)hipFree(c->d_sc);
     (void)hipFree(c->d_sc_thumb);
     (void)hipFree(c->d_prof);

@@ -171,6 +171,11 @@ def lib():
             'h264mi_i420_denoise_dev': (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp]),
             'h264mi_enc_set_denoise': (i, [vp, vp]),
             'h264mi_enc_denoise': (i, [vp, vp]),
+            'h264mi_deinterlace_ok': (i, [vp]),
+            'h264mi_i420_deinterlace_dev': (i, [vp, vp, vp, vp, i, i, i, vp, vp, vp]),
+            'h264mi_i420_deinterlace_host': (i, [vp, vp, vp, i, i, vp, vp]),
+            'h264mi_enc_set_deinterlace': (i, [vp, vp]),
+            'h264mi_enc_deinterlace': (i, [vp, vp]),
             'h264mi_scenecut_ok': (i, [vp]),
             'h264mi_thumb_size': (i, [i, i, vp, vp]),
             'h264mi_scenecut_is_cut': (i, [vp, vp]),
@@ -451,6 +456,26 @@ class BatchEncoder:
         if self._L.h264mi_enc_encode_composed_any(self._e, ctypes.c_void_p(src.data_ptr()), int(src_w), int(src_h), int(nsrc), arr, len(arr),
                                                   int(filter), y, cb, cr) != 0:
             raise ValueError(f'h264mi_enc_encode_composed_any refused {len(arr)} cells of {nsrc} sources {src_w}x{src_h} -> {self.w}x{self.h}')
+
+    def set_deinterlace(self, params):
+        """the deinterlacer of encode(), encode_rgba() and encode_pix() from the next call on
+        (h264mi_enc_set_deinterlace): a Deinterlace, a (parity, spatial, temporal, comb_level) tuple, or None for off. On,
+        the encoder owns S frames of state -- the previous unfiltered input --, filters the input area in place in front
+        of the denoiser, the key-frame policy and the overlay list, and rebuilds the first frame after it was turned on
+        spatially only; encode() then codes a copy of the caller's frames, which stay as they are. While it is on
+        encode_scaled, encode_composed, encode_composed_any and encode_oriented are refused. Off drops the state.
+        ValueError, with the setting in force unchanged, on parameters deinterlace_ok refuses."""
+        d = _deinterlace_params(params)
+        if self._L.h264mi_enc_set_deinterlace(self._e, ctypes.byref(d) if d is not None else None) != 0:
+            raise ValueError(f'h264mi_enc_set_deinterlace refused {d!r}')
+
+    def deinterlace(self):
+        """the deinterlacer in force: a Deinterlace (a copy), or None when it is off (h264mi_enc_deinterlace)"""
+        out = Deinterlace()
+        r = self._L.h264mi_enc_deinterlace(self._e, ctypes.byref(out))
+        if r < 0:
+            raise RuntimeError('h264mi_enc_deinterlace failed')
+        return out if r == 1 else None
 
     def set_denoise(self, params):
         """the pre-filter of every encode*() from its next call on (h264mi_enc_set_denoise): a Denoise, a
@@ -1244,6 +1269,52 @@ def i420_scenecut(cur, w, h, n, params, thumb_out=None, thumb_prev=None, stats=N
     ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     if lib().h264mi_i420_scenecut_dev(ptr(stats), ptr(thumb_out), ptr(cur), ptr(thumb_prev), w, h, n,
                                       ctypes.byref(d) if d is not None else None, _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
+
+
+class Deinterlace(ctypes.Structure):
+    """h264mi_deinterlace (include/h264mi.h): parity 0 (the even lines are kept) or 1, spatial 0 (linear) or 1
+    (edge-directed), temporal 0 or 1 (weave where the previous frame shows no motion), comb_level 0..255 (the
+    statistics' threshold). 16 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('parity', 'spatial', 'temporal', 'comb_level')]
+
+    def __repr__(self):
+        return 'Deinterlace(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
+
+
+def _deinterlace_params(params):
+    """None, a Deinterlace, or a Deinterlace from four integers"""
+    if params is None or isinstance(params, Deinterlace):
+        return params
+    return Deinterlace(*(int(v) for v in params))
+
+
+def deinterlace_ok(params):
+    """0 when every field of params (a Deinterlace or four integers) is in its range, else -1 (None included);
+    h264mi_deinterlace_ok, host only"""
+    d = _deinterlace_params(params)
+    return lib().h264mi_deinterlace_ok(ctypes.byref(d) if d is not None else None)
+
+
+def i420_deinterlace(dst, cur, w, h, n, params, prev=None, prev_out=None, stats=None, stream=None):
+    """n tight w x h I420 frames (uint8 CUDA tensor cur, any alignment) deinterlaced into dst; one launch, async on stream
+    (default: the current one); h264mi_i420_deinterlace_dev. params: a Deinterlace or (parity, spatial, temporal,
+    comb_level). prev, when given: the n previous unfiltered frames (without it the result is spatial only); prev_out,
+    when given, receives the unfiltered cur; stats, when given: a CUDA tensor of 4 n 32-bit words, per frame {missing
+    luma samples, combed luma samples, sum |O - v| over luma, over both chroma planes}, zeroed and then accumulated on
+    the stream. dst may be exactly cur, prev_out exactly prev. The bytes equal tests/deintref.py's. ValueError on a bad
+    argument (a parameter out of range, a side that is odd or outside 2..8192, n < 1, any other overlap of a written
+    range)."""
+    given = tuple(t for t in (dst, cur, prev, prev_out) if t is not None)
+    _assert_dev_u8(*given)
+    need = 0 if n <= 0 or min(w, h) <= 0 else n * _i420_bytes(w, h)
+    assert all(t.numel() >= need for t in given)
+    if stats is not None:
+        assert stats.is_cuda and stats.is_contiguous() and stats.numel() * stats.element_size() >= 16 * max(n, 0)
+    d = _deinterlace_params(params)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    if lib().h264mi_i420_deinterlace_dev(ptr(dst), ptr(prev_out), ptr(cur), ptr(prev), w, h, n, ctypes.byref(d) if d is not None else None,
+                                         ptr(stats), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
 
 

@@ -1,12 +1,12 @@
 // picture_host_san.hip -- the host rules of the picture calls (csrc/picture_host.h and the host halves of scale.hip,
-// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip, scenecut.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
+// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip, scenecut.hip, deinterlace.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
 // is loaded into Python, no kernel is launched, no device is needed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=all tools/picture_host_san.hip openh264-wasm_amd/csrc/scale.hip \
 //         openh264-wasm_amd/csrc/compose.hip openh264-wasm_amd/csrc/overlay.hip openh264-wasm_amd/csrc/upscale.hip \
 //         openh264-wasm_amd/csrc/orient.hip openh264-wasm_amd/csrc/denoise.hip openh264-wasm_amd/csrc/scenecut.hip \
-//         -o picture_host_san && ./picture_host_san
+//         openh264-wasm_amd/csrc/deinterlace.hip -o picture_host_san && ./picture_host_san
 //
 // It runs, with every table in a heap block of exactly the size the call may touch:
 //   * cells_ok (both values of may_enlarge) on valid lists and on every field of a cell made odd, negative, one past the
@@ -31,6 +31,10 @@
 //     at seven sizes (cells 2 wide and high, partial blocks, more than one strip and block row), with and without each
 //     output and in place, against a per-cell restatement; the cut test at its boundary; scenecut_ok and
 //     scenecut_args_ok at their limits and one past each.
+//   * deinterlace.hip's host restatement deinterlace_frame_host on heap blocks of exactly the frame's bytes at eight
+//     sizes (2x2, one-row and five-row chroma planes, more than one strip and row group), for every parity x spatial x
+//     temporal, with and without a previous frame, out of place and in place, against a second per-sample loop that
+//     walks the scores in another order; deinterlace_ok and deinterlace_args_ok at their limits and one past each.
 // Prints one line per group and "ok"; exits 1 at the first difference.
 #include <cstdio>
 #include <cstdlib>
@@ -516,6 +520,115 @@ static void check_denoise() {
     printf("denoise: %d frames at 7 sizes x 6 parameter sets out of place and in place, tables, scalar and range checks\n", frames);
 }
 
+// the rule restated sample by sample in another shape: every output sample looks its own plane, line and taps up
+static int ref_deint_sample(const uint8_t *C, const uint8_t *P, int pw, int ph, int x, int y, const h264mi_deinterlace &p) {
+    const long long v = C[(size_t)y * pw + x];
+    if (y % 2 == p.parity) return (int)v;
+    const bool hu = y - 1 >= 0, hd = y + 1 < ph;
+    if (!hu && !hd) return (int)v;
+    auto at = [&](int yy, long long xx) { return (long long)C[(size_t)yy * pw + (size_t)std::min<long long>(std::max<long long>(xx, 0), pw - 1)]; };
+    long long s;
+    if (hu != hd) {
+        s = at(hu ? y - 1 : y + 1, x);
+    } else {
+        long long score[3];  // d = -1, 0, +1
+        for (int d = -1; d <= 1; d++) score[d + 1] = llabs(at(y - 1, x - 1 + d) - at(y + 1, x - 1 - d)) + llabs(at(y - 1, x + d) - at(y + 1, x - d)) +
+                                                     llabs(at(y - 1, x + 1 + d) - at(y + 1, x + 1 - d));
+        int d = 0;
+        if (p.spatial) {
+            if (score[0] < score[1]) d = -1;
+            if (score[2] < score[1] && score[2] < score[0]) d = 1;
+        }
+        s = (at(y - 1, x + d) + at(y + 1, x - d) + 1) / 2;
+    }
+    if (p.temporal && P) {
+        const int k = (y ^ 1) < ph ? (y ^ 1) : y;
+        const long long m = std::max(llabs(v - P[(size_t)y * pw + x]), llabs((long long)C[(size_t)k * pw + x] - P[(size_t)k * pw + x]));
+        s = std::min(std::max(s, v - m), v + m);
+    }
+    return (int)s;
+}
+static void ref_deinterlace(std::vector<uint8_t> &out, const uint8_t *cur, const uint8_t *prev, int w, int h, const h264mi_deinterlace &p, uint32_t *st) {
+    const size_t ly = (size_t)w * h, lc = (size_t)(w / 2) * (h / 2);
+    st[0] = st[1] = st[2] = st[3] = 0;
+    for (size_t i = 0; i < ly + 2 * lc; i++) {
+        const int pl = i < ly ? 0 : i < ly + lc ? 1 : 2;
+        const size_t base = pl == 0 ? 0 : pl == 1 ? ly : ly + lc, j = i - base;
+        const int pw = pl ? w / 2 : w, ph = pl ? h / 2 : h, x = (int)(j % pw), y = (int)(j / pw);
+        const int o = ref_deint_sample(cur + base, prev ? prev + base : nullptr, pw, ph, x, y, p), v = cur[i];
+        CHECK(o >= 0 && o <= 255);
+        out[i] = (uint8_t)o;
+        const bool missing = y % 2 != p.parity && ph > 1;
+        if (!missing) { CHECK(o == v); continue; }
+        st[pl ? 3 : 2] += (uint32_t)abs(o - v);
+        if (pl == 0) {
+            st[0]++;
+            if (y >= 1 && y + 1 < ph) {
+                const int du = v - cur[i - pw], dd = v - cur[i + pw];
+                if ((long long)du * dd > 0 && std::min(abs(du), abs(dd)) > p.comb_level) st[1]++;
+            }
+        }
+    }
+}
+
+static void check_deinterlace() {
+    const int sizes[][2] = {{2, 2}, {4, 2}, {16, 16}, {18, 10}, {34, 6}, {258, 18}, {528, 34}, {2, 18}};
+    int frames = 0;
+    for (const auto &s : sizes)
+        for (int par = 0; par < 8; par++)
+            for (int with_prev = 0; with_prev < 2; with_prev++) {
+                const h264mi_deinterlace p{par & 1, (par >> 1) & 1, (par >> 2) & 1, 8};
+                const int w = s[0], h = s[1];
+                const size_t fb = i420_bytes(w, h);
+                std::unique_ptr<uint8_t[]> cur(new uint8_t[fb]), prev(new uint8_t[fb]), out(new uint8_t[fb]);  // exactly the frame's bytes
+                for (size_t i = 0; i < fb; i++) {
+                    prev[i] = (i / 5) % 3 ? (uint8_t)pix_rng() : (uint8_t)(i % 256);  // runs of a ramp: ties
+                    const int kind = (int)(i / 8) % 3;  // runs of 8 bytes: fresh, equal, near
+                    cur[i] = kind == 0 ? (uint8_t)pix_rng() : kind == 1 ? prev[i] : (uint8_t)std::min(255, std::max(0, (int)prev[i] + (int)(pix_rng() % 13) - 6));
+                }
+                const uint8_t *pv = with_prev ? prev.get() : nullptr;
+                std::vector<uint8_t> want(fb);
+                uint32_t st_want[4], st[4] = {9, 9, 9, 9};
+                ref_deinterlace(want, cur.get(), pv, w, h, p, st_want);
+                deinterlace_frame_host(out.get(), cur.get(), pv, w, h, p, st);
+                CHECK(memcmp(out.get(), want.data(), fb) == 0);
+                CHECK(memcmp(st, st_want, sizeof st) == 0 && st[0] == (uint32_t)(w * (h / 2)));
+                deinterlace_frame_host(cur.get(), cur.get(), pv, w, h, p, nullptr);  // in place
+                CHECK(memcmp(cur.get(), want.data(), fb) == 0);
+                frames++;
+            }
+    // the scalar checks at their limits and one past each
+    const h264mi_deinterlace lo{0, 0, 0, 0}, hi{1, 1, 1, 255};
+    CHECK(deinterlace_ok(&lo) && deinterlace_ok(&hi) && !deinterlace_ok(nullptr));
+    for (int f = 0; f < 4; f++) {
+        h264mi_deinterlace a = lo, b = hi;
+        ((int32_t *)&a)[f]--; ((int32_t *)&b)[f]++;
+        CHECK(!deinterlace_ok(&a) && !deinterlace_ok(&b));
+        a = lo; ((int32_t *)&a)[f] = INT32_MIN; b = hi; ((int32_t *)&b)[f] = INT32_MAX;
+        CHECK(!deinterlace_ok(&a) && !deinterlace_ok(&b));
+    }
+    const uintptr_t D = 0x10000000u, Q = 0x20000000u, C = 0x30000000u, P = 0x40000000u, S = 0x50000000u;
+    auto ok = [&](uintptr_t d, uintptr_t q, uintptr_t c, uintptr_t p, int w, int h, int n, const h264mi_deinterlace *par, uintptr_t s) {
+        return deinterlace_args_ok((const void *)d, (const void *)q, (const void *)c, (const void *)p, w, h, n, par, (const void *)s);
+    };
+    const size_t nb = 3 * i420_bytes(32, 16), fb = i420_bytes(32, 16);
+    CHECK(ok(D, Q, C, P, 32, 16, 3, &hi, S) && ok(D, 0, C, 0, 32, 16, 3, &hi, 0) && ok(D, Q, C, P, 8192, 8192, 1, &lo, S) && ok(D, 0, C, 0, 2, 2, 1, &lo, 0));
+    CHECK(ok(C, 0, C, P, 32, 16, 3, &hi, S) && ok(D, P, C, P, 32, 16, 3, &hi, S) && ok(C, P, C, P, 32, 16, 3, &hi, S) && ok(D, Q, C, 0, 32, 16, 3, &hi, S));
+    CHECK(ok(D, Q, C, C - fb, 32, 16, 3, &hi, S) && ok(D, Q, C, C, 32, 16, 3, &hi, S) && ok(D, 0, C, C + 1, 32, 16, 3, &hi, 0));  // the read ranges overlap
+    CHECK(!ok(C, Q, C, C - fb, 32, 16, 3, &hi, S) && !ok(D, C - fb, C, C - fb, 32, 16, 3, &hi, S) && !ok(C, 0, C, C, 32, 16, 3, &hi, 0));  // one written
+    CHECK(!ok(0, Q, C, P, 32, 16, 3, &hi, S) && !ok(D, Q, 0, P, 32, 16, 3, &hi, S) && !ok(D, Q, C, P, 32, 16, 3, nullptr, S));
+    CHECK(!ok(D, Q, C, P, 32, 16, 0, &hi, S) && !ok(D, Q, C, P, 31, 16, 3, &hi, S) && !ok(D, Q, C, P, 32, 8194, 3, &hi, S) && !ok(D, Q, C, P, 0, 16, 3, &hi, S));
+    CHECK(!ok(D, D, C, P, 32, 16, 3, &hi, S) && !ok(P, Q, C, P, 32, 16, 3, &hi, S) && !ok(D, C, C, P, 32, 16, 3, &hi, S));
+    for (uintptr_t off : {(uintptr_t)1, (uintptr_t)(nb - 1), (uintptr_t)-1, (uintptr_t)-(intptr_t)(nb - 1)}) {
+        CHECK(!ok(C + off, Q, C, P, 32, 16, 3, &hi, S) && !ok(P + off, Q, C, P, 32, 16, 3, &hi, S) && !ok(Q + off, Q, C, P, 32, 16, 3, &hi, S));
+        CHECK(!ok(D, C + off, C, P, 32, 16, 3, &hi, S) && !ok(D, P + off, C, P, 32, 16, 3, &hi, S) && !ok(D, D + off, C, P, 32, 16, 3, &hi, S));
+    }
+    CHECK(ok(D, Q, C, P, 32, 16, 3, &hi, D + nb) && ok(D, Q, C, P, 32, 16, 3, &hi, D - 48));  // touching
+    for (uintptr_t b : {D, Q, C, P}) CHECK(!ok(D, Q, C, P, 32, 16, 3, &hi, b) && !ok(D, Q, C, P, 32, 16, 3, &hi, b + nb - 4) && !ok(D, Q, C, P, 32, 16, 3, &hi, b - 44));
+    for (uintptr_t off : {1, 2, 3}) CHECK(!ok(D, Q, C, P, 32, 16, 3, &hi, S + off));
+    printf("deinterlace: %d frames at 8 sizes x 8 parameter sets with and without a previous frame, out of place and in place, scalar and range checks\n", frames);
+}
+
 // the thumbnail and the block rule restated cell by cell: every cell looks its own block up
 static void ref_scenecut(std::vector<uint8_t> &thumb, const uint8_t *cur, const uint8_t *tprev, int w, int h, const h264mi_scenecut &p, uint32_t *st) {
     const int tw = (w + 3) / 4, th = (h + 3) / 4, nbx = (tw + 7) / 8, nby = (th + 7) / 8;
@@ -599,6 +712,7 @@ static void check_scenecut() {
 }
 
 int main() {
+    check_deinterlace();
     check_scenecut();
     check_denoise();
     check_pix();
