@@ -228,6 +228,30 @@ int h264mi_dec_streamed(h264mi_decoder *d);
    a bad argument. h264mi_dec_resolve_launches: resolution launches enqueued so far (diagnostic). */
 int h264mi_dec_set_resolve(h264mi_decoder *d, int mode);
 long long h264mi_dec_resolve_launches(h264mi_decoder *d);
+/* slice-copy concealment of lost slices. mode 0 (the default): a picture whose slices do not tile it
+   exactly yields no picture (got 0, err 3), as ever. mode 1: a non-IDR picture for which a reference picture exists,
+   at least one of whose slices parsed to its stop bit and whose good slices do not overlap, is decoded as if every
+   macroblock no good slice covers belonged to a P slice made of a single mb_skip_run -- first_mb_in_slice the gap's
+   first address, SliceQPY and the loop-filter fields those of the good slice that ends where the gap begins (for a gap
+   at address 0, of the one that begins where it ends). The picture is output (got 1, err 0) and becomes the reference
+   unless it is a non-reference picture. IDR pictures, pictures without a reference, access units without a good
+   slice, overlapping good slices, a failed slice whose records reach into a good one and anything outside the
+   supported subset are handled as with mode 0. While it is on no call is streamed (h264mi_dec_streamed reports 0);
+   turning it off restores the mode set before. Applies to the calls enqueued after it. Other modes: -1, nothing changed.
+   h264mi_dec_conceal: the mode in effect.
+   h264mi_dec_concealed: synchronises; mbs[f * nstreams + s] = macroblocks concealed in frame f of stream s of the last
+   decode call (0 for a clean or absent picture); returns that call's frame count, -1 on an error.
+   h264mi_dec_concealed_ptr: the same table on the device (max_frames x nstreams int32), written in stream order.
+   H264MI_DEC_CONCEAL=1 in the environment turns mode 1 on for the decoders behind init_decoder.
+   h264mi_conceal_gaps: the gap rule itself, on the host (the device path calls the same function): the slices of a
+   picture of total_mbs macroblocks as first[j], end[j] (one past the last MB) and ok[j] (parsed to the stop bit), j <
+   nsl <= 32, in any order -> gaps[3 * g] = {first, end, donor slice index} in address order, at most max_gaps of them
+   written. Returns the number of gaps (0: an exact tiling), -1: reject (no good slice, an overlap, a bad argument). */
+int h264mi_dec_set_conceal(h264mi_decoder *d, int mode);
+int h264mi_dec_conceal(h264mi_decoder *d);
+int h264mi_dec_concealed(h264mi_decoder *d, int *mbs);
+const int *h264mi_dec_concealed_ptr(h264mi_decoder *d);
+int h264mi_conceal_gaps(int total_mbs, int nsl, const int *first, const int *end, const int *ok, int *gaps, int max_gaps);
 /* reconstruction gate, for the next decode call only: frame f (< count) of that call is reconstructed once the
    device uint32 *d_counter has reached target + f * step (wrap-safe comparison), or after limit_us microseconds
    of waiting -- a scheduling hint, never a correctness condition. With an encoder's rows counter

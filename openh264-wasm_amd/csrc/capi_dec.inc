@@ -16,6 +16,9 @@ static int dec_host_call(DecSlot *slot, const unsigned char *data, int size, Dec
         // The working decoder is replaced only once its successor exists.
         DecCtx *n = dec_create(mbw, mbh, 1, nullptr, 1, 2, 1);
         if (n) n->slice_waves = 8;  // one picture per call: a multi-slice picture's slices parse concurrently
+        // H264MI_DEC_CONCEAL=1: lost slices of a non-IDR picture are concealed by slice copy (DESIGN.md §6.5) and the
+        // picture is returned; any other value, or none, leaves every access unit handled as before
+        if (const char *e = getenv("H264MI_DEC_CONCEAL")) { if (n && !strcmp(e, "1")) n->conceal = 1; }
         if (!n) return 0;
         dec_free(slot->c);
         slot->c = n;
@@ -217,7 +220,25 @@ int h264mi_dec_set_streamed(h264mi_decoder *d, int mode) {
     if (d->c->streamed_auto && dec_sync_all(d->c) != hipSuccess) return -1;
     return dec_set_streamed(d->c, mode);
 }
-int h264mi_dec_streamed(h264mi_decoder *d) { return d ? d->c->streamed : 0; }
+int h264mi_dec_streamed(h264mi_decoder *d) { return d && !d->c->conceal ? d->c->streamed : 0; }
+int h264mi_dec_set_conceal(h264mi_decoder *d, int mode) {
+    if (!d || mode < 0 || mode > 1) return -1;
+    d->c->conceal = mode;  // each call captures it when it is enqueued (dec_frames)
+    return 0;
+}
+int h264mi_dec_conceal(h264mi_decoder *d) { return d ? d->c->conceal : 0; }
+int h264mi_dec_concealed(h264mi_decoder *d, int *mbs) {
+    if (!d || !mbs) return -1;
+    DecCtx *c = d->c;
+    const int n = c->last_n;
+    if (n > 0 && hipMemcpyAsync(mbs, c->d_conc, sizeof(int32_t) * (size_t)n * c->S, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+    return n;
+}
+const int *h264mi_dec_concealed_ptr(h264mi_decoder *d) { return d ? d->c->d_conc : nullptr; }
+int h264mi_conceal_gaps(int total_mbs, int nsl, const int *first, const int *end, const int *ok, int *gaps, int max_gaps) {
+    return conceal_gaps(total_mbs, nsl, first, end, ok, gaps, max_gaps);
+}
 int h264mi_dec_set_resolve(h264mi_decoder *d, int mode) {
     if (!d || mode < 0 || mode > 1) return -1;
     d->c->resolve = mode;  // each call captures it when it is enqueued (dec_frames)

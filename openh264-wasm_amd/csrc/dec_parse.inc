@@ -1269,7 +1269,8 @@ __global__ __launch_bounds__(64) void dec_parse_prof_kernel(DecParseLaunch a) { 
 // provisional (streamed reconstruction): the slice data may still be parsing, so only what the scan and
 // header kernels decided is applied here; dec_frame_check (in dec_end_kernel) completes the decision afterwards.
 // ticket: the frame's two reconstruction tickets, zeroed here (no separate memset dispatch)
-struct DecBeginLaunch { int S, f; const DecDesc *desc; int provisional; uint32_t *ticket; };  // desc: first slot of the call
+// conceal / conc: slice-copy concealment is on for this call; where frame f of stream s reports its concealed MBs (conc[f * S + s])
+struct DecBeginLaunch { int S, f; const DecDesc *desc; int provisional; uint32_t *ticket; int conceal; int32_t *conc; };  // desc: first slot of the call
 // the picture: every slice parsed, and the slices (in any order) cover its macroblocks exactly once:
 // a chain from MB 0 through first_mb -> end_mb that uses each of the nsl slices once
 DEV bool slices_cover(const DecFrame *F) {
@@ -1284,6 +1285,60 @@ DEV bool slices_cover(const DecFrame *F) {
     }
     return next == total;
 }
+
+// ---------------------------------------------------------------- slice-copy concealment (DESIGN.md §6.5)
+// dec_conceal_kernel, behind the slice data of a call and ahead of dec_resolve_kernel / the reconstruction, only
+// while concealment is on: for every picture of the call that is not an IDR picture and whose good slices leave
+// gaps (conceal_host.h: conceal_gaps, conceal_clean), the MB records of every gap, in dec_parse_kernel's own
+// format -- P_Skip at the donor slice's QP, the synthetic slice's word (first_mb = the gap's first address, the
+// donor's loop-filter fields) in dword 31 -- so that the resolve pass, the reconstruction rows and the deblocking
+// rows read a picture whose lost slices were single skip runs. It also leaves the number of MBs it wrote in
+// DecFrame::ncon (0: nothing to conceal, or a picture that stays rejected); whether a reference exists is the
+// reconstruction side's to know, so dec_frame_begin_kernel makes the final decision from ncon.
+// Work split: a block of 256 lanes per CONCEAL_SPAN MB addresses of a picture; lane t writes dword t & 31 of every
+// eighth record of the gaps' part of that span (a wave instruction = two whole records, 256 contiguous bytes).
+// Lane 0 of each block derives the gap table itself (<= 32 slices: a few hundred scalar steps) -- no second launch.
+constexpr int CONCEAL_SPAN = 512;
+struct DecConcealLaunch { int np, mbw, mbh; const DecDesc *desc; };  // desc: first slot of the call, np = frames x streams
+__global__ __launch_bounds__(256) void dec_conceal_kernel(DecConcealLaunch a) {
+    __shared__ int s_first[H264MI_MAX_SLICES], s_end[H264MI_MAX_SLICES], s_ok[H264MI_MAX_SLICES];
+    __shared__ int s_gap[3 * H264MI_MAX_GAPS];
+    __shared__ uint32_t s_rec[H264MI_MAX_GAPS][3];  // per gap: record dwords 0, 1, 31
+    __shared__ int s_n;
+    const int t = threadIdx.x, w = blockIdx.x, total = a.mbw * a.mbh;
+    if (w >= a.np) return;
+    const DecDesc &D = a.desc[w];
+    DecFrame *F = D.frm;
+    const int nsl = F->nsl;
+    const bool cand = F->hdr_ok && !F->err && nsl > 0 && nsl <= H264MI_MAX_SLICES && F->ps.mbw == a.mbw && F->ps.mbh == a.mbh &&
+                      F->e[F->sl[0].nal].type != 5;  // (the slices of a picture agree on IDR-ness: dec_hdr_kernel)
+    if (cand && t < nsl) { s_first[t] = F->sl[t].first_mb; s_end[t] = F->sl[t].end_mb; s_ok[t] = F->sl[t].ok; }
+    __syncthreads();
+    if (t == 0) {
+        int n = cand ? conceal_gaps(total, nsl, s_first, s_end, s_ok, s_gap, H264MI_MAX_GAPS) : 0;
+        if (n > H264MI_MAX_GAPS || (n > 0 && !conceal_clean(total, nsl, s_first, s_end, s_ok))) n = 0;
+        int mbs = 0;
+        for (int g = 0; g < n; g++) {
+            const SliceEnt &donor = F->sl[s_gap[3 * g + 2]];
+            const int qp = donor.qp, qpc = c_CHROMA_QP[clip3(0, 51, qp + F->cqp)];
+            s_rec[g][0] = MI_PSKIP | ((uint32_t)qp << 8);
+            s_rec[g][1] = (uint32_t)qpc << 8;
+            s_rec[g][2] = (uint32_t)s_gap[3 * g] | (donor.info & ~0xFFFFFu);
+            mbs += s_gap[3 * g + 1] - s_gap[3 * g];
+        }
+        s_n = n > 0 ? n : 0;
+        if (blockIdx.y == 0) F->ncon = n > 0 ? mbs : 0;
+    }
+    __syncthreads();
+    const int n = s_n, lo = (int)blockIdx.y * CONCEAL_SPAN, hi = min(lo + CONCEAL_SPAN, total), dw = t & 31;
+    uint32_t *info32 = (uint32_t *)D.info;
+    for (int g = 0; g < n; g++) {
+        const int g0 = max(s_gap[3 * g], lo), g1 = min(s_gap[3 * g + 1], hi);  // g1 <= total: inside the slot's nmb records
+        const uint32_t v = dw == 0 ? s_rec[g][0] : dw == 1 ? s_rec[g][1] : dw == 31 ? s_rec[g][2] : (dw >= 2 && dw <= 5 ? 0x02020202u : 0u);
+        for (int mb = g0 + (t >> 5); mb < g1; mb += 8) info32[(size_t)mb * 32 + dw] = v;
+    }
+}
+
 __global__ void dec_frame_begin_kernel(DecBeginLaunch a) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s == 0 && a.ticket) { a.ticket[0] = 0; a.ticket[1] = 0; }
@@ -1293,7 +1348,12 @@ __global__ void dec_frame_begin_kernel(DecBeginLaunch a) {
     const DecFrame *F = D.frm;
     if (F->hdr_ok) st->ps = F->ps;
     bool ok = F->hdr_ok && !F->err;
-    if (ok && !a.provisional) ok = slices_cover(F) && !F->res_abort;
+    int ncon = 0;  // MBs concealed: the good slices leave gaps, dec_conceal_kernel filled them, and a reference exists
+    if (ok && !a.provisional) {
+        const bool cover = slices_cover(F);
+        if (!cover && a.conceal && F->ncon > 0 && st->has_ref) ncon = F->ncon;
+        ok = (cover || ncon > 0) && !F->res_abort;
+    }
     // a P slice with no earlier decoded picture (no reference) yields no picture, like a parse error
     if (ok && F->anyp && !st->has_ref) ok = false;
     st->got_pic = ok ? 1 : 0;
@@ -1301,6 +1361,7 @@ __global__ void dec_frame_begin_kernel(DecBeginLaunch a) {
     // per frame: a damaged access unit yields no picture, the next one decodes (no slices at all: no error)
     st->err = ok ? 0 : (F->err ? F->err : (F->hdr_ok ? (F->res_abort ? 1 : 3) : 0));
     if (ok) st->epoch = st->epoch + 1;
+    if (a.conc) a.conc[a.f * a.S + s] = ok ? ncon : 0;
 }
 // Streamed reconstruction, after dec_recon_kernel (and after the slice data of the call is parsed): the
 // picture stands only if its slices cover it and the wavefront was not aborted; otherwise it is

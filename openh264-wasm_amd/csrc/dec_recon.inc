@@ -429,7 +429,7 @@ DEV uint32_t res_type_word(const MbInfo &R) {
 // word (DecFrame::res_abort; dec_frame_begin_kernel then drops the picture). No samples, coefficients or
 // reference windows: 5 KB less LDS and a fifth of the reconstruction's registers.
 #define H264MI_RES_GRANULES_PER_MB 5
-struct DecResolveLaunch { int np, mbw, mbh; const DecDesc *desc; uint32_t *ticket; uint32_t base, tag; };
+struct DecResolveLaunch { int np, mbw, mbh; const DecDesc *desc; uint32_t *ticket; uint32_t base, tag; int conceal; };
 struct ResLds {
     uint32_t gm[3][5];         // above-row MBs, as DecLds::gm
     int8_t modes[16];
@@ -451,7 +451,8 @@ __global__ __launch_bounds__(64) void dec_resolve_kernel(DecResolveLaunch a) {
     DecFrame *F = D.frm;
     // the pictures dec_frame_begin_kernel may accept (it also wants a reference for P slices, which only the
     // reconstruction side knows: a picture resolved for nothing costs nothing else)
-    if (!uni(F->hdr_ok) || uni(F->err) || !uni((int)slices_cover(F))) return;
+    // (with concealment on, also the pictures whose gaps dec_conceal_kernel filled)
+    if (!uni(F->hdr_ok) || uni(F->err) || !uni((int)(slices_cover(F) || (a.conceal && F->ncon > 0)))) return;
     int32_t *abort_word = &F->res_abort;
     const uint32_t tag = a.tag;
     const int mbw = a.mbw;

@@ -193,7 +193,8 @@ struct DecFrame {          // per (frame slot, stream): written by dec_scan_kern
     int32_t anyp;          // some slice is a P slice (needs a reference)
     int32_t cqp;           // chroma_qp_index_offset
     int32_t res_abort;     // dec_resolve_kernel gave up on this picture (bounded wait): its records are not resolved
-    int32_t pad_h[4];
+    int32_t ncon;          // dec_conceal_kernel (only while concealment is on): MBs of the gaps it filled, 0 for none
+    int32_t pad_h[3];
     DecParams ps;          // parameter sets in effect for this frame's slices (cropping for the output)
     NalEnt e[H264MI_MAX_NALS];
     SliceEnt sl[H264MI_MAX_SLICES];

@@ -1,6 +1,7 @@
 // runtime_dec.inc -- host runtime of the decoder: HBM allocation and the per-call launch sequence
 //   dec_parse_kernel -> dec_resolve_kernel -> dec_recon_pre_kernel (+ deblocking rows) -> dec_end_kernel
-//   (a streamed call: dec_parse_kernel -> dec_recon_kernel, which resolves the records itself)
+//   (a streamed call: dec_parse_kernel -> dec_recon_kernel, which resolves the records itself;
+//    with slice-copy concealment on: dec_parse_kernel -> dec_conceal_kernel -> the rest, never streamed)
 namespace h264mi {
 
 constexpr int DEC_PSTREAMS = 3;      // default parse streams: consecutive calls rotate (each wants its own HW queue:
@@ -31,6 +32,12 @@ struct DecCtx {
     // frame on the reconstruction stream gained nothing, profiles/dec_preresolve/placement_ab.txt). 0: never
     // (the in-wavefront build, as a streamed call). Env H264MI_DEC_RESOLVE at creation, h264mi_dec_set_resolve.
     int resolve = 1;
+    // slice-copy concealment of lost slices (DESIGN.md §6.5; h264mi_dec_set_conceal, the C-ABI slots: env
+    // H264MI_DEC_CONCEAL=1): each call captures it when it is enqueued. While it is on no call is streamed (the gaps
+    // are known only once every slice is parsed); `streamed` keeps the mode that returns when it is turned off.
+    int conceal = 0;
+    int32_t *d_conc = nullptr;          // [B][S] concealed MBs of the frames of the last call (dec_frame_begin_kernel)
+    int last_n = 0;                     // frames of the last call
     long long resolve_launches = 0;
     uint32_t *d_rticket = nullptr;      // its ticket counters, never reset: one per slot group (a group's launches are
     uint32_t rt_base[16] = {};          // ordered by ev_recon); the value each has before its next launch
@@ -134,6 +141,7 @@ static void dec_free(DecCtx *c) {
     for (int k = 0; k < 2; k++) for (auto e : c->tev[k]) (void)hipEventDestroy(e);
     for (int i = 0; i < DecCtx::PMAX; i++) if (c->pst[i]) (void)hipStreamDestroy(c->pst[i]);
     (void)hipFree(c->d_pool);
+    (void)hipFree(c->d_conc);
     if (c->h_in) (void)hipHostFree(c->h_in);
     (void)hipFree(c->d_nal);
     (void)hipFree(c->d_rgba);
@@ -225,13 +233,15 @@ static DecCtx *dec_create(int mbw, int mbh, int S, hipStream_t stream, int B = 1
     (void)hipMemcpyAsync(c->d_desc, c->h_desc.data(), sizeof(DecDesc) * nsl, hipMemcpyHostToDevice, c->stream);
     (void)hipMemcpyAsync(c->d_dbk, hd.data(), sizeof(DbkDesc) * nsl, hipMemcpyHostToDevice, c->stream);
     (void)hipMemcpyAsync(c->d_pd, hp.data(), sizeof(PlanesDesc) * S, hipMemcpyHostToDevice, c->stream);
+    if (hipMalloc(&c->d_conc, sizeof(int32_t) * (size_t)S * B) != hipSuccess) c->d_conc = nullptr;
+    else (void)hipMemsetAsync(c->d_conc, 0, sizeof(int32_t) * (size_t)S * B, c->stream);
     if (getenv("H264MI_RECON_PROF") && hipMalloc(&c->d_rprof, sizeof(uint64_t) * 16) == hipSuccess)
         (void)hipMemsetAsync(c->d_rprof, 0, sizeof(uint64_t) * 16, c->stream);
     if (getenv("H264MI_PARSE_PROF") && hipMalloc(&c->d_prof, sizeof(uint64_t) * 16 * nsl) == hipSuccess)
         (void)hipMemsetAsync(c->d_prof, 0, sizeof(uint64_t) * 16 * nsl, c->stream);
     c->lds_bytes = RING_BYTES + 2 * 4 * (size_t)mbw;  // RBSP ring + per column {luma, chroma} TotalCoeff contexts
     c->lds_min = c->lds_bytes;
-    bool ok = c->h_in && hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) == hipSuccess;
+    bool ok = c->h_in && c->d_conc && hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i < c->np && ok; i++) ok = hipStreamCreateWithFlags(&c->pst[i], hipStreamNonBlocking) == hipSuccess;
     for (auto *v : {&c->ev_hdr, &c->ev_parsed, &c->ev_recon}) {
         v->assign(c->NG, nullptr);
@@ -271,7 +281,8 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
     if (n <= 0 || n > c->B) return -1;
     const int S = c->S, ns = n * S, g = c->grp, slot0 = g * c->B;
     const uint32_t pin = c->calls & 1, tag = c->calls + 1;
-    const int streamed = c->streamed;
+    const int conceal = c->conceal;
+    const int streamed = conceal ? 0 : c->streamed;  // gaps are known only once every slice of the picture is parsed
     // a streamed call reconstructs while its slice data is still being parsed: nothing can resolve ahead of it
     const int pre = streamed ? 0 : c->resolve;
     hipStream_t ps = c->pst[c->calls % c->np];
@@ -294,9 +305,13 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
     hipLaunchKernelGGL(c->d_prof ? dec_parse_prof_kernel : dec_parse_kernel, dim3(ns * c->slice_waves), dim3(64), c->lds_bytes, ps,
                        DecParseLaunch{S, n, c->mbw, c->mbh, (int)pin, dd, c->d_prof ? c->d_prof + (size_t)slot0 * S * 16 : nullptr,
                                       c->slice_waves, tag, streamed});
+    if (conceal)  // the gap records of every picture of the call (they depend on no sample: one launch serves all frames;
+                  // what does depend on the frame before -- is there a reference -- is dec_frame_begin_kernel's, per frame)
+        hipLaunchKernelGGL(dec_conceal_kernel, dim3(ns, (c->nmb + CONCEAL_SPAN - 1) / CONCEAL_SPAN), dim3(256), 0, ps,
+                           DecConcealLaunch{ns, c->mbw, c->mbh, dd});
     if (pre) {  // every picture of the call, before ev_parsed
         hipLaunchKernelGGL(dec_resolve_kernel, dim3(ns * c->mbh), dim3(64), 0, ps,
-                           DecResolveLaunch{ns, c->mbw, c->mbh, dd, c->d_rticket + g, c->rt_base[g], tag});
+                           DecResolveLaunch{ns, c->mbw, c->mbh, dd, c->d_rticket + g, c->rt_base[g], tag, conceal});
         c->rt_base[g] += (uint32_t)(ns * c->mbh);
         c->resolve_launches++;
     }
@@ -309,7 +324,7 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
     for (int f = 0; f < n; f++) {
         const DecDesc *df = dd + (size_t)f * S;
         hipLaunchKernelGGL(dec_frame_begin_kernel, dim3((S + 63) / 64), dim3(64), 0, c->stream,
-                           DecBeginLaunch{S, f, dd, streamed, c->d_ticket + 2 * (slot0 + f)});
+                           DecBeginLaunch{S, f, dd, streamed, c->d_ticket + 2 * (slot0 + f), conceal, c->d_conc});
         if (streamed && f == 0 && c->gate_rows > 0)  // a forced (large) streamed launch follows the parse's last quarter only
             hipLaunchKernelGGL(dec_gate_kernel, dim3(1), dim3(64), 0, c->stream, DecGateLaunch{S, df, tag, (uint32_t)c->gate_rows});
         if (rg_counter && f < rg_count)
@@ -340,6 +355,7 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
     HIPCHECK(hipGetLastError());
     c->grp = (g + 1) % c->NG;
     c->calls++;
+    c->last_n = n;
     return 0;
 }
 // Parse streams: each decode call's entropy decoding runs on the next of np streams, so up to np calls

@@ -91,6 +91,11 @@ def lib():
             'h264mi_dec_streamed': (i, [vp]),
             'h264mi_dec_set_resolve': (i, [vp, i]),
             'h264mi_dec_resolve_launches': (ctypes.c_longlong, [vp]),
+            'h264mi_dec_set_conceal': (i, [vp, i]),
+            'h264mi_dec_conceal': (i, [vp]),
+            'h264mi_dec_concealed': (i, [vp, vp]),
+            'h264mi_dec_concealed_ptr': (vp, [vp]),
+            'h264mi_conceal_gaps': (i, [i, i, vp, vp, vp, vp, i]),
             'h264mi_dec_set_streamed_budget': (i, [i]),
             'h264mi_nal_pack': (i, [vp, vp, ctypes.c_size_t, vp, i, vp]),
             'h264mi_nal_unpack': (i, [vp, vp, ctypes.c_size_t, vp, i, vp]),
@@ -686,6 +691,19 @@ class BatchEncoder:
             pass
 
 
+def conceal_gaps(total_mbs, slices, max_gaps=33):
+    """the gap rule of slice-copy concealment (h264mi_conceal_gaps; the decoder's kernels call the same function):
+    slices = [(first_mb, end_mb, ok), ...] of one picture in any order -> [(first, end, donor index), ...] in address
+    order ([] for an exact tiling), or None when the picture is rejected (no good slice, an overlap, a bad argument)"""
+    n = len(slices)
+    arr = [(ctypes.c_int * max(1, n))(*[int(sl[k]) for sl in slices]) for k in range(3)]
+    out = (ctypes.c_int * (3 * max(1, max_gaps)))()
+    r = lib().h264mi_conceal_gaps(total_mbs, n, arr[0], arr[1], arr[2], out, max_gaps)
+    if r < 0:
+        return None
+    return [(out[3 * g], out[3 * g + 1], out[3 * g + 2]) for g in range(min(r, max_gaps))]
+
+
 def masked_stream(cu_lo, cu_hi, complement=False):
     """A torch stream (ExternalStream over h264mi_stream_create_cus) restricted to CU mask bits
     [cu_lo, cu_hi), or to every other CU. Pairs with BatchDecoder.set_parse_cus."""
@@ -827,6 +845,27 @@ class BatchDecoder:
 
     def resolve_launches(self):
         return self._L.h264mi_dec_resolve_launches(self._d)
+
+    def set_conceal(self, mode):
+        """slice-copy concealment of lost slices (h264mi_dec_set_conceal): 1 on, 0 off (default). While it is on no call
+        is streamed. ValueError, with nothing changed, on any other mode."""
+        if self._L.h264mi_dec_set_conceal(self._d, mode) != 0:
+            raise ValueError(f'h264mi_dec_set_conceal({mode!r}) refused')
+
+    def conceal(self):
+        return self._L.h264mi_dec_conceal(self._d)
+
+    def concealed(self):
+        """synchronises; per frame of the last decode call, the macroblocks concealed in each stream: [[mbs] * S] * frames"""
+        out = (ctypes.c_int * (self.S * self.B))()
+        n = self._L.h264mi_dec_concealed(self._d, out)
+        if n < 0:
+            raise RuntimeError('h264mi_dec_concealed failed')
+        return [list(out[f * self.S:(f + 1) * self.S]) for f in range(n)]
+
+    def concealed_ptr(self):
+        """device address of the same table (max_frames x S int32), written in stream order"""
+        return self._L.h264mi_dec_concealed_ptr(self._d)
 
     def set_slice_waves(self, k):
         """slice-data waves per picture (h264mi_dec_set_slice_waves): a multi-slice picture's slices in parallel"""
