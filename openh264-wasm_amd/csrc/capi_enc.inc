@@ -1,4 +1,6 @@
-// capi_enc.inc -- extern "C" boundary, encoder half.
+// capi_enc.inc -- extern "C" boundary, encoder half: the checks that belong to the boundary (null handle, null
+// pointer, the arguments of the standalone *_dev calls) and forwards into the runtime (runtime_enc.inc; the stages in
+// front of the frame step: enc_input.inc).
 //
 // (1) The reference wrapper surface (openh264_wrapper.cpp): init_encoder :198-228,
 //     force_key_frame :230-236, encode_frame :315-356, encode_frame_yuv_i420 :358-389,
@@ -190,71 +192,12 @@ int h264mi_enc_frames_skipped(h264mi_encoder *e, int stream) {
     if (hipMemcpy(&st, e->c->d_st + stream, sizeof(EncState), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return st.skipped;
 }
-// the tail of every entry point that codes the input area: the deinterlacer in force (DESIGN.md §5.15;
-// deinterlace.hip; nothing when off) -- in place against the previous unfiltered frames, which the same launch
-// replaces; the first frame spatial only --, the pre-filter in force (DESIGN.md §5.13; denoise.hip;
-// nothing when off) -- the first frame only copied to the state, every later one filtered in place against the state,
-// which receives the same bytes --, the key-frame policy in force (below), the overlay list in force blended into it
-// (DESIGN.md §5.6; overlay.hip; nothing without a list), then the frame step. A launch that fails ends the call with
-// -1 where it stands: no frame is submitted, and the states of the steps in front of it have advanced
-static int enc_code_input(EncCtx *c) {
-    if (c->di_on) {
-        if (launch_deinterlace_i420(c->d_src, c->d_di, c->d_src, c->di_has ? c->d_di : nullptr, c->w, c->h, c->S, c->di, nullptr, c->stream) != 0)
-            return -1;
-        c->di_has = true;
-    }
-    if (c->dn_on) {
-        if (!c->dn_has) {
-            if (hipMemcpyAsync(c->d_dn, c->d_src, (size_t)c->S * c->fbytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
-            c->dn_has = true;
-        } else if (launch_denoise_i420(c->d_src, c->d_dn, c->d_src, c->d_dn, c->w, c->h, c->S, c->dn, nullptr, c->stream) != 0) {
-            return -1;
-        }
-    }
-    // the key-frame policy in force (DESIGN.md §5.14; scenecut.hip; nothing when off): the detector -- the first frame
-    // only stores its thumbnails, every later one advances them in place and leaves its statistics; no launch with
-    // share == 0 --, then the decision, which sets EncState::force_idr in front of the frame step's begin kernel
-    if (c->sc_on) {
-        uint32_t *stats = nullptr;
-        if (c->sc.share > 0) {
-            const bool has = c->sc_has;
-            if (has) stats = c->d_sc + 16 * (size_t)c->S;
-            if (launch_scenecut_i420(stats, c->d_sc_thumb, c->d_src, has ? c->d_sc_thumb : nullptr, c->w, c->h, c->S, c->sc, c->stream) != 0)
-                return -1;
-            c->sc_has = true;
-        }
-        if (launch_scenecut_decide(c->d_st, c->d_sc, stats, c->S, c->sc, c->stream) != 0) return -1;
-    }
-    if (!c->ov.empty() &&
-        launch_overlay_i420(c->d_src, c->w, c->h, c->ov_sprites, c->ov_w, c->ov_h, c->ov.data(), (int)c->ov.size(), c->stream) != 0)
-        return -1;
-    return enc_frame(c, c->d_src);
-}
-// with the deinterlacer, the pre-filter or the key-frame policy on or an overlay list in force the caller's frames are
-// copied into the input area, filtered, looked at and blended there and coded from there
-int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) {
-    if (!e || !d_frames) return -1;
-    EncCtx *c = e->c;
-    if (c->ov.empty() && !c->di_on && !c->dn_on && !c->sc_on) return enc_frame(c, (const uint8_t *)d_frames);
-    if (d_frames != (const void *)c->d_src) {
-        const size_t nb = (size_t)c->S * c->fbytes;
-        if (byte_ranges_overlap(d_frames, nb, c->d_src, nb)) return -1;  // partly inside the input area
-        if (hipMemcpyAsync(c->d_src, d_frames, nb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
-    }
-    return enc_code_input(c);
-}
+// The input chain (DESIGN.md §5.16; enc_input.inc): with a stage on the caller's frames are coded from the input area
+int h264mi_enc_encode(h264mi_encoder *e, const void *d_frames) { return e && d_frames ? enc_encode(e->c, d_frames) : -1; }
 int h264mi_enc_set_overlays(h264mi_encoder *e, const void *d_sprites, int ow, int oh, int nsprites, const h264mi_overlay *ov, int nov) {
-    if (!e) return -1;
-    EncCtx *c = e->c;
-    if (nov == 0) { c->ov.clear(); c->ov_sprites = nullptr; return 0; }
-    if (!d_sprites || !overlay_args_ok(c->w, c->h, c->S, ow, oh, nsprites, ov, nov) ||
-        byte_ranges_overlap(c->d_src, c->S * i420_bytes(c->w, c->h), d_sprites, nsprites * i420a_bytes(ow, oh)))
-        return -1;
-    c->ov.assign(ov, ov + nov);
-    c->ov_sprites = (const uint8_t *)d_sprites; c->ov_w = ow; c->ov_h = oh;
-    return 0;
+    return e ? enc_set_overlays(e->c, d_sprites, ow, oh, nsprites, ov, nov) : -1;
 }
-int h264mi_enc_overlays(h264mi_encoder *e) { return e ? (int)e->c->ov.size() : -1; }
+int h264mi_enc_overlays(h264mi_encoder *e) { return e ? (int)e->c->in.ov.list.size() : -1; }
 // The temporal denoiser (DESIGN.md §5.13; denoise.hip; the checks: picture_host.h): n frames, one launch
 int h264mi_denoise_ok(const h264mi_denoise *p) { return denoise_ok(p) ? 0 : -1; }
 int h264mi_i420_denoise_dev(void *d_dst, void *d_dst2, const void *d_cur, const void *d_prev, int w, int h, int n, const h264mi_denoise *p,
@@ -263,34 +206,8 @@ int h264mi_i420_denoise_dev(void *d_dst, void *d_dst2, const void *d_cur, const 
     return launch_denoise_i420((uint8_t *)d_dst, (uint8_t *)d_dst2, (const uint8_t *)d_cur, (const uint8_t *)d_prev, w, h, n, *p,
                                (uint32_t *)d_stats, (hipStream_t)hip_stream);
 }
-// the encoder's pre-filter: NULL or both strengths 0 turn it off and free the state (after the stream has finished with
-// it); a refused call leaves the setting in force
-int h264mi_enc_set_denoise(h264mi_encoder *e, const h264mi_denoise *p) {
-    if (!e || (p && !denoise_ok(p))) return -1;
-    EncCtx *c = e->c;
-    if (!p || (p->strength_y == 0 && p->strength_c == 0)) {
-        if (c->d_dn) {
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipFree(c->d_dn);
-            c->d_dn = nullptr;
-        }
-        c->dn_on = c->dn_has = false;
-        return 0;
-    }
-    if (!canvas_ok(c->w, c->h)) return -1;
-    if (!c->d_dn) {
-        if (hipMalloc(&c->d_dn, (size_t)c->S * c->fbytes) != hipSuccess) { c->d_dn = nullptr; return -1; }
-        c->dn_has = false;
-    }
-    c->dn = *p;
-    c->dn_on = true;
-    return 0;
-}
-int h264mi_enc_denoise(h264mi_encoder *e, h264mi_denoise *out) {
-    if (!e) return -1;
-    if (e->c->dn_on && out) *out = e->c->dn;
-    return e->c->dn_on ? 1 : 0;
-}
+int h264mi_enc_set_denoise(h264mi_encoder *e, const h264mi_denoise *p) { return e ? enc_set_denoise(e->c, p) : -1; }
+int h264mi_enc_denoise(h264mi_encoder *e, h264mi_denoise *out) { return e ? stage_get(e->c->in.dn, out) : -1; }
 // The deinterlacer (DESIGN.md §5.15; deinterlace.hip; the checks: picture_host.h): n frames, one launch
 int h264mi_deinterlace_ok(const h264mi_deinterlace *p) { return deinterlace_ok(p) ? 0 : -1; }
 int h264mi_i420_deinterlace_dev(void *d_dst, void *d_prev_out, const void *d_cur, const void *d_prev, int w, int h, int n,
@@ -304,34 +221,8 @@ int h264mi_i420_deinterlace_host(void *dst, const void *cur, const void *prev, i
     deinterlace_frame_host((uint8_t *)dst, (const uint8_t *)cur, (const uint8_t *)prev, w, h, *p, stats);
     return 0;
 }
-// the encoder's deinterlacer: NULL turns it off and frees the state (after the stream has finished with it); a refused
-// call leaves the setting in force
-int h264mi_enc_set_deinterlace(h264mi_encoder *e, const h264mi_deinterlace *p) {
-    if (!e || (p && !deinterlace_ok(p))) return -1;
-    EncCtx *c = e->c;
-    if (!p) {
-        if (c->d_di) {
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipFree(c->d_di);
-            c->d_di = nullptr;
-        }
-        c->di_on = c->di_has = false;
-        return 0;
-    }
-    if (!canvas_ok(c->w, c->h)) return -1;
-    if (!c->d_di) {
-        if (hipMalloc(&c->d_di, (size_t)c->S * c->fbytes) != hipSuccess) { c->d_di = nullptr; return -1; }
-        c->di_has = false;
-    }
-    c->di = *p;
-    c->di_on = true;
-    return 0;
-}
-int h264mi_enc_deinterlace(h264mi_encoder *e, h264mi_deinterlace *out) {
-    if (!e) return -1;
-    if (e->c->di_on && out) *out = e->c->di;
-    return e->c->di_on ? 1 : 0;
-}
+int h264mi_enc_set_deinterlace(h264mi_encoder *e, const h264mi_deinterlace *p) { return e ? enc_set_deinterlace(e->c, p) : -1; }
+int h264mi_enc_deinterlace(h264mi_encoder *e, h264mi_deinterlace *out) { return e ? stage_get(e->c->in.di, out) : -1; }
 // The scene-cut detector (DESIGN.md §5.14; scenecut.hip; the checks: picture_host.h): n frames, one launch
 int h264mi_scenecut_ok(const h264mi_scenecut *p) { return scenecut_ok(p) ? 0 : -1; }
 int h264mi_thumb_size(int w, int h, int *tw, int *th) {
@@ -349,51 +240,11 @@ int h264mi_i420_scenecut_dev(void *d_stats, void *d_thumb_out, const void *d_cur
     return launch_scenecut_i420((uint32_t *)d_stats, (uint8_t *)d_thumb_out, (const uint8_t *)d_cur, (const uint8_t *)d_thumb_prev, w, h, n, *p,
                                 (hipStream_t)hip_stream);
 }
-// the encoder's key-frame policy: NULL or share == 0 && max_gap == 0 turn it off and free the state (after the stream
-// has finished with it); a refused call leaves the setting in force
-int h264mi_enc_set_scenecut(h264mi_encoder *e, const h264mi_scenecut *p) {
-    if (!e || (p && !scenecut_ok(p))) return -1;
-    EncCtx *c = e->c;
-    if (!p || (p->share == 0 && p->max_gap == 0)) {
-        if (c->d_sc || c->d_sc_thumb) {
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipFree(c->d_sc);
-            (void)hipFree(c->d_sc_thumb);
-            c->d_sc = nullptr; c->d_sc_thumb = nullptr;
-        }
-        c->sc_on = c->sc_has = false;
-        return 0;
-    }
-    if (!canvas_ok(c->w, c->h)) return -1;
-    uint32_t *words = c->d_sc;
-    uint8_t *thumb = c->d_sc_thumb;
-    if (!words) {  // 16 words a stream, then 8 statistics words a stream
-        if (hipMalloc(&words, 24 * sizeof(uint32_t) * (size_t)c->S) != hipSuccess) return -1;
-        if (hipMemsetAsync(words, 0, 24 * sizeof(uint32_t) * (size_t)c->S, c->stream) != hipSuccess) { (void)hipFree(words); return -1; }
-    }
-    if (p->share > 0 && !thumb && hipMalloc(&thumb, (size_t)c->S * thumb_bytes(c->w, c->h)) != hipSuccess) {
-        if (!c->d_sc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(words); }
-        return -1;
-    }
-    if (p->share == 0 && thumb) {  // period only: no detector runs, the thumbnails of an earlier setting go
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(thumb);
-        thumb = nullptr;
-    }
-    if (!c->d_sc_thumb || !thumb) c->sc_has = false;
-    c->d_sc = words; c->d_sc_thumb = thumb;
-    c->sc = *p;
-    c->sc_on = true;
-    return 0;
-}
-int h264mi_enc_scenecut(h264mi_encoder *e, h264mi_scenecut *out) {
-    if (!e) return -1;
-    if (e->c->sc_on && out) *out = e->c->sc;
-    return e->c->sc_on ? 1 : 0;
-}
+int h264mi_enc_set_scenecut(h264mi_encoder *e, const h264mi_scenecut *p) { return e ? enc_set_scenecut(e->c, p) : -1; }
+int h264mi_enc_scenecut(h264mi_encoder *e, h264mi_scenecut *out) { return e ? stage_get(e->c->in.sc, out) : -1; }
 int h264mi_enc_scenecut_state(h264mi_encoder *e, int stream, uint32_t *out16) {
-    if (!e || !out16 || !e->c->sc_on || stream < 0 || stream >= e->c->S) return -1;
-    if (hipMemcpyAsync(out16, e->c->d_sc + 16 * (size_t)stream, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->c->stream) != hipSuccess) return -1;
+    if (!e || !out16 || !e->c->in.sc.on || stream < 0 || stream >= e->c->S) return -1;
+    if (hipMemcpyAsync(out16, e->c->in.sc.d_words + 16 * (size_t)stream, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->c->stream) != hipSuccess) return -1;
     return hipStreamSynchronize(e->c->stream) == hipSuccess ? 0 : -1;
 }
 // Sprites from RGBA and the standalone blend (DESIGN.md §5.6; overlay.hip)
@@ -458,7 +309,7 @@ int h264mi_i420_scale_dev(void *d_dst, int dw, int dh, const void *d_src, int sw
 // its stream, then the frame step as h264mi_enc_encode runs it (the quality records then see the scaled source).
 // Every refusal comes before the first launch
 int h264mi_enc_encode_scaled(h264mi_encoder *e, const void *d_frames, int src_w, int src_h) {
-    if (!e || !d_frames || e->c->di_on) return -1;  // the deinterlacer belongs in front of a vertical resampling
+    if (!e || !d_frames || enc_resampling_refused(e->c)) return -1;
     EncCtx *c = e->c;
     if (!scale_args_ok(c->w, c->h, src_w, src_h, c->S) || i420_ranges_overlap(c->d_src, c->w, c->h, c->S, d_frames, src_w, src_h, c->S))
         return -1;
@@ -480,7 +331,7 @@ int h264mi_i420_orient_dev(void *d_dst, const void *d_src, int sw, int sh, int n
 // orientation): one batched launch into the encoder's own input area on its stream, then the frame step as
 // h264mi_enc_encode runs it. Every refusal comes before the first launch
 int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orient) {
-    if (!e || !d_frames || e->c->di_on) return -1;  // as h264mi_enc_encode_scaled
+    if (!e || !d_frames || enc_resampling_refused(e->c)) return -1;
     EncCtx *c = e->c;
     int sw, sh;  // the inverse turns a w x h picture back into the source's size
     if (orient_size(orient_inverse(orient), c->w, c->h, &sw, &sh) != 0 || !orient_args_ok(orient, sw, sh, c->S) ||
@@ -531,7 +382,7 @@ int h264mi_mosaic_cells(h264mi_cell *out, int cap, int n, int src_w, int src_h, 
 // Every refusal comes before the first launch
 static int enc_encode_cells(h264mi_encoder *e, const void *d_src, int src_w, int src_h, int nsrc, const h264mi_cell *cells, int ncells,
                             bool may_enlarge, int filter, int bg_y, int bg_cb, int bg_cr) {
-    if (!e || !d_src || e->c->di_on) return -1;  // as h264mi_enc_encode_scaled
+    if (!e || !d_src || enc_resampling_refused(e->c)) return -1;
     EncCtx *c = e->c;
     if ((may_enlarge && !filter_ok(filter)) || !cells_ok(c->w, c->h, c->S, src_w, src_h, nsrc, cells, ncells, may_enlarge) ||
         i420_ranges_overlap(c->d_src, c->w, c->h, c->S, d_src, src_w, src_h, nsrc))

@@ -35,7 +35,7 @@
 // frame changes and at the end.
 //
 // A translation unit and a code object of its own, as denoise.hip is: the library's other kernels stay byte for byte
-// what they were. The host runtime (capi_enc.inc) reaches it through the functions picture_host.h declares.
+// what they were. The host runtime (enc_input.inc, capi_enc.inc) reaches it through the functions picture_host.h declares.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>

@@ -29,7 +29,7 @@
 // allocation, no copies.
 //
 // A translation unit and a code object of its own, as quality.hip, scale.hip and compose.hip are: the library's other
-// kernels stay byte for byte what they were. The host runtime (capi_enc.inc) reaches it through the functions
+// kernels stay byte for byte what they were. The host runtime (enc_input.inc, capi_enc.inc) reaches it through the functions
 // picture_host.h declares.
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -1,5 +1,6 @@
 // runtime_enc.inc -- host runtime of the encoder: HBM allocation, per-frame launch sequence,
 // parameter-set generation. Lives in the kernels' translation unit so launches see the kernels.
+// The stages in front of the frame step: their state is EncInput here, their logic enc_input.inc.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -149,6 +150,32 @@ static void wait_limit_from_env() {
 }
 
 // ---------------------------------------------------------------- encoder context
+// The stages an encoder runs on its input area in front of the frame step, in the order they run (enc_input.inc holds
+// the chain, the setters and the release; DESIGN.md §5.16). Each holds its parameters p, whether it is on, its device
+// state -- allocated when the stage is turned on, freed when it is turned off -- and whether that state holds a frame
+// yet. Every stage off: a frame step enqueues what it did before the stages existed
+struct EncInput {
+    struct Deinterlace {  // h264mi_enc_set_deinterlace; deinterlace.hip
+        bool on = false, has = false; h264mi_deinterlace p = {};
+        uint8_t *d_prev = nullptr;  // the S previous unfiltered frames
+    } di;
+    struct Denoise {  // the pre-filter: h264mi_enc_set_denoise; denoise.hip
+        bool on = false, has = false; h264mi_denoise p = {};
+        uint8_t *d_prev = nullptr;  // the S previous filtered frames
+    } dn;
+    struct Scenecut {  // the key-frame policy: h264mi_enc_set_scenecut; scenecut.hip
+        bool on = false, has = false; h264mi_scenecut p = {};
+        uint32_t *d_words = nullptr;  // per stream sixteen words, then per stream eight statistics words: 24 S words
+        uint8_t *d_thumb = nullptr;   // the S thumbnails, only with share > 0; has speaks of them
+    } sc;
+    struct Overlays {  // h264mi_enc_set_overlays; overlay.hip: host copies of the placements, the caller's sprites
+        std::vector<h264mi_overlay> list;  // empty: off
+        const uint8_t *sprites = nullptr;
+        int w = 0, h = 0;  // the sprites' size
+    } ov;
+    bool any() const { return di.on || dn.on || sc.on || !ov.list.empty(); }
+};
+
 struct EncCtx {
     int w, h, mbw, mbh, nmb, cw, ch, S, bitrate;
     hipStream_t stream;
@@ -191,34 +218,10 @@ struct EncCtx {
     int ncu = 256;               // the device's CUs (enc_frame's build choice)
     std::vector<hipEvent_t> ev;
     int ev_used = 0;
-    // the overlay list in force (h264mi_enc_set_overlays; overlay.hip): host copies of the placements, the caller's
-    // sprites. Empty: every frame step enqueues what it did before the list existed
-    std::vector<h264mi_overlay> ov;
-    const uint8_t *ov_sprites = nullptr;
-    int ov_w = 0, ov_h = 0;
     // what h264mi_enc_encode_rgba converts under (h264mi_enc_set_colorspec; colorspace.hip). All 0: the wrapper's
     // conversion by color.inc's kernel, as before the specification existed
     h264mi_colorspec cs = {};
-    // the pre-filter in force (h264mi_enc_set_denoise; denoise.hip): its parameters, the S previous filtered frames
-    // (allocated when it is turned on, freed when it is turned off) and whether they hold a frame yet. Off: every
-    // frame step enqueues what it did before the filter existed
-    bool dn_on = false, dn_has = false;
-    h264mi_denoise dn = {};
-    uint8_t *d_dn = nullptr;
-    // the deinterlacer in force (h264mi_enc_set_deinterlace; deinterlace.hip): its parameters, the S previous unfiltered
-    // frames (allocated when it is turned on, freed when it is turned off) and whether they hold a frame yet. Off: every
-    // frame step enqueues what it did before the filter existed
-    bool di_on = false, di_has = false;
-    h264mi_deinterlace di = {};
-    uint8_t *d_di = nullptr;
-    // the key-frame policy in force (h264mi_enc_set_scenecut; scenecut.hip): its parameters, per stream sixteen words
-    // and eight statistics words (d_sc, 24 S words, allocated when it is turned on, freed when it is turned off), the S
-    // thumbnails (d_sc_thumb, only with share > 0) and whether they hold a frame yet. Off: every frame step enqueues
-    // what it did before the policy existed
-    bool sc_on = false, sc_has = false;
-    h264mi_scenecut sc = {};
-    uint32_t *d_sc = nullptr;
-    uint8_t *d_sc_thumb = nullptr;
+    EncInput in;                 // the stages in front of the frame step (above; their logic: enc_input.inc)
 };
 
 struct EncMbLaunch {  // enc_mb_kernel reads the source frames through this launch-time base
@@ -226,16 +229,15 @@ struct EncMbLaunch {  // enc_mb_kernel reads the source frames through this laun
     size_t src_stride;
 };
 
+static void enc_input_release(EncCtx *c);  // enc_input.inc
+
 static void enc_free(EncCtx *c) {
     if (!c) return;
 
     for (auto e : c->ev) (void)hipEventDestroy(e);
     (void)hipFree(c->d_pool);
     (void)hipFree(c->d_qual);
-    (void)hipFree(c->d_dn);
-    (void)hipFree(c->d_di);
-    (void)hipFree(c->d_sc);
-    (void)hipFree(c->d_sc_thumb);
+    enc_input_release(c);
     (void)hipFree(c->d_prof);
     (void)hipFree(c->d_tl);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);

@@ -365,6 +365,30 @@ def _hip_stream(stream):
     return ctypes.c_void_p(stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream)
 
 
+def _byref(x):
+    """x by reference, NULL for None"""
+    return ctypes.byref(x) if x is not None else None
+
+
+def _ptr(t):
+    """tensor t's device pointer, NULL for None"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class _Record(ctypes.Structure):
+    """base of the parameter and record structures: the repr names every field (it appears in error messages)"""
+
+    def __repr__(self):
+        return type(self).__name__ + '(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
+
+    @classmethod
+    def _of(cls, params):
+        """None, an instance, or an instance from a tuple of integers"""
+        if params is None or isinstance(params, cls):
+            return params
+        return cls(*(int(v) for v in params))
+
+
 class BatchEncoder:
     """S independent encoder streams of one geometry, frames and NAL units resident in HBM."""
 
@@ -396,7 +420,7 @@ class BatchEncoder:
         """what encode_rgba converts under from its next call on: a ColorSpec, or None for the default (BT.601 limited
         range, chroma of the top-left pixel: the bytes and the launch of before). No other input path changes.
         ValueError, with the previous specification still in force, on one colorspec_ok refuses."""
-        if self._L.h264mi_enc_set_colorspec(self._e, ctypes.byref(spec) if spec is not None else None) != 0:
+        if self._L.h264mi_enc_set_colorspec(self._e, _byref(spec)) != 0:
             raise ValueError(f'h264mi_enc_set_colorspec refused {spec!r}')
 
     def colorspec(self):
@@ -462,6 +486,20 @@ class BatchEncoder:
                                                   int(filter), y, cb, cr) != 0:
             raise ValueError(f'h264mi_enc_encode_composed_any refused {len(arr)} cells of {nsrc} sources {src_w}x{src_h} -> {self.w}x{self.h}')
 
+    def _set_stage(self, name, cls, params):
+        """h264mi_enc_set_<name> with what cls._of makes of params; ValueError when the library refuses"""
+        d = cls._of(params)
+        if getattr(self._L, 'h264mi_enc_set_' + name)(self._e, _byref(d)) != 0:
+            raise ValueError(f'h264mi_enc_set_{name} refused {d!r}')
+
+    def _get_stage(self, name, cls):
+        """h264mi_enc_<name>: a cls (a copy) when the stage is on, None when it is off"""
+        out = cls()
+        r = getattr(self._L, 'h264mi_enc_' + name)(self._e, ctypes.byref(out))
+        if r < 0:
+            raise RuntimeError(f'h264mi_enc_{name} failed')
+        return out if r == 1 else None
+
     def set_deinterlace(self, params):
         """the deinterlacer of encode(), encode_rgba() and encode_pix() from the next call on
         (h264mi_enc_set_deinterlace): a Deinterlace, a (parity, spatial, temporal, comb_level) tuple, or None for off. On,
@@ -470,17 +508,11 @@ class BatchEncoder:
         spatially only; encode() then codes a copy of the caller's frames, which stay as they are. While it is on
         encode_scaled, encode_composed, encode_composed_any and encode_oriented are refused. Off drops the state.
         ValueError, with the setting in force unchanged, on parameters deinterlace_ok refuses."""
-        d = _deinterlace_params(params)
-        if self._L.h264mi_enc_set_deinterlace(self._e, ctypes.byref(d) if d is not None else None) != 0:
-            raise ValueError(f'h264mi_enc_set_deinterlace refused {d!r}')
+        self._set_stage('deinterlace', Deinterlace, params)
 
     def deinterlace(self):
         """the deinterlacer in force: a Deinterlace (a copy), or None when it is off (h264mi_enc_deinterlace)"""
-        out = Deinterlace()
-        r = self._L.h264mi_enc_deinterlace(self._e, ctypes.byref(out))
-        if r < 0:
-            raise RuntimeError('h264mi_enc_deinterlace failed')
-        return out if r == 1 else None
+        return self._get_stage('deinterlace', Deinterlace)
 
     def set_denoise(self, params):
         """the pre-filter of every encode*() from its next call on (h264mi_enc_set_denoise): a Denoise, a
@@ -489,17 +521,11 @@ class BatchEncoder:
         the overlay list and the frame step, and codes the first frame after it was turned on unfiltered; encode() then
         codes a copy of the caller's frames, which stay as they are. Off drops the state. ValueError, with the setting
         in force unchanged, on parameters denoise_ok refuses."""
-        d = _denoise_params(params)
-        if self._L.h264mi_enc_set_denoise(self._e, ctypes.byref(d) if d is not None else None) != 0:
-            raise ValueError(f'h264mi_enc_set_denoise refused {d!r}')
+        self._set_stage('denoise', Denoise, params)
 
     def denoise(self):
         """the pre-filter in force: a Denoise (a copy), or None when it is off (h264mi_enc_denoise)"""
-        out = Denoise()
-        r = self._L.h264mi_enc_denoise(self._e, ctypes.byref(out))
-        if r < 0:
-            raise RuntimeError('h264mi_enc_denoise failed')
-        return out if r == 1 else None
+        return self._get_stage('denoise', Denoise)
 
     def set_scenecut(self, params):
         """the key-frame policy of every encode*() from its next call on (h264mi_enc_set_scenecut): a Scenecut, a
@@ -508,17 +534,11 @@ class BatchEncoder:
         behind the denoiser and in front of the overlay list and the frame step, and codes an IDR at a cut, at the
         period and whenever it would anyway; encode() then codes a copy of the caller's frames. Off drops the state.
         ValueError, with the setting in force unchanged, on parameters scenecut_ok refuses."""
-        d = _scenecut_params(params)
-        if self._L.h264mi_enc_set_scenecut(self._e, ctypes.byref(d) if d is not None else None) != 0:
-            raise ValueError(f'h264mi_enc_set_scenecut refused {d!r}')
+        self._set_stage('scenecut', Scenecut, params)
 
     def scenecut(self):
         """the key-frame policy in force: a Scenecut (a copy), or None when it is off (h264mi_enc_scenecut)"""
-        out = Scenecut()
-        r = self._L.h264mi_enc_scenecut(self._e, ctypes.byref(out))
-        if r < 0:
-            raise RuntimeError('h264mi_enc_scenecut failed')
-        return out if r == 1 else None
+        return self._get_stage('scenecut', Scenecut)
 
     def scenecut_state(self, stream):
         """stream's state after the last submitted frame (h264mi_enc_scenecut_state; waits for the encoder's stream): a
@@ -648,7 +668,7 @@ class BatchEncoder:
     def copy_nals(self, dst, slot, sizes=None):
         """async device copy of every stream's NAL into dst[s*slot:(s+1)*slot] (uint8 CUDA tensor);
         byte counts into sizes (int32 CUDA tensor of S) when given"""
-        sp = ctypes.c_void_p(sizes.data_ptr()) if sizes is not None else None
+        sp = _ptr(sizes)
         if self._L.h264mi_enc_copy_nals(self._e, ctypes.c_void_p(dst.data_ptr()), slot, sp) != 0:
             raise RuntimeError('h264mi_enc_copy_nals failed')
 
@@ -793,7 +813,7 @@ class BatchDecoder:
         PixLayout checked against the decoder's width x height; frame_stride is unused, every out pointer is a frame's
         base and must hold pix_span(layout, w, h) bytes), or None: back to the format set last. The last setter
         wins: set_output_format clears a layout. ValueError, with nothing changed, on a layout pix_layout_ok refuses."""
-        if self._L.h264mi_dec_set_output_layout(self._d, ctypes.byref(layout) if layout is not None else None) != 0:
+        if self._L.h264mi_dec_set_output_layout(self._d, _byref(layout)) != 0:
             raise ValueError(f'h264mi_dec_set_output_layout refused {layout!r} for {self.w}x{self.h}')
 
     def output_layout(self):
@@ -807,7 +827,7 @@ class BatchDecoder:
         Nothing changes for 'i420' or layout output; the setting is kept across format changes. BILINEAR clamps to the
         cropped picture: the bytes equal i420_to_rgba(..., spec=spec) on the cropped I420 picture. ValueError, with
         nothing changed, on one colorspec_ok refuses."""
-        if self._L.h264mi_dec_set_output_colorspec(self._d, ctypes.byref(spec) if spec is not None else None) != 0:
+        if self._L.h264mi_dec_set_output_colorspec(self._d, _byref(spec)) != 0:
             raise ValueError(f'h264mi_dec_set_output_colorspec refused {spec!r}')
 
     def output_colorspec(self):
@@ -1014,18 +1034,15 @@ CHROMA_DOWN_TOPLEFT, CHROMA_DOWN_AVERAGE = 0, 1  # H264MI_CHROMA_DOWN_*: RGBA ->
 CHROMA_UP_REPEAT, CHROMA_UP_BILINEAR = 0, 1      # H264MI_CHROMA_UP_*: 4:2:0 -> RGBA by repetition, or centre-sited 9-3-3-1 interpolation
 
 
-class ColorSpec(ctypes.Structure):
+class ColorSpec(_Record):
     """h264mi_colorspec (include/h264mi.h): the matrix, the range and how chroma is reduced and restored at an RGBA
     edge; all 0 is the reference wrapper's conversion. 16 bytes"""
     _fields_ = [(k, ctypes.c_int32) for k in ('matrix', 'range', 'chroma_down', 'chroma_up')]
 
-    def __repr__(self):
-        return 'ColorSpec(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
-
 
 def colorspec_ok(spec):
     """0 when every field of spec is 0 or 1, else -1 (None included); h264mi_colorspec_ok, host only"""
-    return lib().h264mi_colorspec_ok(ctypes.byref(spec) if spec is not None else None)
+    return lib().h264mi_colorspec_ok(_byref(spec))
 
 
 def _convert_cs_dev(fn, dst, src, dst_bytes, src_bytes, w, h, n, spec, stream):
@@ -1065,13 +1082,10 @@ def i420_scale(dst, src, sw, sh, dw, dh, n, stream=None):
         raise ValueError(f'bad arguments: {sw}x{sh} -> {dw}x{dh}, {n} frames')
 
 
-class Cell(ctypes.Structure):
+class Cell(_Record):
     """h264mi_cell (include/h264mi.h): a crop (sx, sy, sw, sh) of source frame src to a rectangle (dx, dy, dw, dh) of
     canvas `canvas`, 40 bytes"""
     _fields_ = [(k, ctypes.c_int32) for k in ('src', 'canvas', 'sx', 'sy', 'sw', 'sh', 'dx', 'dy', 'dw', 'dh')]
-
-    def __repr__(self):
-        return 'Cell(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
 
 
 def _cell_array(cells):
@@ -1195,28 +1209,17 @@ def i420_orient(dst, src, sw, sh, n, orient, stream=None):
         raise ValueError(f'bad arguments: orientation {orient} of {n} frames {sw}x{sh}')
 
 
-class Denoise(ctypes.Structure):
+class Denoise(_Record):
     """h264mi_denoise (include/h264mi.h): strength_y, strength_c 0..224 (the share of 256 of a vanishing difference that
     is removed), reach 1..32 (differences of reach or more are kept), motion 0..1020 (the mean absolute luma difference
     of an 8x8 block, in quarter levels, above which the block is left as it is). 16 bytes"""
     _fields_ = [(k, ctypes.c_int32) for k in ('strength_y', 'strength_c', 'reach', 'motion')]
 
-    def __repr__(self):
-        return 'Denoise(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
-
-
-def _denoise_params(params):
-    """None, a Denoise, or a Denoise from four integers"""
-    if params is None or isinstance(params, Denoise):
-        return params
-    return Denoise(*(int(v) for v in params))
-
 
 def denoise_ok(params):
     """0 when every field of params (a Denoise or four integers) is in its range, else -1 (None included);
     h264mi_denoise_ok, host only"""
-    d = _denoise_params(params)
-    return lib().h264mi_denoise_ok(ctypes.byref(d) if d is not None else None)
+    return lib().h264mi_denoise_ok(_byref(Denoise._of(params)))
 
 
 def i420_denoise(dst, cur, prev, w, h, n, params, dst2=None, stats=None, stream=None):
@@ -1234,49 +1237,36 @@ def i420_denoise(dst, cur, prev, w, h, n, params, dst2=None, stats=None, stream=
     assert all(t.numel() >= need for t in (dst, cur, prev) + ((dst2,) if dst2 is not None else ()))
     if stats is not None:
         assert stats.is_cuda and stats.is_contiguous() and stats.numel() * stats.element_size() >= 16 * max(n, 0)
-    d = _denoise_params(params)
-    if lib().h264mi_i420_denoise_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(dst2.data_ptr()) if dst2 is not None else None,
-                                     ctypes.c_void_p(cur.data_ptr()), ctypes.c_void_p(prev.data_ptr()), w, h, n,
-                                     ctypes.byref(d) if d is not None else None,
-                                     ctypes.c_void_p(stats.data_ptr()) if stats is not None else None, _hip_stream(stream)) != 0:
+    d = Denoise._of(params)
+    if lib().h264mi_i420_denoise_dev(_ptr(dst), _ptr(dst2), _ptr(cur), _ptr(prev), w, h, n, _byref(d), _ptr(stats),
+                                     _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
 
 
-class Scenecut(ctypes.Structure):
+class Scenecut(_Record):
     """h264mi_scenecut (include/h264mi.h): level 0..1020 (the mean absolute thumbnail difference of a 32x32 block, in
     quarter levels, above which the block is changed), share 0..256 (the share of 256 of the blocks that must be
     changed; 0: detection off), min_gap, max_gap 0..65535 (frames between key frames; max_gap 0: no period),
     compensate 0/1 (a uniform brightness step changes no block). 20 bytes"""
     _fields_ = [(k, ctypes.c_int32) for k in ('level', 'share', 'min_gap', 'max_gap', 'compensate')]
 
-    def __repr__(self):
-        return 'Scenecut(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
-
 
 SCENECUT_DEFAULT = (64, 128, 4, 0, 1)  # the header's documented default
 SCENECUT_STATE = ('cut', 'key', 'reason', 'dist', 'keys_by_cut', 'keys_by_period', 'keys_other', 'frames')
 
 
-def _scenecut_params(params):
-    """None, a Scenecut, or a Scenecut from five integers"""
-    if params is None or isinstance(params, Scenecut):
-        return params
-    return Scenecut(*(int(v) for v in params))
-
-
 def scenecut_ok(params):
     """0 when every field of params (a Scenecut or five integers) is in its range, else -1 (None included);
     h264mi_scenecut_ok, host only"""
-    d = _scenecut_params(params)
-    return lib().h264mi_scenecut_ok(ctypes.byref(d) if d is not None else None)
+    return lib().h264mi_scenecut_ok(_byref(Scenecut._of(params)))
 
 
 def scenecut_is_cut(params, stats):
     """1 when a frame's eight statistics words are a cut under params, 0 when not, -1 on bad parameters;
     h264mi_scenecut_is_cut, host only"""
-    d = _scenecut_params(params)
+    d = Scenecut._of(params)
     words = (ctypes.c_uint32 * 8)(*(int(v) for v in stats))
-    return lib().h264mi_scenecut_is_cut(ctypes.byref(d) if d is not None else None, words)
+    return lib().h264mi_scenecut_is_cut(_byref(d), words)
 
 
 def thumb_size(w, h):
@@ -1304,35 +1294,23 @@ def i420_scenecut(cur, w, h, n, params, thumb_out=None, thumb_prev=None, stats=N
             assert t.numel() >= tb
     if stats is not None:
         assert stats.is_cuda and stats.is_contiguous() and stats.numel() * stats.element_size() >= 32 * max(n, 0)
-    d = _scenecut_params(params)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    if lib().h264mi_i420_scenecut_dev(ptr(stats), ptr(thumb_out), ptr(cur), ptr(thumb_prev), w, h, n,
-                                      ctypes.byref(d) if d is not None else None, _hip_stream(stream)) != 0:
+    d = Scenecut._of(params)
+    if lib().h264mi_i420_scenecut_dev(_ptr(stats), _ptr(thumb_out), _ptr(cur), _ptr(thumb_prev), w, h, n, _byref(d),
+                                      _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
 
 
-class Deinterlace(ctypes.Structure):
+class Deinterlace(_Record):
     """h264mi_deinterlace (include/h264mi.h): parity 0 (the even lines are kept) or 1, spatial 0 (linear) or 1
     (edge-directed), temporal 0 or 1 (weave where the previous frame shows no motion), comb_level 0..255 (the
     statistics' threshold). 16 bytes"""
     _fields_ = [(k, ctypes.c_int32) for k in ('parity', 'spatial', 'temporal', 'comb_level')]
 
-    def __repr__(self):
-        return 'Deinterlace(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
-
-
-def _deinterlace_params(params):
-    """None, a Deinterlace, or a Deinterlace from four integers"""
-    if params is None or isinstance(params, Deinterlace):
-        return params
-    return Deinterlace(*(int(v) for v in params))
-
 
 def deinterlace_ok(params):
     """0 when every field of params (a Deinterlace or four integers) is in its range, else -1 (None included);
     h264mi_deinterlace_ok, host only"""
-    d = _deinterlace_params(params)
-    return lib().h264mi_deinterlace_ok(ctypes.byref(d) if d is not None else None)
+    return lib().h264mi_deinterlace_ok(_byref(Deinterlace._of(params)))
 
 
 def i420_deinterlace(dst, cur, w, h, n, params, prev=None, prev_out=None, stats=None, stream=None):
@@ -1350,10 +1328,9 @@ def i420_deinterlace(dst, cur, w, h, n, params, prev=None, prev_out=None, stats=
     assert all(t.numel() >= need for t in given)
     if stats is not None:
         assert stats.is_cuda and stats.is_contiguous() and stats.numel() * stats.element_size() >= 16 * max(n, 0)
-    d = _deinterlace_params(params)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    if lib().h264mi_i420_deinterlace_dev(ptr(dst), ptr(prev_out), ptr(cur), ptr(prev), w, h, n, ctypes.byref(d) if d is not None else None,
-                                         ptr(stats), _hip_stream(stream)) != 0:
+    d = Deinterlace._of(params)
+    if lib().h264mi_i420_deinterlace_dev(_ptr(dst), _ptr(prev_out), _ptr(cur), _ptr(prev), w, h, n, _byref(d),
+                                         _ptr(stats), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
 
 
@@ -1430,13 +1407,10 @@ def i420_to_pix(dst, layout, src, w, h, n, stream=None):
         raise ValueError(f'bad arguments: {layout!r}, {n} frames {w}x{h}')
 
 
-class Overlay(ctypes.Structure):
+class Overlay(_Record):
     """h264mi_overlay (include/h264mi.h): the w x h crop at (sx, sy) of sprite `sprite` blended 1:1 onto canvas
     `canvas` at (dx, dy), its alpha scaled by opacity / 256; reserved is 0; 40 bytes"""
     _fields_ = [(k, ctypes.c_int32) for k in ('sprite', 'canvas', 'sx', 'sy', 'w', 'h', 'dx', 'dy', 'opacity', 'reserved')]
-
-    def __repr__(self):
-        return 'Overlay(' + ', '.join(f'{k}={getattr(self, k)}' for k, _ in self._fields_) + ')'
 
 
 def _overlay_array(overlays):

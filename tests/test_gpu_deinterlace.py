@@ -315,6 +315,62 @@ def test_encoder_runs_the_deinterlacer_in_front_of_denoiser_scenecut_and_overlay
     assert got[3]['nal'] != _run(deint, prepare=tail)[3]['nal'], 'the denoiser changed nothing'
 
 
+def test_encoder_all_four_stages_off_and_on_again(gpu_lib):
+    """all four stages on for frames 0-1, all off in front of frame 2, all on again in front of frame 4: frames 2-3 are
+    the raw frames, coded as an encoder with nothing configured codes them behind the same frames 0-1, and from frame 4
+    every stage starts anew -- the deinterlacer spatial only, the denoiser with a copy, the detector with thumbnails
+    only. The reference encoder is fed the chained models' frames and has only the key-frame policy and the overlay
+    list, switched at the same steps"""
+    import torch
+    import h264mi
+    DN, SC = (128, 64, 12, 24), (64, 128, 2, 4, 1)
+    raw = _interlaced()
+
+    def chained(lo, hi):
+        """steps lo..hi-1 as deintref and then denoiseref's recursion leave them, both started at step lo"""
+        deint = _model(raw[:hi], start=lo)[lo:]
+        per = [denoiseref.denoise_sequence([st[s] for st in deint], W, H, DN)[0] for s in range(S)]
+        return [np.stack([per[s][t] for s in range(S)]) for t in range(hi - lo)]
+
+    first, again, never_off = chained(0, 2), chained(4, NF), chained(0, NF)
+    assert not np.array_equal(never_off[2], raw[2]) and not np.array_equal(never_off[3], raw[3]), 'off shows nothing'
+    assert not np.array_equal(again[0], never_off[4]) and not np.array_equal(again[1], never_off[5]), 'the restart shows nothing'
+    sprite = torch.from_numpy(np.random.default_rng(93).integers(0, 256, h264mi.i420a_bytes(16, 16), dtype=np.uint8)).cuda()
+    ov = [h264mi.Overlay(0, s, 0, 0, 16, 16, 8, 8, 256, 0) for s in range(S)]
+
+    def tail(enc):
+        enc.set_scenecut(SC)
+        enc.set_overlays(sprite, 16, 16, 1, ov)
+
+    def all_on(enc):
+        tail(enc)
+        enc.set_denoise(DN)
+        _on(enc)
+
+    def tail_off(enc):
+        enc.set_scenecut(None)
+        enc.clear_overlays()
+        assert enc.scenecut() is None and enc.overlays() == 0
+
+    def all_off(enc):
+        enc.set_deinterlace(None)
+        enc.set_denoise(None)
+        tail_off(enc)
+        assert enc.deinterlace() is None and enc.denoise() is None
+
+    def switched(on, off):
+        def before(enc, t):
+            if t in (0, 4):
+                on(enc)
+            if t == 2:
+                off(enc)
+        return before
+
+    got = _run(raw, before=switched(all_on, all_off))
+    _same(got, _run(first + raw[2:4] + again, before=switched(tail, tail_off)))
+    assert got[2]['nal'] != _run(never_off[:3], prepare=tail)[2]['nal'], 'frame 2 is coded as if nothing had been turned off'
+
+
 def test_encoder_off_and_on_again_restarts_spatial_only(gpu_lib):
     """on for frames 0-1, off for 2, on again for 3-5: frame 2 raw, frame 3 spatial only, frame 4 against raw 3"""
     raw = _interlaced()
