@@ -617,6 +617,64 @@ int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orie
 #define H264MI_PIX_NV21 2   /* as NV12 with Cr first */
 #define H264MI_PIX_YUY2 3   /* one plane, h rows of 2w bytes: Y0 Cb Y1 Cr */
 #define H264MI_PIX_UYVY 4   /* one plane: Cb Y0 Cr Y1 */
+/* Values 5..15 are unassigned and refused everywhere; the formats of the next table are 16..24.
+   Deeper and wider layouts: 4:2:2 and 4:4:4 planar, 8-bit grey, and 10 bits a sample as a hardware
+   decoder of HDR or broadcast material (P010, P210), a software pipeline (I010, I210) or an SDI capture card (V210)
+   leaves them. w and h even; each plane as row bytes x rows:
+     id  pix   planes                                                      samples
+     16  I422  0: Y w x h      1: Cb w/2 x h      2: Cr w/2 x h             8 bit
+     17  I444  0: Y w x h      1: Cb w x h        2: Cr w x h               8 bit
+     18  NV16  0: Y w x h      1: w x h, byte 2i = Cb[i], 2i+1 = Cr[i]      8 bit
+     19  Y800  0: Y w x h                                                   8 bit grey
+     20  P010  0: Y 2w x h     1: 2w x h/2, words Cb Cr interleaved         16-bit LE words, the value in bits 15..6
+     21  I010  0: Y 2w x h     1: Cb w x h/2      2: Cr w x h/2             16-bit LE words, the value in bits 9..0
+     22  P210  0: Y 2w x h     1: 2w x h, words Cb Cr interleaved           as P010, 4:2:2
+     23  I210  0: Y 2w x h     1: Cb w x h        2: Cr w x h               as I010, 4:2:2
+     24  V210  0: 16 * ceil(w/6) x h                                        packed 10-bit 4:2:2
+   V210: a group of six pixels is four 32-bit LE words of three 10-bit fields at bits 9..0, 19..10 and 29..20:
+     word 0: Cb0 Y0 Cr0    word 1: Y1 Cb1 Y2    word 2: Cr1 Y3 Cb2    word 3: Y4 Cr2 Y5
+   Cbk and Crk belong to luma samples 2k and 2k+1 of the group. On writing, bits 31..30 are zero and so are the fields
+   of samples at or beyond w in the last group; all 16 * ceil(w/6) row bytes are named bytes and are written. On
+   reading, those fields and bits are ignored.
+   Each format has a unit u: 1 byte for ids 0..4 and 16..19, 2 for 20..23, 4 for 24. h264mi_pix_layout_ok refuses a used
+   pitch, an offset or a frame_stride that is no multiple of u, and the device calls a layout-side base pointer that is
+   none; every other rule below holds as written. h264mi_pix_layout_tight gives pitch = row bytes, planes back to back
+   and frame_stride = the span for these too, except V210: its tight pitch is 128 * ceil(w/48), the format's customary
+   row alignment, and its frame_stride h * pitch.
+   To tight I420, exact integers:
+     1. each sample at its source depth: 8-bit formats as is; P010, P210 word >> 6; I010, I210 word & 1023; V210 the field
+     2. chroma reduced at source depth:  4:2:2  (C[2y][x] + C[2y+1][x] + 1) >> 1
+                                         4:4:4  (C[2y][2x] + C[2y][2x+1] + C[2y+1][2x] + C[2y+1][2x+1] + 2) >> 2
+                                         4:2:0  moved        Y800  Cb = Cr = 128
+     3. 10-bit values v to 8 bits by the depth rule of h264mi_pixopt, x and y being the position of the output sample in
+        its own output plane:
+          H264MI_DEPTH_ROUND   min(255, (v + 2) >> 2)                           (0: the default, and what NULL means)
+          H264MI_DEPTH_DITHER  min(255, (v + D[y & 1][x & 1]) >> 2), D = {{0, 2}, {3, 1}}
+          H264MI_DEPTH_TRUNC   v >> 2
+        The option is ignored for the 8-bit formats.
+   From tight I420: luma is moved; chroma is repeated, C[y][x] = C420[y >> 1][x] for 4:2:2 and C420[y >> 1][x >> 1] for
+   4:4:4, and dropped for Y800; 8 bits go to 10 as v << 2, exact for video levels (16 -> 64, 235 -> 940); the MSB
+   formats store v10 << 6 with the low six bits 0, the LSB formats v10 with the high six bits 0.
+   So I420 -> any format -> I420 is the identity under all three depth rules; for Y800 on luma, with chroma 128. No
+   colour matrix, range change or tone mapping is involved. Not provided: NV24, NV42, Y210, Y410, AYUV, 12- and 16-bit
+   depths, tiled or compressed surfaces, chroma siting filters other than the box rules above, error-diffusion dither. */
+#define H264MI_PIX_I422 16
+#define H264MI_PIX_I444 17
+#define H264MI_PIX_NV16 18
+#define H264MI_PIX_Y800 19
+#define H264MI_PIX_P010 20
+#define H264MI_PIX_I010 21
+#define H264MI_PIX_P210 22
+#define H264MI_PIX_I210 23
+#define H264MI_PIX_V210 24
+#define H264MI_DEPTH_ROUND 0
+#define H264MI_DEPTH_DITHER 1
+#define H264MI_DEPTH_TRUNC 2
+typedef struct h264mi_pixopt { int32_t depth; int32_t reserved[3]; } h264mi_pixopt; /* 16 bytes; reserved must be 0 */
+/* host only: 0 when depth is 0..2 and every reserved field is 0, else -1 (a null pointer included) */
+int h264mi_pixopt_ok(const h264mi_pixopt *opt);
+/* host only: the unit of a format, 1, 2 or 4 (1 for ids 0..4); -1 for an unknown id */
+int h264mi_pix_unit(int pix);
 typedef struct h264mi_pix_layout {
     int32_t pix;            /* H264MI_PIX_* */
     int32_t pitch[3];       /* bytes between rows of plane p; entries of unused planes are 0 */
@@ -640,18 +698,29 @@ int h264mi_pix_layout_ok(const h264mi_pix_layout *layout, int w, int h);
    frames at d_i420 to n frames in *dst at d_dst (any alignment on both sides: 16-byte accesses where a plane's rows
    allow them, bytes otherwise, the same result). The same bytes from run to run, equal to a restatement of the table
    above on any host. Return 0, or -1 on a bad argument, which is checked before the device is touched: a null pointer,
-   n <= 0, a layout that h264mi_pix_layout_ok refuses for w x h, or source and destination byte ranges that overlap
-   (n * frame_stride bytes on the layout's side, n tight frames on the other). */
+   n <= 0, a layout that h264mi_pix_layout_ok refuses for w x h, a layout-side pointer that is no multiple of the
+   format's unit, or source and destination byte ranges that overlap (n * frame_stride bytes on the layout's side, n
+   tight frames on the other). */
 int h264mi_pix_to_i420_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, int w, int h, int n, void *hip_stream);
 int h264mi_i420_to_pix_dev(void *d_dst, const h264mi_pix_layout *dst, const void *d_i420, int w, int h, int n, void *hip_stream);
+/* h264mi_pix_to_i420_dev under a depth rule: opt NULL means all zeros, and h264mi_pix_to_i420_dev is this call with
+   NULL. -1 before the device is touched on an opt that h264mi_pixopt_ok refuses, as on every other bad argument. */
+int h264mi_pix_to_i420_opt_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, const h264mi_pixopt *opt, int w, int h, int n,
+                               void *hip_stream);
 /* async, as h264mi_enc_encode_oriented, from nstreams frames of the encoder's width x height in *layout at d_frames
    (device; frame s at d_frames + s * frame_stride): one batched launch (h264mi_pix_to_i420_dev) into the encoder's
    input area on its stream; then an overlay list in force is blended, then the same frame step -- rate control,
    slices, exact GOM, inject_error and the quality records as in h264mi_enc_encode. With the tight I420 layout the NAL
    bytes are those of h264mi_enc_encode on the same frames. Returns -1 and enqueues nothing on a null pointer, a layout
-   that h264mi_pix_layout_ok refuses for the encoder's size (an encoder of odd width or height included), or frames
-   whose nstreams * frame_stride bytes overlap the encoder's input area. */
+   that h264mi_pix_layout_ok refuses for the encoder's size (an encoder of odd width or height included), frames at
+   an address that is no multiple of the format's unit, or frames whose nstreams * frame_stride bytes overlap the
+   encoder's input area. */
 int h264mi_enc_encode_pix(h264mi_encoder *e, const void *d_frames, const h264mi_pix_layout *layout);
+/* the depth rule h264mi_enc_encode_pix converts under from its next call on (it matters for the 10-bit formats only).
+   Returns 0, or -1 -- the previous setting stays in force -- on a null encoder or an opt h264mi_pixopt_ok refuses.
+   h264mi_enc_pixopt copies the one in force to *out (0, or -1 on a null pointer). */
+int h264mi_enc_set_pixopt(h264mi_encoder *e, const h264mi_pixopt *opt);               /* NULL: the default */
+int h264mi_enc_pixopt(h264mi_encoder *e, h264mi_pixopt *out);
 /* what h264mi_dec_decode_frames_out writes to d_out, beyond the two formats: with a layout set, frame f's cropped
    picture goes to d_out[f * nstreams + s] in that layout (frame_stride is checked but unused: every d_out entry is a
    frame's base), converted straight from the deblocked picture; d_got, "left untouched when no picture" and "each
@@ -661,7 +730,8 @@ int h264mi_enc_encode_pix(h264mi_encoder *e, const void *d_frames, const h264mi_
    format, h264mi_dec_set_output_format (which accepts H264MI_FMT_I420 and H264MI_FMT_RGBA only, as before) clears
    the layout, and NULL clears it too, back to the format set last. h264mi_dec_output_format reports
    H264MI_FMT_LAYOUT while a layout is in effect. h264mi_dec_output_layout: 1 and the layout copied to *out when one
-   is set, 0 when none is, -1 on a null pointer. */
+   is set, 0 when none is, -1 on a null pointer. The formats 16..24 are written by the rules "from tight I420"; a d_out
+   entry that is no multiple of the format's unit is reported in d_got but not written. */
 #define H264MI_FMT_LAYOUT 2   /* what h264mi_dec_output_format reports while a layout is in effect */
 int h264mi_dec_set_output_layout(h264mi_decoder *d, const h264mi_pix_layout *layout);  /* NULL: back to the format */
 int h264mi_dec_output_layout(h264mi_decoder *d, h264mi_pix_layout *out);              /* 1 set (copied to out), 0 not set, -1 bad d */

@@ -10,6 +10,7 @@ SRC_OVERLAY = os.path.join(HERE, 'csrc', 'overlay.hip')  # likewise
 SRC_UPSCALE = os.path.join(HERE, 'csrc', 'upscale.hip')  # likewise
 SRC_ORIENT = os.path.join(HERE, 'csrc', 'orient.hip')  # likewise
 SRC_PIXFMT = os.path.join(HERE, 'csrc', 'pixfmt.hip')  # likewise
+SRC_PIXDEEP = os.path.join(HERE, 'csrc', 'pixdeep.hip')  # likewise
 SRC_COLORSPACE = os.path.join(HERE, 'csrc', 'colorspace.hip')  # likewise
 SRC_DENOISE = os.path.join(HERE, 'csrc', 'denoise.hip')  # likewise
 SRC_SCENECUT = os.path.join(HERE, 'csrc', 'scenecut.hip')  # likewise
@@ -24,7 +25,7 @@ def build(force=False, verbose=False):
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wno-unused-result',
-           '-Wno-pass-failed', '-o', OUT + '.tmp', SRC, SRC_QUALITY, SRC_SCALE, SRC_COMPOSE, SRC_OVERLAY, SRC_UPSCALE, SRC_ORIENT, SRC_PIXFMT,
+           '-Wno-pass-failed', '-o', OUT + '.tmp', SRC, SRC_QUALITY, SRC_SCALE, SRC_COMPOSE, SRC_OVERLAY, SRC_UPSCALE, SRC_ORIENT, SRC_PIXFMT, SRC_PIXDEEP,
            SRC_COLORSPACE, SRC_DENOISE, SRC_SCENECUT, SRC_DEINTERLACE]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

@@ -344,12 +344,24 @@ int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orie
 int h264mi_pix_layout_tight(h264mi_pix_layout *out, int pix, int w, int h) { return pix_layout_tight(out, pix, w, h); }
 int64_t h264mi_pix_span(const h264mi_pix_layout *layout, int w, int h) { return pix_span(layout, w, h); }
 int h264mi_pix_layout_ok(const h264mi_pix_layout *layout, int w, int h) { return pix_layout_ok(layout, w, h) ? 0 : -1; }
-int h264mi_pix_to_i420_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, int w, int h, int n, void *hip_stream) {
-    if (!d_i420 || !d_src || !pix_args_ok(src, w, h, n) || pix_ranges_overlap(d_src, *src, d_i420, w, h, n)) return -1;
+int h264mi_pix_unit(int pix) { return pix_unit(pix); }
+int h264mi_pixopt_ok(const h264mi_pixopt *opt) { return pixopt_ok(opt) ? 0 : -1; }
+// the formats 16..24 go to pixdeep.hip (DESIGN.md §5.17), under the depth rule of opt; the others never look at it
+int h264mi_pix_to_i420_opt_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, const h264mi_pixopt *opt, int w, int h, int n,
+                               void *hip_stream) {
+    if (!d_i420 || !d_src || (opt && !pixopt_ok(opt)) || !pix_args_ok(src, w, h, n) || !pix_base_ok(d_src, *src) ||
+        pix_ranges_overlap(d_src, *src, d_i420, w, h, n))
+        return -1;
+    if (pix_is_deep(src->pix))
+        return launch_pixdeep_to_i420((uint8_t *)d_i420, (const uint8_t *)d_src, *src, opt ? opt->depth : 0, w, h, n, (hipStream_t)hip_stream);
     return launch_pix_to_i420((uint8_t *)d_i420, (const uint8_t *)d_src, *src, w, h, n, (hipStream_t)hip_stream);
 }
+int h264mi_pix_to_i420_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, int w, int h, int n, void *hip_stream) {
+    return h264mi_pix_to_i420_opt_dev(d_i420, d_src, src, nullptr, w, h, n, hip_stream);
+}
 int h264mi_i420_to_pix_dev(void *d_dst, const h264mi_pix_layout *dst, const void *d_i420, int w, int h, int n, void *hip_stream) {
-    if (!d_dst || !d_i420 || !pix_args_ok(dst, w, h, n) || pix_ranges_overlap(d_dst, *dst, d_i420, w, h, n)) return -1;
+    if (!d_dst || !d_i420 || !pix_args_ok(dst, w, h, n) || !pix_base_ok(d_dst, *dst) || pix_ranges_overlap(d_dst, *dst, d_i420, w, h, n)) return -1;
+    if (pix_is_deep(dst->pix)) return launch_i420_to_pixdeep((uint8_t *)d_dst, *dst, (const uint8_t *)d_i420, w, h, n, (hipStream_t)hip_stream);
     return launch_i420_to_pix((uint8_t *)d_dst, *dst, (const uint8_t *)d_i420, w, h, n, (hipStream_t)hip_stream);
 }
 // nstreams frames of the encoder's size in *layout: one batched launch into the encoder's own input area on its stream,
@@ -357,9 +369,25 @@ int h264mi_i420_to_pix_dev(void *d_dst, const h264mi_pix_layout *dst, const void
 int h264mi_enc_encode_pix(h264mi_encoder *e, const void *d_frames, const h264mi_pix_layout *layout) {
     if (!e || !d_frames) return -1;
     EncCtx *c = e->c;
-    if (!pix_args_ok(layout, c->w, c->h, c->S) || pix_ranges_overlap(d_frames, *layout, c->d_src, c->w, c->h, c->S)) return -1;
-    if (launch_pix_to_i420(c->d_src, (const uint8_t *)d_frames, *layout, c->w, c->h, c->S, c->stream) != 0) return -1;
+    if (!pix_args_ok(layout, c->w, c->h, c->S) || !pix_base_ok(d_frames, *layout) ||
+        pix_ranges_overlap(d_frames, *layout, c->d_src, c->w, c->h, c->S))
+        return -1;
+    const int r = pix_is_deep(layout->pix)
+                      ? launch_pixdeep_to_i420(c->d_src, (const uint8_t *)d_frames, *layout, c->pixopt.depth, c->w, c->h, c->S, c->stream)
+                      : launch_pix_to_i420(c->d_src, (const uint8_t *)d_frames, *layout, c->w, c->h, c->S, c->stream);
+    if (r != 0) return -1;
     return enc_code_input(c);
+}
+// the depth rule the next h264mi_enc_encode_pix converts under; a refused one leaves the previous in force
+int h264mi_enc_set_pixopt(h264mi_encoder *e, const h264mi_pixopt *opt) {
+    if (!e || (opt && !pixopt_ok(opt))) return -1;
+    e->c->pixopt = opt ? *opt : h264mi_pixopt{};
+    return 0;
+}
+int h264mi_enc_pixopt(h264mi_encoder *e, h264mi_pixopt *out) {
+    if (!e || !out) return -1;
+    *out = e->c->pixopt;
+    return 0;
 }
 // Several pictures into one (DESIGN.md §5.4; compose.hip): every cell's crop of a source frame area-averaged into its
 // rectangle of a canvas, 64 cells to a launch

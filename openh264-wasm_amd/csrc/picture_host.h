@@ -1,5 +1,5 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, pixdeep.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
@@ -60,29 +60,48 @@ static inline unsigned launch_blocks(long long waves) { return (unsigned)std::mi
 
 // ---- pixel formats and pitched layouts (include/h264mi.h)
 constexpr int PIX_MAX_PITCH = 65536;
-// planes of a format, 0 for an unknown one
+// planes of a format, 0 for an unknown one (ids 5..15 are unassigned)
 static inline int pix_planes(int pix) {
     switch (pix) {
-    case H264MI_PIX_I420: return 3;
-    case H264MI_PIX_NV12: case H264MI_PIX_NV21: return 2;
-    case H264MI_PIX_YUY2: case H264MI_PIX_UYVY: return 1;
+    case H264MI_PIX_I420: case H264MI_PIX_I422: case H264MI_PIX_I444: case H264MI_PIX_I010: case H264MI_PIX_I210: return 3;
+    case H264MI_PIX_NV12: case H264MI_PIX_NV21: case H264MI_PIX_NV16: case H264MI_PIX_P010: case H264MI_PIX_P210: return 2;
+    case H264MI_PIX_YUY2: case H264MI_PIX_UYVY: case H264MI_PIX_Y800: case H264MI_PIX_V210: return 1;
     default: return 0;
     }
 }
+// the unit of a format: every used pitch and offset, frame_stride and the layout side's base are multiples of it. -1 for
+// an unknown format
+static inline int pix_unit(int pix) {
+    if (pix_planes(pix) == 0) return -1;
+    return pix == H264MI_PIX_V210 ? 4 : pix >= H264MI_PIX_P010 ? 2 : 1;
+}
+// the formats of pixdeep.hip (ids 16..24); the others are pixfmt.hip's
+static inline bool pix_is_deep(int pix) { return pix >= H264MI_PIX_I422; }
 // row bytes and rows of plane p < pix_planes(pix) of a w x h frame
 static inline void pix_plane_size(int pix, int p, int w, int h, int *row_bytes, int *rows) {
-    if (pix == H264MI_PIX_YUY2 || pix == H264MI_PIX_UYVY) { *row_bytes = 2 * w; *rows = h; }
-    else if (p == 0) { *row_bytes = w; *rows = h; }
-    else if (pix == H264MI_PIX_I420) { *row_bytes = w / 2; *rows = h / 2; }
-    else { *row_bytes = w; *rows = h / 2; }
+    *rows = h;
+    switch (pix) {
+    case H264MI_PIX_YUY2: case H264MI_PIX_UYVY: *row_bytes = 2 * w; return;
+    case H264MI_PIX_V210: *row_bytes = 16 * ((w + 5) / 6); return;
+    case H264MI_PIX_I444: case H264MI_PIX_Y800: case H264MI_PIX_NV16: *row_bytes = w; return;
+    case H264MI_PIX_I422: *row_bytes = p == 0 ? w : w / 2; return;
+    case H264MI_PIX_P210: *row_bytes = 2 * w; return;
+    case H264MI_PIX_I210: *row_bytes = p == 0 ? 2 * w : w; return;
+    case H264MI_PIX_P010: *row_bytes = 2 * w; break;
+    case H264MI_PIX_I010: *row_bytes = p == 0 ? 2 * w : w; break;
+    case H264MI_PIX_I420: *row_bytes = p == 0 ? w : w / 2; break;
+    default: *row_bytes = w; break;  // NV12, NV21
+    }
+    if (p > 0) *rows = h / 2;  // the 4:2:0 formats
 }
-// the span of a layout for w x h frames -- every rule of h264mi_pix_layout_ok but the frame_stride one -- or -1. 64-bit
-// arithmetic that cannot overflow: a plane's extent is at most 8191 * 65536 + 16384 < 2^30, and an offset that would
+// the span of a layout for w x h frames -- every rule of h264mi_pix_layout_ok but the two frame_stride ones -- or -1. 64-bit
+// arithmetic that cannot overflow: a plane's extent is at most 8191 * 65536 + 21856 < 2^30, and an offset that would
 // carry its end past INT64_MAX is refused before the sum is formed
 static inline int64_t pix_span(const h264mi_pix_layout *L, int w, int h) {
     if (!L || !canvas_ok(w, h)) return -1;
     const int np = pix_planes(L->pix);
     if (np == 0) return -1;
+    const int um = pix_unit(L->pix) - 1;
     int64_t end[3] = {0, 0, 0}, span = 0;
     for (int p = 0; p < 3; p++) {
         if (p >= np) {
@@ -92,6 +111,7 @@ static inline int64_t pix_span(const h264mi_pix_layout *L, int w, int h) {
         int rb, rows;
         pix_plane_size(L->pix, p, w, h, &rb, &rows);
         if (L->pitch[p] < rb || L->pitch[p] > PIX_MAX_PITCH || L->offset[p] < 0) return -1;
+        if ((L->pitch[p] & um) || (L->offset[p] & um)) return -1;
         const int64_t extent = (int64_t)(rows - 1) * L->pitch[p] + rb;
         if (L->offset[p] > INT64_MAX - extent) return -1;
         end[p] = L->offset[p] + extent;
@@ -104,7 +124,7 @@ static inline int64_t pix_span(const h264mi_pix_layout *L, int w, int h) {
 }
 static inline bool pix_layout_ok(const h264mi_pix_layout *L, int w, int h) {
     const int64_t span = pix_span(L, w, h);
-    return span >= 0 && L->frame_stride >= span;
+    return span >= 0 && L->frame_stride >= span && !(L->frame_stride & (pix_unit(L->pix) - 1));
 }
 static inline int pix_layout_tight(h264mi_pix_layout *out, int pix, int w, int h) {
     const int np = pix_planes(pix);
@@ -115,6 +135,7 @@ static inline int pix_layout_tight(h264mi_pix_layout *out, int pix, int w, int h
     for (int p = 0; p < np; p++) {
         int rb, rows;
         pix_plane_size(pix, p, w, h, &rb, &rows);
+        if (pix == H264MI_PIX_V210) rb = 128 * ((w + 47) / 48);  // the format's customary row alignment
         L.pitch[p] = rb;
         L.offset[p] = at;
         at += (int64_t)rb * rows;
@@ -133,6 +154,11 @@ static inline bool pix_ranges_overlap(const void *a, const h264mi_pix_layout &L,
 }
 // arguments of a conversion call, everything but the pointers' values
 static inline bool pix_args_ok(const h264mi_pix_layout *L, int w, int h, int n) { return n > 0 && pix_layout_ok(L, w, h); }
+// the layout side's base pointer of a good layout: a multiple of the format's unit
+static inline bool pix_base_ok(const void *base, const h264mi_pix_layout &L) { return !((uintptr_t)base & (uintptr_t)(pix_unit(L.pix) - 1)); }
+static inline bool pixopt_ok(const h264mi_pixopt *o) {
+    return o && (uint32_t)o->depth <= 2 && !(o->reserved[0] | o->reserved[1] | o->reserved[2]);
+}
 
 // ---- colour specifications (include/h264mi.h)
 // one row of the header's table, as the kernels of colorspace.hip take it in their arguments
@@ -377,6 +403,10 @@ void deinterlace_frame_host(uint8_t *out, const uint8_t *cur, const uint8_t *pre
 // pixfmt.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);
+int launch_pixdeep_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int depth, int w, int h, int n, hipStream_t s);
+int launch_i420_to_pixdeep(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);
+int launch_dec_output_pixdeep(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in, const h264mi_pix_layout &L,
+                              hipStream_t s);
 int launch_dec_output_pix(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in, const h264mi_pix_layout &L,
                           hipStream_t s);
 // colorspace.hip: a good specification, even sides within PIC_MAX_SIDE; alpha: I420A sprites out (A = the fourth byte)

@@ -221,6 +221,7 @@ struct EncCtx {
     // what h264mi_enc_encode_rgba converts under (h264mi_enc_set_colorspec; colorspace.hip). All 0: the wrapper's
     // conversion by color.inc's kernel, as before the specification existed
     h264mi_colorspec cs = {};
+    h264mi_pixopt pixopt = {};   // the depth rule h264mi_enc_encode_pix converts 10-bit layouts under (h264mi_enc_set_pixopt)
     EncInput in;                 // the stages in front of the frame step (above; their logic: enc_input.inc)
 };
 

@@ -162,6 +162,11 @@ def lib():
             'h264mi_pix_to_i420_dev': (i, [vp, vp, vp, i, i, i, vp]),
             'h264mi_i420_to_pix_dev': (i, [vp, vp, vp, i, i, i, vp]),
             'h264mi_enc_encode_pix': (i, [vp, vp, vp]),
+            'h264mi_pix_unit': (i, [i]),
+            'h264mi_pixopt_ok': (i, [vp]),
+            'h264mi_pix_to_i420_opt_dev': (i, [vp, vp, vp, vp, i, i, i, vp]),
+            'h264mi_enc_set_pixopt': (i, [vp, vp]),
+            'h264mi_enc_pixopt': (i, [vp, vp]),
             'h264mi_dec_set_output_layout': (i, [vp, vp]),
             'h264mi_dec_output_layout': (i, [vp, vp]),
             'h264mi_colorspec_ok': (i, [vp]),
@@ -459,6 +464,19 @@ class BatchEncoder:
         assert pix_layout_ok(layout, self.w, self.h) != 0 or frames.numel() >= (self.S - 1) * layout.frame_stride + pix_span(layout, self.w, self.h)
         if self._L.h264mi_enc_encode_pix(self._e, ctypes.c_void_p(frames.data_ptr()), ctypes.byref(layout)) != 0:
             raise ValueError(f'h264mi_enc_encode_pix refused {layout!r} for {self.w}x{self.h}')
+
+    def set_pixopt(self, opt):
+        """the depth rule encode_pix converts the 10-bit layouts under from its next call on: a PixOpt, or None for the
+        default (DEPTH_ROUND). ValueError, with the previous setting still in force, on one pixopt_ok refuses."""
+        if self._L.h264mi_enc_set_pixopt(self._e, _byref(opt)) != 0:
+            raise ValueError(f'h264mi_enc_set_pixopt refused {opt!r}')
+
+    def pixopt(self):
+        """the depth rule in force (a copy)"""
+        out = PixOpt()
+        if self._L.h264mi_enc_pixopt(self._e, ctypes.byref(out)) != 0:
+            raise RuntimeError('h264mi_enc_pixopt failed')
+        return out
 
     def encode_composed(self, src, src_w, src_h, nsrc, cells, bg=(16, 128, 128)):
         """src: uint8 CUDA tensor holding nsrc tight I420 frames of src_w x src_h back to back, any alignment; cells: a
@@ -1339,6 +1357,11 @@ PIX_NV12 = 1  # plane 0 Y; plane 1: h/2 rows of w bytes, byte 2i = Cb[i], 2i+1 =
 PIX_NV21 = 2  # as NV12 with Cr first
 PIX_YUY2 = 3  # one plane, h rows of 2w bytes: Y0 Cb Y1 Cr
 PIX_UYVY = 4  # one plane: Cb Y0 Cr Y1
+# 5..15 are unassigned and refused; the deeper and wider layouts (include/h264mi.h has their table):
+PIX_I422, PIX_I444, PIX_NV16, PIX_Y800 = 16, 17, 18, 19  # 8 bit: planar 4:2:2 and 4:4:4, semi-planar 4:2:2, grey
+PIX_P010, PIX_I010, PIX_P210, PIX_I210 = 20, 21, 22, 23  # 10 bit in 16-bit words: P* in bits 15..6, I* in bits 9..0
+PIX_V210 = 24  # packed 10-bit 4:2:2, six pixels in four 32-bit words
+DEPTH_ROUND, DEPTH_DITHER, DEPTH_TRUNC = 0, 1, 2  # H264MI_DEPTH_*: how 10 bits become 8
 FMT_LAYOUT = 2  # H264MI_FMT_LAYOUT: what h264mi_dec_output_format reports while a layout is in effect
 
 
@@ -1357,6 +1380,32 @@ class PixLayout(ctypes.Structure):
 
     def __repr__(self):
         return f'PixLayout(pix={self.pix}, pitch={list(self.pitch)}, offset={list(self.offset)}, frame_stride={self.frame_stride})'
+
+
+class PixOpt(_Record):
+    """h264mi_pixopt (include/h264mi.h): the depth rule (DEPTH_*) that 10-bit samples become 8-bit ones under; the
+    reserved fields must be 0. 16 bytes"""
+    _fields_ = [('depth', ctypes.c_int32), ('reserved', ctypes.c_int32 * 3)]
+
+    def __init__(self, depth=0, reserved=(0, 0, 0)):
+        super().__init__()
+        self.depth = depth
+        for k, v in enumerate(reserved):
+            self.reserved[k] = v
+
+    def __repr__(self):
+        return f'PixOpt(depth={self.depth}, reserved={list(self.reserved)})'
+
+
+def pixopt_ok(opt):
+    """0 when depth is 0..2 and the reserved fields are 0, else -1 (None included); h264mi_pixopt_ok, host only"""
+    return lib().h264mi_pixopt_ok(_byref(opt))
+
+
+def pix_unit(pix):
+    """the unit of format pix, 1, 2 or 4 bytes: what pitches, offsets, frame_stride and the base address are multiples
+    of; -1 for an unknown format (h264mi_pix_unit; host only)"""
+    return lib().h264mi_pix_unit(int(pix))
 
 
 def pix_layout_tight(pix, w, h):
@@ -1383,17 +1432,18 @@ def _pix_fits(t, layout, w, h, n):
     return n <= 0 or pix_layout_ok(layout, w, h) != 0 or t.numel() >= (n - 1) * layout.frame_stride + pix_span(layout, w, h)
 
 
-def pix_to_i420(dst, src, layout, w, h, n, stream=None):
+def pix_to_i420(dst, src, layout, w, h, n, stream=None, opt=None):
     """n w x h frames in `layout` (a PixLayout; uint8 CUDA tensor src, frame f at f * layout.frame_stride, any
-    alignment) to n tight I420 frames (dst), one launch, async on stream (default: the current one);
-    h264mi_pix_to_i420_dev. I420, NV12 and NV21 samples are moved; YUY2 and UYVY chroma is (rows 2y + 2y+1 + 1) >> 1:
-    the bytes equal tests/pixref.py's. ValueError on a bad argument (a layout pix_layout_ok refuses, n <= 0,
-    overlapping buffers)."""
+    alignment that is a multiple of pix_unit) to n tight I420 frames (dst), one launch, async on stream (default: the
+    current one); h264mi_pix_to_i420_opt_dev. I420, NV12 and NV21 samples are moved; 4:2:2 chroma is
+    (rows 2y + 2y+1 + 1) >> 1, 4:4:4 chroma the rounded mean of each 2x2; 10-bit samples become 8-bit ones under opt (a
+    PixOpt; None: DEPTH_ROUND): the bytes equal tests/pixref.py's and tests/pixdeepref.py's. ValueError on a bad
+    argument (a layout pix_layout_ok refuses, an opt pixopt_ok refuses, n <= 0, overlapping buffers)."""
     _assert_dev_u8(dst, src)
     assert n <= 0 or min(w, h) <= 0 or (dst.numel() >= n * _i420_bytes(w, h) and _pix_fits(src, layout, w, h, n))
-    if lib().h264mi_pix_to_i420_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), ctypes.byref(layout), w, h, n,
-                                    _hip_stream(stream)) != 0:
-        raise ValueError(f'bad arguments: {layout!r}, {n} frames {w}x{h}')
+    if lib().h264mi_pix_to_i420_opt_dev(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()), ctypes.byref(layout), _byref(opt),
+                                        w, h, n, _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {layout!r}, {opt!r}, {n} frames {w}x{h}')
 
 
 def i420_to_pix(dst, layout, src, w, h, n, stream=None):

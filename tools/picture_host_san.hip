@@ -24,6 +24,9 @@
 //   * the pixel-layout rules (pix_span, pix_layout_ok, pix_layout_tight, pix_ranges_overlap): every verdict and span
 //     against a restatement in 128-bit arithmetic over random fields and extreme ones (INT32_MAX pitches, INT64_MAX
 //     offsets and strides, negative values), and the tight layouts and spans of the five formats against their byte counts.
+//   * the same for the formats 16..24 (I422 .. V210) with the unit rule -- every used pitch, offset, frame_stride and the
+//     base a multiple of 1, 2 or 4 --, V210's tight pitch, ids 5..15 and 25 refused, pix_unit, and pixopt_ok at and past
+//     its limits.
 //   * denoise.hip's host restatement denoise_frame_host on heap blocks of exactly the frame's bytes at seven sizes (2x2
 //     and partial blocks among them), out of place and in place, against a per-sample restatement; the k tables at the
 //     limits of the parameters; denoise_ok and denoise_args_ok at their limits and one past each.
@@ -322,14 +325,26 @@ static void check_orient() {
 // the layout rules of include/h264mi.h restated in 128-bit arithmetic, one predicate per rule; the span, or -1
 static __int128 ref_pix_span(const h264mi_pix_layout &L, long long w, long long h) {
     if (w % 2 || h % 2 || w < 2 || h < 2 || w > 8192 || h > 8192) return -1;
-    __int128 rb[3], rows[3];
+    __int128 rb[3], rows[3], unit = 1;
     int np;
     switch (L.pix) {
     case 0: np = 3; rb[0] = w; rows[0] = h; rb[1] = rb[2] = w / 2; rows[1] = rows[2] = h / 2; break;
     case 1: case 2: np = 2; rb[0] = w; rows[0] = h; rb[1] = w; rows[1] = h / 2; break;
     case 3: case 4: np = 1; rb[0] = 2 * w; rows[0] = h; break;
+    // the table of ids 16..24: I422, I444, NV16, Y800, P010, I010, P210, I210, V210
+    case 16: np = 3; rb[0] = w; rb[1] = rb[2] = w / 2; rows[0] = rows[1] = rows[2] = h; break;
+    case 17: np = 3; rb[0] = rb[1] = rb[2] = w; rows[0] = rows[1] = rows[2] = h; break;
+    case 18: np = 2; rb[0] = rb[1] = w; rows[0] = rows[1] = h; break;
+    case 19: np = 1; rb[0] = w; rows[0] = h; break;
+    case 20: np = 2; unit = 2; rb[0] = rb[1] = 2 * w; rows[0] = h; rows[1] = h / 2; break;
+    case 21: np = 3; unit = 2; rb[0] = 2 * w; rb[1] = rb[2] = w; rows[0] = h; rows[1] = rows[2] = h / 2; break;
+    case 22: np = 2; unit = 2; rb[0] = rb[1] = 2 * w; rows[0] = rows[1] = h; break;
+    case 23: np = 3; unit = 2; rb[0] = 2 * w; rb[1] = rb[2] = w; rows[0] = rows[1] = rows[2] = h; break;
+    case 24: np = 1; unit = 4; rb[0] = 16 * ((w + 5) / 6); rows[0] = h; break;
     default: return -1;
     }
+    for (int p = 0; p < np; p++)
+        if ((__int128)L.pitch[p] % unit != 0 || (__int128)L.offset[p] % unit != 0) return -1;  // the unit rule
     __int128 lo[3], hi[3], span = 0;
     for (int p = 0; p < 3; p++) {
         if (p >= np) {
@@ -421,6 +436,96 @@ static void check_pix() {
     }
     CHECK(good > cases / 20 && good < cases - cases / 20);
     printf("pixel layouts: tight layouts of 5 formats x 6 sizes, %d random and extreme layouts (%d good)\n", cases, good);
+}
+
+static int ref_pix_unit(int pix) { return (pix >= 0 && pix <= 4) || (pix >= 16 && pix <= 19) ? 1 : pix >= 20 && pix <= 23 ? 2 : pix == 24 ? 4 : -1; }
+
+// the formats 16..24 and the unit rule: tight layouts, then random and extreme fields against the restatement
+static void check_pixdeep() {
+    const int sizes[][2] = {{2, 2}, {6, 2}, {36, 18}, {50, 2}, {1280, 720}, {8192, 8192}, {8192, 2}, {2, 8192}};
+    const int bits[9] = {16, 24, 16, 8, 24, 24, 32, 32, 0};
+    for (const auto &s : sizes)
+        for (int pix = 16; pix <= 24; pix++) {
+            std::unique_ptr<h264mi_pix_layout> L(new h264mi_pix_layout);
+            const long long w = s[0], h = s[1];
+            CHECK(pix_layout_tight(L.get(), pix, s[0], s[1]) == 0 && L->pix == pix && L->offset[0] == 0 && pix_layout_ok(L.get(), s[0], s[1]));
+            const long long span = pix == 24 ? (h - 1) * 128 * ((w + 47) / 48) + 16 * ((w + 5) / 6) : w * h * bits[pix - 16] / 8;
+            CHECK(pix_span(L.get(), s[0], s[1]) == span && ref_pix_span(*L, w, h) == span);
+            CHECK(L->frame_stride == (pix == 24 ? h * 128 * ((w + 47) / 48) : span) && L->frame_stride % ref_pix_unit(pix) == 0);
+            if (pix == 24) CHECK(L->pitch[0] == 128 * ((w + 47) / 48) && L->pitch[0] <= 65536);
+            h264mi_pix_layout m = *L;
+            m.frame_stride = span - ref_pix_unit(pix);
+            CHECK(!pix_layout_ok(&m, s[0], s[1]) && pix_span(&m, s[0], s[1]) == span);
+            for (int d = 1; d < ref_pix_unit(pix); d++) {  // the unit rule, field by field
+                m = *L; m.frame_stride += d;
+                CHECK(!pix_layout_ok(&m, s[0], s[1]) && pix_span(&m, s[0], s[1]) == span);
+                m = *L; m.offset[0] += d; m.frame_stride = INT64_MAX - 3;
+                CHECK(!pix_layout_ok(&m, s[0], s[1]) && pix_span(&m, s[0], s[1]) == -1);
+                m = *L; m.pitch[0] += d; m.frame_stride = INT64_MAX - 3;
+                CHECK(!pix_layout_ok(&m, s[0], s[1]) && pix_span(&m, s[0], s[1]) == -1);
+                CHECK(!pix_base_ok((const void *)(uintptr_t)(0x10000000u + d), *L));
+            }
+            CHECK(pix_base_ok((const void *)(uintptr_t)0x10000000u, *L) && pix_base_ok((const void *)(uintptr_t)(0x10000000u + 4), *L));
+        }
+    for (int pix = -2; pix <= 30; pix++) CHECK(pix_unit(pix) == ref_pix_unit(pix) && (pix_planes(pix) == 0) == (ref_pix_unit(pix) < 0));
+    CHECK(pix_unit(INT32_MAX) == -1 && pix_unit(INT32_MIN) == -1);
+    h264mi_pix_layout keep{7, {7, 7, 7}, {7, 7, 7}, 7};
+    for (int bad = 5; bad <= 15; bad++) CHECK(pix_layout_tight(&keep, bad, 16, 16) == -1);
+    CHECK(pix_layout_tight(&keep, 25, 16, 16) == -1 && keep.pix == 7 && keep.frame_stride == 7);
+    const int32_t e32[] = {0, 1, -1, 2, 2147483647, -2147483647 - 1, 65536, 65537, 65534, 16, 18, 36, 72, 96, 144};
+    const int64_t e64[] = {0, 1, -1, 2, INT64_MAX, INT64_MIN, INT64_MAX - 1, INT64_MAX - 3, INT64_MAX - 647, 1LL << 31, 1LL << 32, 648, 1296, 2592};
+    int good = 0, cases = 0;
+    for (int it = 0; it < 200000; it++) {
+        std::unique_ptr<h264mi_pix_layout> L(new h264mi_pix_layout);  // a heap block of exactly the struct
+        int w = 36, h = 18;
+        if (it % 2) {
+            L->pix = 14 + (int)(pix_rng() % 13);
+            for (int p = 0; p < 3; p++) {
+                L->pitch[p] = pix_rng() % 3 ? (int32_t)(pix_rng() % 300) : e32[pix_rng() % (sizeof e32 / sizeof *e32)];
+                L->offset[p] = pix_rng() % 3 ? (int64_t)(pix_rng() % 6000) : e64[pix_rng() % (sizeof e64 / sizeof *e64)];
+            }
+            L->frame_stride = pix_rng() % 3 ? (int64_t)(pix_rng() % 12000) : e64[pix_rng() % (sizeof e64 / sizeof *e64)];
+            if (pix_rng() % 8 == 0) w = e32[pix_rng() % (sizeof e32 / sizeof *e32)];
+            if (pix_rng() % 8 == 0) h = e32[pix_rng() % (sizeof e32 / sizeof *e32)];
+        } else {  // a tight layout with one field moved a little or to an extreme
+            CHECK(pix_layout_tight(L.get(), 16 + (int)(pix_rng() % 9), w, h) == 0);
+            const int f = (int)(pix_rng() % 9);
+            const bool ext = pix_rng() % 4 == 0;
+            const int d = (int)(pix_rng() % 17) - 8;
+            if (f < 3) L->pitch[f] = ext ? e32[pix_rng() % (sizeof e32 / sizeof *e32)] : L->pitch[f] + d;
+            else if (f < 6) L->offset[f - 3] = ext ? e64[pix_rng() % (sizeof e64 / sizeof *e64)] : L->offset[f - 3] + d;
+            else if (f == 6) L->frame_stride = ext ? e64[pix_rng() % (sizeof e64 / sizeof *e64)] : L->frame_stride + d;
+        }
+        const __int128 want = ref_pix_span(*L, w, h);
+        CHECK((__int128)pix_span(L.get(), w, h) == want);
+        const bool ok = want >= 0 && (__int128)L->frame_stride >= want && (__int128)L->frame_stride % ref_pix_unit(L->pix) == 0;
+        CHECK(pix_layout_ok(L.get(), w, h) == ok);
+        CHECK(pix_args_ok(L.get(), w, h, 1) == ok && !pix_args_ok(L.get(), w, h, 0));
+        if (ok) {
+            const int n = 1 + (int)(pix_rng() % 3);
+            const uintptr_t a0 = 0x10000000u, b0 = pix_rng() % 2 ? a0 + (uintptr_t)(pix_rng() % 16000) : a0 - (uintptr_t)(pix_rng() % 16000);
+            const unsigned __int128 ab = (unsigned __int128)L->frame_stride * n, bb = (unsigned __int128)i420_bytes(w, h) * n;
+            const bool share = (ab >> 63) != 0 || ((unsigned __int128)a0 < b0 + bb && (unsigned __int128)b0 < a0 + ab);
+            CHECK(pix_ranges_overlap((const void *)a0, *L, (const void *)b0, w, h, n) == share);
+        }
+        good += ok;
+        cases++;
+    }
+    CHECK(good > cases / 20 && good < cases - cases / 20);
+    // h264mi_pixopt: depth 0..2, reserved all zero
+    for (int depth = -2; depth <= 4; depth++) {
+        std::unique_ptr<h264mi_pixopt> o(new h264mi_pixopt{depth, {0, 0, 0}});
+        CHECK(pixopt_ok(o.get()) == (depth >= 0 && depth <= 2));
+        for (int k = 0; k < 3; k++)
+            for (int32_t v : {1, -1, INT32_MAX, INT32_MIN}) {
+                h264mi_pixopt q = *o;
+                q.reserved[k] = v;
+                CHECK(!pixopt_ok(&q));
+            }
+    }
+    const h264mi_pixopt lo{INT32_MIN, {0, 0, 0}}, hi{INT32_MAX, {0, 0, 0}};
+    CHECK(!pixopt_ok(nullptr) && !pixopt_ok(&lo) && !pixopt_ok(&hi));
+    printf("deep pixel layouts: tight layouts of 9 formats x 8 sizes with the unit rule, %d random and extreme layouts (%d good), pixopt\n", cases, good);
 }
 
 // the sample rule and the gate restated sample by sample: every sample looks its own block up
@@ -716,6 +821,7 @@ int main() {
     check_scenecut();
     check_denoise();
     check_pix();
+    check_pixdeep();
     check_orient();
     check_cells();
     check_tables();
