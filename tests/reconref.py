@@ -105,8 +105,10 @@ def required_classes():
 
 
 class Result:
-    def __init__(self, planes, records, counts, units):
+    def __init__(self, planes, records, counts, units, pred=None, skip_mv=None):
         self.planes, self.records, self.counts, self._units = planes, records, counts, units
+        self.skip_mv = skip_mv   # macroblock address of every P_L0_16x16 -> the vector a P_Skip would have had there (8.4.1.1)
+        self.pred = pred   # the prediction sample of every position, three planes beside `planes` (I_PCM: the sample itself)
 
     def i420(self, w=None, h=None):
         Y, U, V_ = self.planes
@@ -136,6 +138,7 @@ class _Picture:
         W, H = 16 * mbw, 16 * mbh
         self.P = [np.zeros((H, W), np.int32), np.zeros((H // 2, W // 2), np.int32), np.zeros((H // 2, W // 2), np.int32)]
         self.built = [np.zeros(a.shape, bool) for a in self.P]       # sample constructed in this picture
+        self.pred = [np.full(a.shape, -1, np.int32) for a in self.P]  # the prediction each sample was built from
         self.mv = np.zeros((4 * mbh, 4 * mbw, 2), np.int32)          # motion field on the 4x4 grid
         self.ref = np.full((4 * mbh, 4 * mbw), -1, np.int32)         # refIdxL0, -1 intra
         self.derived = np.zeros((4 * mbh, 4 * mbw), bool)            # the block's prediction mode / vector is known
@@ -547,6 +550,7 @@ def reconstruct(syntax, geometry, ref_planes=None):
     rec = np.zeros((mbw * mbh, REC_INTS), np.int32)
     hv = _halves(np.asarray(ref_planes[0])) if ref_planes is not None else None
     qpy = np.zeros(mbw * mbh, np.int32)
+    skip_mv = {}
     carried = [None] * (mbw * mbh)   # why the macroblock's QPY is its predecessor's: 'skip' / 'pcm' / 'cbp0', else None
 
     def note(addr, plane, x, y, w, h, what, cls):
@@ -612,6 +616,10 @@ def reconstruct(syntax, geometry, ref_planes=None):
             pic.P[0][Y:Y + 16, X:X + 16] = pcm[:256].reshape(16, 16)
             pic.P[1][Y // 2:Y // 2 + 8, X // 2:X // 2 + 8] = pcm[256:320].reshape(8, 8)
             pic.P[2][Y // 2:Y // 2 + 8, X // 2:X // 2 + 8] = pcm[320:384].reshape(8, 8)
+            for pl, sz in ((0, 16), (1, 8), (2, 8)):
+                py, px = Y * sz // 16, X * sz // 16
+                assert (pic.pred[pl][py:py + sz, px:px + sz] == -1).all()
+                pic.pred[pl][py:py + sz, px:px + sz] = pic.P[pl][py:py + sz, px:px + sz]
             r[2:18] = 16
             _finish_mb(pic, addr, intra=True)
             continue
@@ -661,6 +669,8 @@ def reconstruct(syntax, geometry, ref_planes=None):
             hh, ww = u.shape
             pic.P[plane][py:py + hh, px:px + ww] = np.clip(u, 0, 255)
             pic.built[plane][py:py + hh, px:px + ww] = True
+            assert (pic.pred[plane][py:py + hh, px:px + ww] == -1).all(), 'a sample predicted twice'
+            pic.pred[plane][py:py + hh, px:px + ww] = pred
             return cls
 
         if typ in (0, 1):     # ---- intra (8.3)
@@ -715,6 +725,7 @@ def reconstruct(syntax, geometry, ref_planes=None):
             parts = [(0, 0, 16, 16, 'skip', 0)]
         elif typ == 2:
             parts = [(0, 0, 16, 16, None, 0)]
+            skip_mv[addr] = tuple(_skip_mv(pic, addr)[0])
         elif typ == 4:
             parts = [(0, 0, 16, 8, '16x8', 0), (0, 8, 16, 8, '16x8', 1)]
         elif typ == 5:
@@ -757,7 +768,8 @@ def reconstruct(syntax, geometry, ref_planes=None):
 
     rec[:, 22:54] = pic.mv.reshape(mbh, 4, mbw, 4, 2).transpose(0, 2, 1, 3, 4).reshape(mbw * mbh, 32)
     planes = tuple(a.astype(np.uint8) for a in pic.P)
-    return Result(planes, rec, counts, units)
+    assert all((a >= 0).all() for a in pic.pred), 'a sample without a prediction'
+    return Result(planes, rec, counts, units, tuple(a.astype(np.uint8) for a in pic.pred), skip_mv)
 
 
 def _finish_mb(pic, addr, intra):
