@@ -999,6 +999,82 @@ int h264mi_i420_deinterlace_host(void *dst, const void *cur, const void *prev, i
 int h264mi_enc_set_deinterlace(h264mi_encoder *e, const h264mi_deinterlace *p);
 int h264mi_enc_deinterlace(h264mi_encoder *e, h264mi_deinterlace *out);
 
+/* Sharpening, blurring and masking a picture on the device: the spatial filter that follows a
+   downscale or a denoise -- an unsharp mask; with a negative amount a pre-blur that saves bits on low rungs -- and
+   privacy masks for many-camera recording. The library's own rules, exact integers, the same bytes on any host
+   (tests/spatialref.py restates them in numpy). A frame is tight I420, w x h, both sides even, 2..8192.
+     radius_y, radius_c  0..3      the low-pass' radius for luma and for both chroma planes; 0 copies the plane(s)
+     amount_y, amount_c  -64..255  in 1/64 units; 0 copies the plane(s), -64 is the pure blur
+     core                0..255    with a positive amount, differences of at most core are left alone
+   The rule applies to each plane on its own, with the plane's own pw x ph and its kind's radius r and amount. C is the
+   source sample, O the output.
+     Low-pass L: the separable binomial of radius r, row weights {1,2,1}, {1,4,6,4,1}, {1,6,15,20,15,6,1} (sum 4^r),
+       over samples whose coordinates are clamped to the plane. S = sum over j, i = -r..r of wt[j] wt[i]
+       C[cy(y + j)][cx(x + i)], not rounded in between (the horizontal sum is at most 255 * 64, S at most 255 * 4096);
+       L = (S + (1 << (4r - 1))) >> 4r.
+     Sample: d = C - L. If amount > 0 and |d| <= core then O = C. Otherwise O = clip(0, 255, C + ((amount * d + 32) >> 6)),
+       the shift arithmetic (floor). amount == -64 gives O = L exactly.
+   A setting whose planes are all inert (r == 0 or amount == 0 for luma and for chroma) is "off" for an encoder.
+   Not provided: region-limited blur, larger radii, per-stream parameters, decoder-side use. */
+typedef struct { int32_t radius_y, radius_c, amount_y, amount_c, core; } h264mi_spatial;
+/* host only: 0 when every field of *p is in its range, -1 otherwise (a null pointer included) */
+int h264mi_spatial_ok(const h264mi_spatial *p);
+/* async on hip_stream: n >= 1 frames at d_src filtered into the n frames at d_dst, one launch; no scratch memory. Any
+   alignment of the frames. A stencil: out of place only. No access leaves a plane, nothing outside the n destination
+   frames is written, the source is not written. Returns 0, or -1 before anything is enqueued on: a null d_dst, d_src or
+   p, an odd side or one outside 2..8192, n < 1, a parameter out of range, any byte the two ranges share. */
+int h264mi_i420_spatial_dev(void *d_dst, const void *d_src, int w, int h, int n, const h264mi_spatial *p, void *hip_stream);
+/* host only: the same rule for one frame in host memory as plain loops (the restatement the device is tested against);
+   dst and src must not overlap. Returns 0, or -1 on a null pointer, a bad side or parameter. */
+int h264mi_i420_spatial_host(void *dst, const void *src, int w, int h, const h264mi_spatial *p);
+
+/* A privacy mask: the luma rectangle (x, y, w, h) of frame `frame` -- all four even, w, h >= 2, inside the frame -- and
+   the chroma rectangle (x/2, y/2, w/2, h/2) of Cb and of Cr.
+     H264MI_PRIVACY_PIXELATE  block is 4, 8, 16, 32 or 64. The rectangle of a plane is cut into cells of B x B samples
+                              (B = block for luma, block / 2 for chroma) on a grid anchored at the rectangle's own
+                              corner; the cells at its right and lower edge are partial. Every sample of a cell becomes
+                              (sum + n / 2) / n over the cell's n samples, integer division. The fill values are ignored.
+     H264MI_PRIVACY_FILL      every luma sample becomes fill_y, every Cb sample fill_cb, every Cr sample fill_cr, each
+                              0..255. block is ignored.
+   Two rectangles on the same frame that share a sample are refused; a list holds at most 4096 entries.
+   Not provided: overlapping masks, blurred (rather than pixelated) regions, mask lists that live on the device. */
+#define H264MI_PRIVACY_PIXELATE 0
+#define H264MI_PRIVACY_FILL 1
+#define H264MI_PRIVACY_PER_LAUNCH 64 /* entries that travel in one kernel launch's arguments */
+typedef struct { int32_t frame, x, y, w, h, mode, block, fill_y, fill_cb, fill_cr; } h264mi_privacy;
+/* host only: 0 when list[0..n-1] is a good list for nframes frames of w x h, -1 otherwise (a null list, n outside
+   1..4096, an odd side or one outside 2..8192, nframes < 1, a bad entry, two entries of one frame that share a sample) */
+int h264mi_privacy_ok(const h264mi_privacy *list, int n, int w, int h, int nframes);
+/* async on hip_stream: the masks of list (host memory, copied by the call) applied in place to the nframes tight w x h
+   I420 frames at d_frames; one launch per 64 entries, no scratch memory: a cell reads only what it writes. Any alignment.
+   Samples outside the rectangles are never written. Returns 0, or -1 before anything is enqueued on a null d_frames
+   or a list h264mi_privacy_ok refuses. */
+int h264mi_i420_privacy_dev(void *d_frames, int w, int h, int nframes, const h264mi_privacy *list, int nlist, void *hip_stream);
+/* host only: the same for frames in host memory, as plain loops. Returns 0 or -1 as above. */
+int h264mi_i420_privacy_host(void *frames, int w, int h, int nframes, const h264mi_privacy *list, int nlist);
+
+/* the encoder's spatial filter and privacy masks. Every entry point that codes the input area (h264mi_enc_encode, which
+   then copies the caller's frames into the input area as with an overlay list, _rgba, _scaled, _oriented, _pix,
+   _composed, _composed_any) runs, on the encoder's stream and in this order: the deinterlacer, the denoiser, the
+   spatial filter, the privacy masks, the key-frame policy, the overlay list, the frame step.
+     * The spatial filter (NULL or an inert setting: off) owns nstreams frames of device memory to filter *into* --
+       allocated when it is turned on, freed when it is turned off and at destroy. The later stages and the frame step
+       work on that buffer: the denoiser's state never holds a sharpened or masked frame, and sharpen-after-downscale
+       is h264mi_enc_encode_scaled with the filter on.
+     * The privacy list: `frame` is the stream index; n == 0 clears it. The entries are copied. The masks are applied
+       in place to the frames the filter left (or to the input area). The key-frame policy sees the frame as coded
+       without sprites; labels are blended over masks; quality records compare what was coded.
+     * Off (the default) nothing changes: no launch, no allocation. The drop-in functions never use either.
+   h264mi_enc_set_spatial returns 0, or -1 with the setting in force unchanged on a null encoder, parameters
+   h264mi_spatial_ok refuses, or a failed allocation; h264mi_enc_spatial returns 1 (on, *out filled when out is not
+   null), 0 (off, *out untouched) or -1 (a null encoder). h264mi_enc_set_privacy returns 0, or -1 with the list in force
+   unchanged on a null encoder or a list h264mi_privacy_ok refuses for the encoder's size and streams;
+   h264mi_enc_privacy returns the number of entries in force, or -1 on a null encoder. */
+int h264mi_enc_set_spatial(h264mi_encoder *e, const h264mi_spatial *p);
+int h264mi_enc_spatial(h264mi_encoder *e, h264mi_spatial *out);
+int h264mi_enc_set_privacy(h264mi_encoder *e, const h264mi_privacy *list, int n);
+int h264mi_enc_privacy(h264mi_encoder *e);
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -15,6 +15,7 @@ SRC_COLORSPACE = os.path.join(HERE, 'csrc', 'colorspace.hip')  # likewise
 SRC_DENOISE = os.path.join(HERE, 'csrc', 'denoise.hip')  # likewise
 SRC_SCENECUT = os.path.join(HERE, 'csrc', 'scenecut.hip')  # likewise
 SRC_DEINTERLACE = os.path.join(HERE, 'csrc', 'deinterlace.hip')  # likewise
+SRC_SPATIAL = os.path.join(HERE, 'csrc', 'spatial.hip')  # likewise
 OUT = os.path.join(HERE, 'lib', 'libh264mi.so')
 
 
@@ -26,7 +27,7 @@ def build(force=False, verbose=False):
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wno-unused-result',
            '-Wno-pass-failed', '-o', OUT + '.tmp', SRC, SRC_QUALITY, SRC_SCALE, SRC_COMPOSE, SRC_OVERLAY, SRC_UPSCALE, SRC_ORIENT, SRC_PIXFMT, SRC_PIXDEEP,
-           SRC_COLORSPACE, SRC_DENOISE, SRC_SCENECUT, SRC_DEINTERLACE]
+           SRC_COLORSPACE, SRC_DENOISE, SRC_SCENECUT, SRC_DEINTERLACE, SRC_SPATIAL]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)

@@ -223,6 +223,31 @@ int h264mi_i420_deinterlace_host(void *dst, const void *cur, const void *prev, i
 }
 int h264mi_enc_set_deinterlace(h264mi_encoder *e, const h264mi_deinterlace *p) { return e ? enc_set_deinterlace(e->c, p) : -1; }
 int h264mi_enc_deinterlace(h264mi_encoder *e, h264mi_deinterlace *out) { return e ? stage_get(e->c->in.di, out) : -1; }
+// The spatial filter and the privacy masks (DESIGN.md §5.18; spatial.hip; the checks: picture_host.h)
+int h264mi_spatial_ok(const h264mi_spatial *p) { return spatial_ok(p) ? 0 : -1; }
+int h264mi_i420_spatial_dev(void *d_dst, const void *d_src, int w, int h, int n, const h264mi_spatial *p, void *hip_stream) {
+    if (!spatial_args_ok(d_dst, d_src, w, h, n, p)) return -1;
+    return launch_spatial_i420((uint8_t *)d_dst, (const uint8_t *)d_src, w, h, n, *p, (hipStream_t)hip_stream);
+}
+int h264mi_i420_spatial_host(void *dst, const void *src, int w, int h, const h264mi_spatial *p) {
+    if (!spatial_args_ok(dst, src, w, h, 1, p)) return -1;
+    spatial_frame_host((uint8_t *)dst, (const uint8_t *)src, w, h, *p);
+    return 0;
+}
+int h264mi_privacy_ok(const h264mi_privacy *list, int n, int w, int h, int nframes) { return privacy_ok(list, n, w, h, nframes) ? 0 : -1; }
+int h264mi_i420_privacy_dev(void *d_frames, int w, int h, int nframes, const h264mi_privacy *list, int nlist, void *hip_stream) {
+    if (!d_frames || !privacy_ok(list, nlist, w, h, nframes)) return -1;
+    return launch_privacy_i420((uint8_t *)d_frames, w, h, list, nlist, (hipStream_t)hip_stream);
+}
+int h264mi_i420_privacy_host(void *frames, int w, int h, int nframes, const h264mi_privacy *list, int nlist) {
+    if (!frames || !privacy_ok(list, nlist, w, h, nframes)) return -1;
+    privacy_frames_host((uint8_t *)frames, w, h, list, nlist);
+    return 0;
+}
+int h264mi_enc_set_spatial(h264mi_encoder *e, const h264mi_spatial *p) { return e ? enc_set_spatial(e->c, p) : -1; }
+int h264mi_enc_spatial(h264mi_encoder *e, h264mi_spatial *out) { return e ? stage_get(e->c->in.sp, out) : -1; }
+int h264mi_enc_set_privacy(h264mi_encoder *e, const h264mi_privacy *list, int n) { return e ? enc_set_privacy(e->c, list, n) : -1; }
+int h264mi_enc_privacy(h264mi_encoder *e) { return e ? (int)e->c->in.pv.list.size() : -1; }
 // The scene-cut detector (DESIGN.md §5.14; scenecut.hip; the checks: picture_host.h): n frames, one launch
 int h264mi_scenecut_ok(const h264mi_scenecut *p) { return scenecut_ok(p) ? 0 : -1; }
 int h264mi_thumb_size(int w, int h, int *tw, int *th) {

@@ -20,7 +20,8 @@ template <class T> static int state_ensure(T *&p, size_t bytes) {
 }
 // enc_free's part. Nothing waits here: h264mi_enc_destroy has synchronised the stream, the wrapper's encoder has no stage
 static void enc_input_release(EncCtx *c) {
-    state_free(c->in.di.d_prev); state_free(c->in.dn.d_prev); state_free(c->in.sc.d_words); state_free(c->in.sc.d_thumb);
+    state_free(c->in.di.d_prev); state_free(c->in.dn.d_prev); state_free(c->in.sp.d_buf); state_free(c->in.sc.d_words);
+    state_free(c->in.sc.d_thumb);
 }
 
 // ---------------------------------------------------------------- the chain
@@ -28,11 +29,15 @@ static void enc_input_release(EncCtx *c) {
 // deinterlace.hip; nothing when off) -- in place against the previous unfiltered frames, which the same launch
 // replaces; the first frame spatial only --, the pre-filter in force (DESIGN.md §5.13; denoise.hip;
 // nothing when off) -- the first frame only copied to the state, every later one filtered in place against the state,
-// which receives the same bytes --, the key-frame policy in force (below), the overlay list in force blended into it
-// (DESIGN.md §5.6; overlay.hip; nothing without a list), then the frame step. A launch that fails ends the call with
-// -1 where it stands: no frame is submitted, and the states of the steps in front of it have advanced
+// which receives the same bytes --, the spatial filter in force (DESIGN.md §5.18; spatial.hip; nothing when off) -- out
+// of place into the stage's own frames, which are the current frames `cur` of everything behind it, so the denoiser's
+// state never holds a sharpened frame --, the privacy masks in force (the same unit; nothing without a list) in place
+// on the current frames, the key-frame policy in force (below), the overlay list in force blended into them
+// (DESIGN.md §5.6; overlay.hip; nothing without a list), then the frame step on them. A launch that fails ends the
+// call with -1 where it stands: no frame is submitted, and the states of the steps in front of it have advanced
 static int enc_code_input(EncCtx *c) {
     EncInput &in = c->in;
+    uint8_t *cur = c->d_src;  // the current frames: the input area, behind the spatial filter its buffer
     if (in.di.on) {
         if (launch_deinterlace_i420(c->d_src, in.di.d_prev, c->d_src, in.di.has ? in.di.d_prev : nullptr, c->w, c->h, c->S, in.di.p, nullptr, c->stream) != 0)
             return -1;
@@ -46,6 +51,11 @@ static int enc_code_input(EncCtx *c) {
             return -1;
         }
     }
+    if (in.sp.on) {
+        if (launch_spatial_i420(in.sp.d_buf, cur, c->w, c->h, c->S, in.sp.p, c->stream) != 0) return -1;
+        cur = in.sp.d_buf;
+    }
+    if (!in.pv.list.empty() && launch_privacy_i420(cur, c->w, c->h, in.pv.list.data(), (int)in.pv.list.size(), c->stream) != 0) return -1;
     // the key-frame policy in force (DESIGN.md §5.14; scenecut.hip; nothing when off): the detector -- the first frame
     // only stores its thumbnails, every later one advances them in place and leaves its statistics; no launch with
     // share == 0 --, then the decision, which sets EncState::force_idr in front of the frame step's begin kernel
@@ -54,19 +64,19 @@ static int enc_code_input(EncCtx *c) {
         if (in.sc.p.share > 0) {
             const bool has = in.sc.has;
             if (has) stats = in.sc.d_words + 16 * (size_t)c->S;
-            if (launch_scenecut_i420(stats, in.sc.d_thumb, c->d_src, has ? in.sc.d_thumb : nullptr, c->w, c->h, c->S, in.sc.p, c->stream) != 0)
+            if (launch_scenecut_i420(stats, in.sc.d_thumb, cur, has ? in.sc.d_thumb : nullptr, c->w, c->h, c->S, in.sc.p, c->stream) != 0)
                 return -1;
             in.sc.has = true;
         }
         if (launch_scenecut_decide(c->d_st, in.sc.d_words, stats, c->S, in.sc.p, c->stream) != 0) return -1;
     }
     if (!in.ov.list.empty() &&
-        launch_overlay_i420(c->d_src, c->w, c->h, in.ov.sprites, in.ov.w, in.ov.h, in.ov.list.data(), (int)in.ov.list.size(), c->stream) != 0)
+        launch_overlay_i420(cur, c->w, c->h, in.ov.sprites, in.ov.w, in.ov.h, in.ov.list.data(), (int)in.ov.list.size(), c->stream) != 0)
         return -1;
-    return enc_frame(c, c->d_src);
+    return enc_frame(c, cur);
 }
 // h264mi_enc_encode: with every stage off the caller's frames are coded where they lie; with the deinterlacer, the
-// pre-filter or the key-frame policy on or an overlay list in force they are copied into the input area, filtered,
+// pre-filter, the spatial filter or the key-frame policy on or a mask or overlay list in force they are copied into the input area, filtered,
 // looked at and blended there and coded from there
 static int enc_encode(EncCtx *c, const void *d_frames) {
     if (!c->in.any()) return enc_frame(c, (const uint8_t *)d_frames);
@@ -107,6 +117,22 @@ static int enc_set_denoise(EncCtx *c, const h264mi_denoise *p) {
 static int enc_set_deinterlace(EncCtx *c, const h264mi_deinterlace *p) {
     if (p && !deinterlace_ok(p)) return -1;
     return set_prev_frame_stage(c, c->in.di, p, !p);
+}
+// the spatial filter: NULL or an inert setting turn it off and free the frames it filtered into
+static int enc_set_spatial(EncCtx *c, const h264mi_spatial *p) {
+    if (p && !spatial_ok(p)) return -1;
+    EncInput::Spatial &s = c->in.sp;
+    if (!p || spatial_inert(*p)) { state_drop(c, s.d_buf); s.on = false; return 0; }
+    if (!canvas_ok(c->w, c->h) || state_ensure(s.d_buf, (size_t)c->S * c->fbytes) < 0) return -1;
+    s.p = *p; s.on = true;
+    return 0;
+}
+// the privacy masks: n == 0 clears the list. The entries are copied; frame is the stream
+static int enc_set_privacy(EncCtx *c, const h264mi_privacy *list, int n) {
+    if (n == 0) { c->in.pv.list.clear(); return 0; }
+    if (!privacy_ok(list, n, c->w, c->h, c->S)) return -1;
+    c->in.pv.list.assign(list, list + n);
+    return 0;
 }
 // the key-frame policy: NULL or share == 0 && max_gap == 0 turn it off. The words are zeroed on the stream when they
 // are allocated and kept across a change of the parameters; the thumbnails exist only with share > 0

@@ -1,5 +1,5 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip, pixdeep.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, pixdeep.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
@@ -281,6 +281,57 @@ static inline bool deinterlace_args_ok(const void *dst, const void *prev_out, co
     return true;
 }
 
+// ---- the spatial filter and the privacy masks (include/h264mi.h)
+constexpr int SPATIAL_MAX_RADIUS = 3, SPATIAL_MIN_AMOUNT = -64, SPATIAL_MAX_AMOUNT = 255, SPATIAL_MAX_CORE = 255;
+static inline bool spatial_ok(const h264mi_spatial *p) {
+    return p && p->radius_y >= 0 && p->radius_y <= SPATIAL_MAX_RADIUS && p->radius_c >= 0 && p->radius_c <= SPATIAL_MAX_RADIUS &&
+           p->amount_y >= SPATIAL_MIN_AMOUNT && p->amount_y <= SPATIAL_MAX_AMOUNT && p->amount_c >= SPATIAL_MIN_AMOUNT &&
+           p->amount_c <= SPATIAL_MAX_AMOUNT && p->core >= 0 && p->core <= SPATIAL_MAX_CORE;
+}
+// a good setting that changes no sample: each plane kind has r == 0 or amount == 0
+static inline bool spatial_inert(const h264mi_spatial &p) {
+    return (p.radius_y == 0 || p.amount_y == 0) && (p.radius_c == 0 || p.amount_c == 0);
+}
+// row weight k = 0..2r of the binomial of radius r = 1..3; the weights of a row sum to 4^r
+__host__ __device__ static inline int spatial_weight(int r, int k) {
+    return r == 1 ? (k == 1 ? 2 : 1) : r == 2 ? (k == 2 ? 6 : (k & 1) ? 4 : 1) : (k == 3 ? 20 : (k == 2 || k == 4) ? 15 : (k == 1 || k == 5) ? 6 : 1);
+}
+// the sample rule: c the source sample, l the low-pass there
+__host__ __device__ static inline int spatial_sample(int c, int l, int amount, int core) {
+    const int d = c - l;
+    if (amount > 0 && (d < 0 ? -d : d) <= core) return c;
+    const int o = c + ((amount * d + 32) >> 6);
+    return o < 0 ? 0 : o > 255 ? 255 : o;
+}
+// arguments of a spatial call, the pointers' values included
+static inline bool spatial_args_ok(const void *dst, const void *src, int w, int h, int n, const h264mi_spatial *p) {
+    if (!dst || !src || n < 1 || !canvas_ok(w, h) || !spatial_ok(p)) return false;
+    const size_t nb = (size_t)n * i420_bytes(w, h);
+    return !byte_ranges_overlap(dst, nb, src, nb);
+}
+// a list of privacy masks for nframes frames of w x h, everything but the frames' pointer. No entry is read before list
+// and n are known to be good
+static inline bool privacy_ok(const h264mi_privacy *list, int n, int w, int h, int nframes) {
+    if (!list || n <= 0 || n > PIC_MAX_LIST || nframes < 1 || !canvas_ok(w, h)) return false;
+    for (int k = 0; k < n; k++) {
+        const h264mi_privacy &m = list[k];
+        if (m.frame < 0 || m.frame >= nframes || ((m.x | m.y | m.w | m.h) & 1)) return false;
+        if (m.x < 0 || m.y < 0 || m.x > w || m.y > h || m.w < 2 || m.h < 2 || m.w > w - m.x || m.h > h - m.y) return false;
+        if (m.mode == H264MI_PRIVACY_PIXELATE) {
+            if (m.block != 4 && m.block != 8 && m.block != 16 && m.block != 32 && m.block != 64) return false;
+        } else if (m.mode == H264MI_PRIVACY_FILL) {
+            if ((uint32_t)m.fill_y > 255 || (uint32_t)m.fill_cb > 255 || (uint32_t)m.fill_cr > 255) return false;
+        } else {
+            return false;
+        }
+    }
+    for (int k = 1; k < n; k++)
+        for (int j = 0; j < k; j++)
+            if (list[k].frame == list[j].frame && rects_share(list[k].x, list[k].y, list[k].w, list[k].h, list[j].x, list[j].y, list[j].w, list[j].h))
+                return false;
+    return true;
+}
+
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
 static inline int cell_kind(const h264mi_cell &c) {
@@ -400,6 +451,11 @@ int launch_scenecut_decide(EncState *st, uint32_t *words, const uint32_t *stats,
 int launch_deinterlace_i420(uint8_t *dst, uint8_t *prev_out, const uint8_t *cur, const uint8_t *prev, int w, int h, int n,
                             const h264mi_deinterlace &p, uint32_t *stats, hipStream_t s);
 void deinterlace_frame_host(uint8_t *out, const uint8_t *cur, const uint8_t *prev, int w, int h, const h264mi_deinterlace &p, uint32_t *stats);
+// spatial.hip: arguments as spatial_args_ok / privacy_ok accept them. The _host functions: the same rules as plain loops
+int launch_spatial_i420(uint8_t *dst, const uint8_t *src, int w, int h, int n, const h264mi_spatial &p, hipStream_t s);
+void spatial_frame_host(uint8_t *out, const uint8_t *src, int w, int h, const h264mi_spatial &p);
+int launch_privacy_i420(uint8_t *frames, int w, int h, const h264mi_privacy *list, int nlist, hipStream_t s);
+void privacy_frames_host(uint8_t *frames, int w, int h, const h264mi_privacy *list, int nlist);
 // pixfmt.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);

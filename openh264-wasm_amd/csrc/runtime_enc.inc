@@ -163,6 +163,13 @@ struct EncInput {
         bool on = false, has = false; h264mi_denoise p = {};
         uint8_t *d_prev = nullptr;  // the S previous filtered frames
     } dn;
+    struct Spatial {  // the sharpen/blur filter: h264mi_enc_set_spatial; spatial.hip
+        bool on = false; h264mi_spatial p = {};
+        uint8_t *d_buf = nullptr;  // the S frames it filters into: what the later stages and the frame step work on
+    } sp;
+    struct Privacy {  // h264mi_enc_set_privacy; spatial.hip: host copies of the masks, frame = stream
+        std::vector<h264mi_privacy> list;  // empty: off
+    } pv;
     struct Scenecut {  // the key-frame policy: h264mi_enc_set_scenecut; scenecut.hip
         bool on = false, has = false; h264mi_scenecut p = {};
         uint32_t *d_words = nullptr;  // per stream sixteen words, then per stream eight statistics words: 24 S words
@@ -173,7 +180,7 @@ struct EncInput {
         const uint8_t *sprites = nullptr;
         int w = 0, h = 0;  // the sprites' size
     } ov;
-    bool any() const { return di.on || dn.on || sc.on || !ov.list.empty(); }
+    bool any() const { return di.on || dn.on || sp.on || !pv.list.empty() || sc.on || !ov.list.empty(); }
 };
 
 struct EncCtx {

@@ -193,6 +193,16 @@ def lib():
             'h264mi_enc_set_scenecut': (i, [vp, vp]),
             'h264mi_enc_scenecut': (i, [vp, vp]),
             'h264mi_enc_scenecut_state': (i, [vp, i, vp]),
+            'h264mi_spatial_ok': (i, [vp]),
+            'h264mi_i420_spatial_dev': (i, [vp, vp, i, i, i, vp, vp]),
+            'h264mi_i420_spatial_host': (i, [vp, vp, i, i, vp]),
+            'h264mi_privacy_ok': (i, [vp, i, i, i, i]),
+            'h264mi_i420_privacy_dev': (i, [vp, i, i, i, vp, i, vp]),
+            'h264mi_i420_privacy_host': (i, [vp, i, i, i, vp, i]),
+            'h264mi_enc_set_spatial': (i, [vp, vp]),
+            'h264mi_enc_spatial': (i, [vp, vp]),
+            'h264mi_enc_set_privacy': (i, [vp, vp, i]),
+            'h264mi_enc_privacy': (i, [vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -544,6 +554,32 @@ class BatchEncoder:
     def denoise(self):
         """the pre-filter in force: a Denoise (a copy), or None when it is off (h264mi_enc_denoise)"""
         return self._get_stage('denoise', Denoise)
+
+    def set_spatial(self, params):
+        """the sharpen/blur filter of every encode*() from its next call on (h264mi_enc_set_spatial): a Spatial, a
+        (radius_y, radius_c, amount_y, amount_c, core) tuple, or None for off (a setting that changes no plane is off
+        too). On, the encoder owns S frames to filter into, behind the denoiser and in front of the privacy masks, the
+        key-frame policy and the overlay list, which then work on those frames; encode_scaled() with the filter on is
+        sharpen-after-downscale. Off frees the frames. ValueError, with the setting in force unchanged, on parameters
+        spatial_ok refuses."""
+        self._set_stage('spatial', Spatial, params)
+
+    def spatial(self):
+        """the spatial filter in force: a Spatial (a copy), or None when it is off (h264mi_enc_spatial)"""
+        return self._get_stage('spatial', Spatial)
+
+    def set_privacy(self, masks):
+        """the privacy masks of every encode*() from its next call on (h264mi_enc_set_privacy): a sequence of Privacy
+        whose `frame` is the stream index; an empty one (or None) clears the list. The masks are applied behind the
+        spatial filter and in front of the key-frame policy and the overlay list: the samples never reach the stream,
+        labels are blended over masks. ValueError, with the list in force unchanged, on a list privacy_ok refuses."""
+        arr = _privacy_array(masks or ())
+        if self._L.h264mi_enc_set_privacy(self._e, arr if len(arr) else None, len(arr)) != 0:
+            raise ValueError(f'h264mi_enc_set_privacy refused {len(arr)} masks on {self.S} streams {self.w}x{self.h}')
+
+    def privacy(self):
+        """masks in force (h264mi_enc_privacy)"""
+        return self._L.h264mi_enc_privacy(self._e)
 
     def set_scenecut(self, params):
         """the key-frame policy of every encode*() from its next call on (h264mi_enc_set_scenecut): a Scenecut, a
@@ -1350,6 +1386,65 @@ def i420_deinterlace(dst, cur, w, h, n, params, prev=None, prev_out=None, stats=
     if lib().h264mi_i420_deinterlace_dev(_ptr(dst), _ptr(prev_out), _ptr(cur), _ptr(prev), w, h, n, _byref(d),
                                          _ptr(stats), _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
+
+
+class Spatial(_Record):
+    """h264mi_spatial (include/h264mi.h): radius_y, radius_c 0..3 (the binomial low-pass' radius; 0 copies), amount_y,
+    amount_c -64..255 in 1/64 units (positive sharpens, negative blurs, -64 is the low-pass itself, 0 copies), core
+    0..255 (with a positive amount, differences of at most core are left alone). 20 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('radius_y', 'radius_c', 'amount_y', 'amount_c', 'core')]
+
+
+def spatial_ok(params):
+    """0 when every field of params (a Spatial or five integers) is in its range, else -1 (None included);
+    h264mi_spatial_ok, host only"""
+    return lib().h264mi_spatial_ok(_byref(Spatial._of(params)))
+
+
+def i420_spatial(dst, src, w, h, n, params, stream=None):
+    """n tight w x h I420 frames (uint8 CUDA tensor src, any alignment) sharpened or blurred into dst; one launch, async
+    on stream (default: the current one); h264mi_i420_spatial_dev. params: a Spatial or (radius_y, radius_c, amount_y,
+    amount_c, core). Out of place only. The bytes equal tests/spatialref.py's. ValueError on a bad argument (a
+    parameter out of range, a side that is odd or outside 2..8192, n < 1, buffers that share a byte)."""
+    _assert_dev_u8(dst, src)
+    need = 0 if n <= 0 or min(w, h) <= 0 else n * _i420_bytes(w, h)
+    assert dst.numel() >= need and src.numel() >= need
+    d = Spatial._of(params)
+    if lib().h264mi_i420_spatial_dev(_ptr(dst), _ptr(src), w, h, n, _byref(d), _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
+
+
+PRIVACY_PIXELATE = 0  # H264MI_PRIVACY_PIXELATE: cells of block x block become their mean
+PRIVACY_FILL = 1      # H264MI_PRIVACY_FILL: the rectangle becomes (fill_y, fill_cb, fill_cr)
+
+
+class Privacy(_Record):
+    """h264mi_privacy (include/h264mi.h): the even rectangle (x, y, w, h) of frame `frame`, mode PRIVACY_PIXELATE with
+    block 4, 8, 16, 32 or 64, or PRIVACY_FILL with fill_y, fill_cb, fill_cr 0..255. 40 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('frame', 'x', 'y', 'w', 'h', 'mode', 'block', 'fill_y', 'fill_cb', 'fill_cr')]
+
+
+def _privacy_array(masks):
+    masks = [Privacy._of(m) for m in masks]
+    return (Privacy * len(masks))(*masks)
+
+
+def privacy_ok(masks, w, h, nframes):
+    """0 when masks (a sequence of Privacy or ten-integer tuples) is a good list for nframes frames of w x h, else -1
+    (an empty one included); h264mi_privacy_ok, host only"""
+    arr = _privacy_array(masks or ())
+    return lib().h264mi_privacy_ok(arr if len(arr) else None, len(arr), int(w), int(h), int(nframes))
+
+
+def i420_privacy(frames, w, h, nframes, masks, stream=None):
+    """the masks applied in place to nframes tight w x h I420 frames (uint8 CUDA tensor frames, any alignment); one
+    launch per 64 masks, async on stream (default: the current one); h264mi_i420_privacy_dev. Samples outside the
+    rectangles are never written. The bytes equal tests/spatialref.py's. ValueError on a list privacy_ok refuses."""
+    _assert_dev_u8(frames)
+    assert nframes <= 0 or min(w, h) <= 0 or frames.numel() >= nframes * _i420_bytes(w, h)
+    arr = _privacy_array(masks or ())
+    if lib().h264mi_i420_privacy_dev(_ptr(frames), int(w), int(h), int(nframes), arr if len(arr) else None, len(arr), _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {len(arr)} masks on {nframes} frames {w}x{h}')
 
 
 PIX_I420 = 0  # H264MI_PIX_*: planes Y (w x h), Cb, Cr (w/2 x h/2)

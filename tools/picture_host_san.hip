@@ -1,12 +1,12 @@
 // picture_host_san.hip -- the host rules of the picture calls (csrc/picture_host.h and the host halves of scale.hip,
-// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip, scenecut.hip, deinterlace.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
+// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
 // is loaded into Python, no kernel is launched, no device is needed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=all tools/picture_host_san.hip openh264-wasm_amd/csrc/scale.hip \
 //         openh264-wasm_amd/csrc/compose.hip openh264-wasm_amd/csrc/overlay.hip openh264-wasm_amd/csrc/upscale.hip \
 //         openh264-wasm_amd/csrc/orient.hip openh264-wasm_amd/csrc/denoise.hip openh264-wasm_amd/csrc/scenecut.hip \
-//         openh264-wasm_amd/csrc/deinterlace.hip -o picture_host_san && ./picture_host_san
+//         openh264-wasm_amd/csrc/deinterlace.hip openh264-wasm_amd/csrc/spatial.hip -o picture_host_san && ./picture_host_san
 //
 // It runs, with every table in a heap block of exactly the size the call may touch:
 //   * cells_ok (both values of may_enlarge) on valid lists and on every field of a cell made odd, negative, one past the
@@ -38,6 +38,11 @@
 //     sizes (2x2, one-row and five-row chroma planes, more than one strip and row group), for every parity x spatial x
 //     temporal, with and without a previous frame, out of place and in place, against a second per-sample loop that
 //     walks the scores in another order; deinterlace_ok and deinterlace_args_ok at their limits and one past each.
+//   * spatial.hip's host restatements spatial_frame_host and privacy_frames_host on heap blocks of exactly the frames'
+//     bytes: the filter at seven sizes (2x2, planes narrower than the stencil, more than one tile both ways) x eight
+//     parameter sets against a restatement that sums columns first and floors without a shift, the masks of three lists
+//     on three frames against a per-sample restatement; spatial_ok, spatial_args_ok and privacy_ok at their limits and
+//     one past each, lists of 4096 entries and one more.
 // Prints one line per group and "ok"; exits 1 at the first difference.
 #include <cstdio>
 #include <cstdlib>
@@ -816,7 +821,174 @@ static void check_scenecut() {
     printf("scenecut: %d frames at 7 sizes x 5 parameter sets (with and without outputs, in place), the cut test, scalar and range checks\n", frames);
 }
 
+// the filter restated the other way round: columns first into a 32-bit plane, then rows; the rule spelt out again
+static void ref_spatial(std::vector<uint8_t> &out, const uint8_t *src, int w, int h, const h264mi_spatial &p) {
+    static const int W[4][7] = {{1}, {1, 2, 1}, {1, 4, 6, 4, 1}, {1, 6, 15, 20, 15, 6, 1}};
+    size_t off = 0;
+    for (int pl = 0; pl < 3; pl++) {
+        const int pw = pl ? w / 2 : w, ph = pl ? h / 2 : h, r = pl ? p.radius_c : p.radius_y, am = pl ? p.amount_c : p.amount_y;
+        std::vector<long long> v((size_t)pw * ph);
+        for (int y = 0; y < ph; y++)
+            for (int x = 0; x < pw; x++) {
+                long long s = 0;
+                for (int j = -r; j <= r; j++) s += (long long)W[r][j + r] * src[off + (size_t)std::min(std::max(y + j, 0), ph - 1) * pw + x];
+                v[(size_t)y * pw + x] = s;
+            }
+        for (int y = 0; y < ph; y++)
+            for (int x = 0; x < pw; x++) {
+                long long s = 0;
+                for (int i = -r; i <= r; i++) s += (long long)W[r][i + r] * v[(size_t)y * pw + std::min(std::max(x + i, 0), pw - 1)];
+                const long long c = src[off + (size_t)y * pw + x];
+                long long o = c;
+                if (r > 0) {
+                    const long long l = (s + (1ll << (4 * r - 1))) >> (4 * r), d = c - l;
+                    if (!(am > 0 && llabs(d) <= p.core)) {
+                        const long long t = am * d + 32;
+                        o = c + (t >= 0 ? t / 64 : -((-t + 63) / 64));  // the floor without a shift
+                        o = std::min(255ll, std::max(0ll, o));
+                    }
+                }
+                out[off + (size_t)y * pw + x] = (uint8_t)o;
+            }
+        off += (size_t)pw * ph;
+    }
+}
+// the masks restated per sample: every sample looks up its rectangle and its cell
+static void ref_privacy(std::vector<uint8_t> &fr, int w, int h, int nframes, const std::vector<h264mi_privacy> &list) {
+    const std::vector<uint8_t> src(fr);
+    const size_t fb = i420_bytes(w, h);
+    for (int f = 0; f < nframes; f++) {
+        size_t off = 0;
+        for (int pl = 0; pl < 3; pl++) {
+            const int sh = pl ? 1 : 0, pw = w >> sh, ph = h >> sh;
+            for (int y = 0; y < ph; y++)
+                for (int x = 0; x < pw; x++)
+                    for (const h264mi_privacy &m : list) {
+                        const int rx = m.x >> sh, ry = m.y >> sh, rw = m.w >> sh, rh = m.h >> sh;
+                        if (m.frame != f || x < rx || x >= rx + rw || y < ry || y >= ry + rh) continue;
+                        uint8_t *o = &fr[f * fb + off + (size_t)y * pw + x];
+                        if (m.mode == H264MI_PRIVACY_FILL) { *o = (uint8_t)(pl == 0 ? m.fill_y : pl == 1 ? m.fill_cb : m.fill_cr); continue; }
+                        const int B = m.block >> sh, x0 = rx + (x - rx) / B * B, y0 = ry + (y - ry) / B * B;
+                        const int x1 = std::min(x0 + B, rx + rw), y1 = std::min(y0 + B, ry + rh);
+                        long long sum = 0, n = 0;
+                        for (int yy = y0; yy < y1; yy++)
+                            for (int xx = x0; xx < x1; xx++) { sum += src[f * fb + off + (size_t)yy * pw + xx]; n++; }
+                        *o = (uint8_t)((sum + n / 2) / n);
+                    }
+            off += (size_t)pw * ph;
+        }
+    }
+}
+
+static void check_spatial() {
+    const int sizes[][2] = {{2, 2}, {4, 4}, {8, 6}, {16, 16}, {36, 18}, {130, 66}, {260, 34}};
+    const h264mi_spatial sets[] = {{1, 2, 40, -17, 3}, {2, 3, -64, 255, 0}, {3, 1, 255, -64, 0}, {3, 3, -17, 40, 255}, {0, 2, 40, 40, 3},
+                                   {2, 0, -64, 40, 0}, {1, 1, 0, 0, 0}, {3, 3, 255, 255, 0}};
+    int frames = 0;
+    for (const auto &s : sizes)
+        for (const h264mi_spatial &p : sets) {
+            const int w = s[0], h = s[1];
+            const size_t fb = i420_bytes(w, h);
+            std::unique_ptr<uint8_t[]> src(new uint8_t[fb]), out(new uint8_t[fb]);  // exactly the frame's bytes
+            for (size_t i = 0; i < fb; i++) src[i] = (i / 5) % 3 == 0 ? (uint8_t)(255 * ((i / 2) & 1)) : (i / 7) % 4 == 0 ? 90 : (uint8_t)pix_rng();
+            memset(out.get(), 0x5A, fb);
+            std::vector<uint8_t> want(fb);
+            ref_spatial(want, src.get(), w, h, p);
+            spatial_frame_host(out.get(), src.get(), w, h, p);
+            CHECK(memcmp(out.get(), want.data(), fb) == 0);
+            if (spatial_inert(p)) CHECK(memcmp(out.get(), src.get(), fb) == 0);
+            frames++;
+        }
+    for (int r = 1; r <= 3; r++) {
+        int sum = 0;
+        for (int k = 0; k <= 2 * r; k++) { sum += spatial_weight(r, k); CHECK(spatial_weight(r, k) == spatial_weight(r, 2 * r - k)); }
+        CHECK(sum == 1 << (2 * r));
+    }
+    CHECK(spatial_sample(100, 90, 64, 0) == 110 && spatial_sample(100, 90, -64, 0) == 90 && spatial_sample(100, 97, 255, 3) == 100);
+    CHECK(spatial_sample(100, 97, -17, 3) == 99 && spatial_sample(250, 0, 255, 0) == 255 && spatial_sample(5, 255, 255, 0) == 0);
+    // the masks on heap blocks of exactly the frames' bytes
+    const int w = 130, h = 66, nf = 3;
+    const std::vector<std::vector<h264mi_privacy>> lists = {
+        {{0, 2, 4, 126, 58, 0, 4, 0, 0, 0}},
+        {{1, 0, 0, 130, 66, 0, 64, 0, 0, 0}, {2, 0, 0, 130, 66, 0, 4, 0, 0, 0}, {0, 128, 64, 2, 2, 0, 4, 0, 0, 0}},
+        {{0, 0, 0, 64, 32, 0, 8, 0, 0, 0}, {0, 64, 32, 66, 34, 0, 32, 0, 0, 0}, {1, 32, 16, 16, 16, 0, 16, 0, 0, 0}, {2, 6, 2, 100, 50, 1, 0, 17, 200, 90},
+         {1, 100, 40, 30, 26, 1, 0, 0, 255, 128}},
+    };
+    int nlists = 0;
+    for (const auto &list : lists) {
+        const size_t nb = nf * i420_bytes(w, h);
+        std::unique_ptr<uint8_t[]> fr(new uint8_t[nb]);
+        std::unique_ptr<h264mi_privacy[]> hl(new h264mi_privacy[list.size()]);  // exactly the entries
+        for (size_t k = 0; k < list.size(); k++) hl[k] = list[k];
+        std::vector<uint8_t> want(nb);
+        for (size_t i = 0; i < nb; i++) want[i] = fr[i] = (uint8_t)pix_rng();
+        CHECK(privacy_ok(hl.get(), (int)list.size(), w, h, nf));
+        ref_privacy(want, w, h, nf, list);
+        privacy_frames_host(fr.get(), w, h, hl.get(), (int)list.size());
+        CHECK(memcmp(fr.get(), want.data(), nb) == 0);
+        nlists++;
+    }
+    // the scalar checks at their limits and one past each
+    const h264mi_spatial lo{0, 0, -64, -64, 0}, hi{3, 3, 255, 255, 255};
+    CHECK(spatial_ok(&lo) && spatial_ok(&hi) && !spatial_ok(nullptr));
+    for (int f = 0; f < 5; f++) {
+        h264mi_spatial a = lo, b = hi;
+        ((int32_t *)&a)[f]--; ((int32_t *)&b)[f]++;
+        CHECK(!spatial_ok(&a) && !spatial_ok(&b));
+        a = lo; ((int32_t *)&a)[f] = INT32_MIN; b = hi; ((int32_t *)&b)[f] = INT32_MAX;
+        CHECK(!spatial_ok(&a) && !spatial_ok(&b));
+    }
+    const uintptr_t D = 0x10000000u, S = 0x20000000u;
+    auto ok = [&](uintptr_t d, uintptr_t s, int ww, int hh, int n, const h264mi_spatial *par) {
+        return spatial_args_ok((const void *)d, (const void *)s, ww, hh, n, par);
+    };
+    const size_t nb = 3 * i420_bytes(32, 16);
+    CHECK(ok(D, S, 32, 16, 3, &hi) && ok(D, S, 8192, 8192, 1, &lo) && ok(D, S, 2, 2, 1, &lo) && ok(D, D + nb, 32, 16, 3, &hi) && ok(D, D - nb, 32, 16, 3, &hi));
+    CHECK(!ok(0, S, 32, 16, 3, &hi) && !ok(D, 0, 32, 16, 3, &hi) && !ok(D, S, 32, 16, 3, nullptr) && !ok(D, S, 32, 16, 0, &hi) && !ok(D, S, 32, 16, -1, &hi));
+    CHECK(!ok(D, S, 31, 16, 3, &hi) && !ok(D, S, 32, 15, 3, &hi) && !ok(D, S, 0, 16, 3, &hi) && !ok(D, S, 8194, 16, 3, &hi) && !ok(D, S, 32, 8194, 3, &hi));
+    for (uintptr_t off : {(uintptr_t)0, (uintptr_t)1, (uintptr_t)(nb - 1), (uintptr_t)-1, (uintptr_t)-(intptr_t)(nb - 1)}) CHECK(!ok(D, D + off, 32, 16, 3, &hi));
+    auto one = [&](h264mi_privacy m, int ww = 32, int hh = 16, int nfr = 2) {
+        std::unique_ptr<h264mi_privacy[]> q(new h264mi_privacy[1]);
+        q[0] = m;
+        return privacy_ok(q.get(), 1, ww, hh, nfr);
+    };
+    const h264mi_privacy g{1, 28, 12, 4, 4, 0, 4, 0, 0, 0}, fl{0, 0, 0, 32, 16, 1, 0, 255, 255, 255};
+    CHECK(one(g) && one(fl) && one({0, 30, 14, 2, 2, 0, 64, -9, 999, 0}) && one({0, 0, 0, 2, 2, 1, 77, 0, 0, 0}));
+    CHECK(!one(g, 32, 16, 1) && !one(g, 31, 16) && !one(g, 32, 8194) && !one(g, 30, 16) && !one(g, 32, 14) && !one(g, 32, 16, 0));
+    for (int f = 0; f < 5; f++) {  // frame, x, y, w, h: one below, one past, odd, and the extremes
+        h264mi_privacy a = g, b = g, c = g, d = g;
+        ((int32_t *)&a)[f] = f == 0 ? -1 : f < 3 ? -2 : 0;
+        ((int32_t *)&b)[f] += f == 0 ? 1 : 2;
+        ((int32_t *)&c)[f] = INT32_MAX - (f > 0);
+        ((int32_t *)&d)[f] = INT32_MIN;
+        CHECK(!one(a) && !one(b) && !one(c) && !one(d));
+        if (f > 0) { h264mi_privacy o = g; ((int32_t *)&o)[f]--; CHECK(!one(o)); }
+    }
+    for (int blk : {0, 2, 3, 5, 6, 12, 63, 65, 128, -4, INT32_MAX, INT32_MIN}) { h264mi_privacy a = g; a.block = blk; CHECK(!one(a)); }
+    for (int blk : {4, 8, 16, 32, 64}) { h264mi_privacy a = g; a.block = blk; CHECK(one(a)); }
+    for (int mode : {-1, 2, INT32_MAX, INT32_MIN}) { h264mi_privacy a = g; a.mode = mode; CHECK(!one(a)); }
+    for (int f = 7; f < 10; f++) {
+        h264mi_privacy a = fl, b = fl;
+        ((int32_t *)&a)[f] = 256; ((int32_t *)&b)[f] = -1;
+        CHECK(!one(a) && !one(b));
+    }
+    {   // two entries: touching, sharing one sample, the same rectangle on two frames; the counts
+        std::unique_ptr<h264mi_privacy[]> q(new h264mi_privacy[2]);
+        q[0] = {0, 0, 0, 16, 8, 0, 8, 0, 0, 0}; q[1] = {0, 16, 0, 16, 8, 1, 0, 1, 2, 3};
+        CHECK(privacy_ok(q.get(), 2, 32, 16, 2));
+        q[1].x = 14; CHECK(!privacy_ok(q.get(), 2, 32, 16, 2));
+        q[1].frame = 1; CHECK(privacy_ok(q.get(), 2, 32, 16, 2));
+        CHECK(!privacy_ok(q.get(), 0, 32, 16, 2) && !privacy_ok(q.get(), -1, 32, 16, 2) && !privacy_ok(nullptr, 2, 32, 16, 2));
+        std::unique_ptr<h264mi_privacy[]> many(new h264mi_privacy[PIC_MAX_LIST]);
+        for (int k = 0; k < PIC_MAX_LIST; k++) many[k] = {0, 2 * k, 0, 2, 2, 1, 0, 1, 2, 3};
+        CHECK(privacy_ok(many.get(), PIC_MAX_LIST, 8192, 2, 1) && !privacy_ok(many.get(), PIC_MAX_LIST + 1, 8192, 2, 1));
+    }
+    printf("spatial: %d frames at 7 sizes x 8 parameter sets, the weights and the sample rule; privacy: %d lists on 3 frames of 130x66; scalar, list and range checks\n",
+           frames, nlists);
+}
+
 int main() {
+    check_spatial();
     check_deinterlace();
     check_scenecut();
     check_denoise();
