@@ -2,20 +2,9 @@
 import os, subprocess, sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, 'csrc', 'h264mi_kernels.hip')
-SRC_QUALITY = os.path.join(HERE, 'csrc', 'quality.hip')  # its own code object (see the file)
-SRC_SCALE = os.path.join(HERE, 'csrc', 'scale.hip')  # likewise
-SRC_COMPOSE = os.path.join(HERE, 'csrc', 'compose.hip')  # likewise
-SRC_OVERLAY = os.path.join(HERE, 'csrc', 'overlay.hip')  # likewise
-SRC_UPSCALE = os.path.join(HERE, 'csrc', 'upscale.hip')  # likewise
-SRC_ORIENT = os.path.join(HERE, 'csrc', 'orient.hip')  # likewise
-SRC_PIXFMT = os.path.join(HERE, 'csrc', 'pixfmt.hip')  # likewise
-SRC_PIXDEEP = os.path.join(HERE, 'csrc', 'pixdeep.hip')  # likewise
-SRC_COLORSPACE = os.path.join(HERE, 'csrc', 'colorspace.hip')  # likewise
-SRC_DENOISE = os.path.join(HERE, 'csrc', 'denoise.hip')  # likewise
-SRC_SCENECUT = os.path.join(HERE, 'csrc', 'scenecut.hip')  # likewise
-SRC_DEINTERLACE = os.path.join(HERE, 'csrc', 'deinterlace.hip')  # likewise
-SRC_SPATIAL = os.path.join(HERE, 'csrc', 'spatial.hip')  # likewise
+# one code object each: the codec, then the picture units (see the files)
+UNITS = ('h264mi_kernels', 'quality', 'scale', 'compose', 'overlay', 'upscale', 'orient', 'pixfmt', 'pixdeep', 'colorspace', 'denoise',
+         'scenecut', 'deinterlace', 'spatial')
 OUT = os.path.join(HERE, 'lib', 'libh264mi.so')
 
 
@@ -26,8 +15,7 @@ def build(force=False, verbose=False):
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wno-unused-result',
-           '-Wno-pass-failed', '-o', OUT + '.tmp', SRC, SRC_QUALITY, SRC_SCALE, SRC_COMPOSE, SRC_OVERLAY, SRC_UPSCALE, SRC_ORIENT, SRC_PIXFMT, SRC_PIXDEEP,
-           SRC_COLORSPACE, SRC_DENOISE, SRC_SCENECUT, SRC_DEINTERLACE, SRC_SPATIAL]
+           '-Wno-pass-failed', '-o', OUT + '.tmp'] + [os.path.join(HERE, 'csrc', u + '.hip') for u in UNITS]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)

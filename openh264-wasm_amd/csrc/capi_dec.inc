@@ -254,7 +254,7 @@ int h264mi_dec_set_output_format(h264mi_decoder *d, int fmt) {
     return 0;
 }
 int h264mi_dec_output_format(h264mi_decoder *d) { return d ? (d->c->out_lay_set ? H264MI_FMT_LAYOUT : d->c->out_fmt) : -1; }
-// a layout instead of a format (DESIGN.md §5.10; pixfmt.hip dec_output_pix_kernel), checked here against the size the
+// a layout instead of a format (DESIGN.md §5.10; pix_rows.h dec_output_rows_kernel), checked here against the size the
 // decoder was created with; each call hands the layout in force to its read-out launches by value (dec_frames)
 int h264mi_dec_set_output_layout(h264mi_decoder *d, const h264mi_pix_layout *layout) {
     if (!d) return -1;

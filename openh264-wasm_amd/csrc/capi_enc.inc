@@ -377,17 +377,14 @@ int h264mi_pix_to_i420_opt_dev(void *d_i420, const void *d_src, const h264mi_pix
     if (!d_i420 || !d_src || (opt && !pixopt_ok(opt)) || !pix_args_ok(src, w, h, n) || !pix_base_ok(d_src, *src) ||
         pix_ranges_overlap(d_src, *src, d_i420, w, h, n))
         return -1;
-    if (pix_is_deep(src->pix))
-        return launch_pixdeep_to_i420((uint8_t *)d_i420, (const uint8_t *)d_src, *src, opt ? opt->depth : 0, w, h, n, (hipStream_t)hip_stream);
-    return launch_pix_to_i420((uint8_t *)d_i420, (const uint8_t *)d_src, *src, w, h, n, (hipStream_t)hip_stream);
+    return launch_layout_to_i420((uint8_t *)d_i420, (const uint8_t *)d_src, *src, opt ? opt->depth : 0, w, h, n, (hipStream_t)hip_stream);
 }
 int h264mi_pix_to_i420_dev(void *d_i420, const void *d_src, const h264mi_pix_layout *src, int w, int h, int n, void *hip_stream) {
     return h264mi_pix_to_i420_opt_dev(d_i420, d_src, src, nullptr, w, h, n, hip_stream);
 }
 int h264mi_i420_to_pix_dev(void *d_dst, const h264mi_pix_layout *dst, const void *d_i420, int w, int h, int n, void *hip_stream) {
     if (!d_dst || !d_i420 || !pix_args_ok(dst, w, h, n) || !pix_base_ok(d_dst, *dst) || pix_ranges_overlap(d_dst, *dst, d_i420, w, h, n)) return -1;
-    if (pix_is_deep(dst->pix)) return launch_i420_to_pixdeep((uint8_t *)d_dst, *dst, (const uint8_t *)d_i420, w, h, n, (hipStream_t)hip_stream);
-    return launch_i420_to_pix((uint8_t *)d_dst, *dst, (const uint8_t *)d_i420, w, h, n, (hipStream_t)hip_stream);
+    return launch_i420_to_layout((uint8_t *)d_dst, *dst, (const uint8_t *)d_i420, w, h, n, (hipStream_t)hip_stream);
 }
 // nstreams frames of the encoder's size in *layout: one batched launch into the encoder's own input area on its stream,
 // then the frame step as h264mi_enc_encode runs it. Every refusal comes before the first launch
@@ -397,10 +394,7 @@ int h264mi_enc_encode_pix(h264mi_encoder *e, const void *d_frames, const h264mi_
     if (!pix_args_ok(layout, c->w, c->h, c->S) || !pix_base_ok(d_frames, *layout) ||
         pix_ranges_overlap(d_frames, *layout, c->d_src, c->w, c->h, c->S))
         return -1;
-    const int r = pix_is_deep(layout->pix)
-                      ? launch_pixdeep_to_i420(c->d_src, (const uint8_t *)d_frames, *layout, c->pixopt.depth, c->w, c->h, c->S, c->stream)
-                      : launch_pix_to_i420(c->d_src, (const uint8_t *)d_frames, *layout, c->w, c->h, c->S, c->stream);
-    if (r != 0) return -1;
+    if (launch_layout_to_i420(c->d_src, (const uint8_t *)d_frames, *layout, c->pixopt.depth, c->w, c->h, c->S, c->stream) != 0) return -1;
     return enc_code_input(c);
 }
 // the depth rule the next h264mi_enc_encode_pix converts under; a refused one leaves the previous in force

@@ -46,25 +46,24 @@
 #include "../../include/h264mi.h"
 #include "h264mi_types.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define CDEV __device__ __forceinline__
-
 #define H264MI_CS_MAX_FRAMES_Y 256  // frames on blockIdx.y; further frames are a stride loop
 
-CDEV int cs_clamp8(int v) { return min(max(v, 0), 255); }
-CDEV uint32_t cs_pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return a | (b << 8) | (c << 16) | (d << 24); }
-CDEV int cs_byte(uint32_t v, int k) { return (int)((v >> (8 * k)) & 255); }
-CDEV int cs_dot(const int32_t *f, int r, int g, int b) { return __mul24(f[0], r) + __mul24(f[1], g) + __mul24(f[2], b); }
+PICDEV int cs_clamp8(int v) { return min(max(v, 0), 255); }
+PICDEV uint32_t cs_pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return a | (b << 8) | (c << 16) | (d << 24); }
+PICDEV int cs_byte(uint32_t v, int k) { return (int)((v >> (8 * k)) & 255); }
+PICDEV int cs_dot(const int32_t *f, int r, int g, int b) { return __mul24(f[0], r) + __mul24(f[1], g) + __mul24(f[2], b); }
 
 // ---- RGBA -> 4:2:0
 // One RGBA pixel (R | G << 8 | B << 16 | A << 24) to Y
-CDEV uint32_t cs_y(const CsCoef &k, uint32_t p) {
+PICDEV uint32_t cs_y(const CsCoef &k, uint32_t p) {
     return (uint32_t)cs_clamp8(((cs_dot(k.fy, cs_byte(p, 0), cs_byte(p, 1), cs_byte(p, 2)) + 128) >> 8) + k.yo);
 }
 // The 2x2 block p00 p01 / p10 p11 to Cb (f = k.fu) or Cr (k.fv): of p00, or of the sum of the four
 template <bool AVG>
-CDEV uint32_t cs_c(const int32_t *f, uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11) {
+PICDEV uint32_t cs_c(const int32_t *f, uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11) {
     if (AVG) {
         const int r = cs_byte(p00, 0) + cs_byte(p01, 0) + cs_byte(p10, 0) + cs_byte(p11, 0);
         const int g = cs_byte(p00, 1) + cs_byte(p01, 1) + cs_byte(p10, 1) + cs_byte(p11, 1);
@@ -76,7 +75,7 @@ CDEV uint32_t cs_c(const int32_t *f, uint32_t p00, uint32_t p01, uint32_t p10, u
 
 // A unit's 8 x 2 pixels p[row][i] to its bytes: y[row][i], a[row][i] (ALPHA), cb[j] and cr[j] of the 2x2 block j
 template <bool AVG, bool ALPHA>
-CDEV void cs_in_unit(const CsCoef &k, const uint32_t (&p)[2][8], uint32_t (&y)[2][8], uint32_t (&a)[2][8], uint32_t (&cb)[4], uint32_t (&cr)[4]) {
+PICDEV void cs_in_unit(const CsCoef &k, const uint32_t (&p)[2][8], uint32_t (&y)[2][8], uint32_t (&a)[2][8], uint32_t (&cb)[4], uint32_t (&cr)[4]) {
 #pragma unroll
     for (int r = 0; r < 2; r++)
 #pragma unroll
@@ -149,16 +148,16 @@ __global__ __launch_bounds__(256) void rgba_to_i420_cs_kernel(CsInLaunch a) {
 // ---- 4:2:0 -> RGBA
 // Saturate before the shift, as color.inc's sat_shr8 and for its reason: the shift-then-saturate form matches
 // v_ashr_pk_u8_i32, whose untouched upper half hipcc then takes for zero (toolchain notes)
-CDEV uint32_t cs_sat_shr8(int x) { return (uint32_t)min(max(x, 0), 65535) >> 8; }
+PICDEV uint32_t cs_sat_shr8(int x) { return (uint32_t)min(max(x, 0), 65535) >> 8; }
 // One pixel from its samples Y, Cb, Cr (0..255). The header's c + RV cr + 128 with c = IY (Y - yo), cr = Cr - 128 is
 // IY Y + RV Cr + (128 - IY yo - 128 RV): the same integer, with the constant part (k.kr, kg, kb: cs_out_coef) formed once
 // on the scalar unit. Written chroma first, so that pixels which share a chroma pair (REPEAT) share those terms too
 struct CsOut { int iy, rv, gu, gv, bu, kr, kg, kb; };
-CDEV CsOut cs_out_coef(const CsCoef &k) {
+PICDEV CsOut cs_out_coef(const CsCoef &k) {
     const int c = 128 - k.iy * k.yo;
     return CsOut{k.iy, k.rv, k.gu, k.gv, k.bu, c - 128 * k.rv, c + 128 * (k.gu + k.gv), c - 128 * k.bu};
 }
-CDEV uint32_t cs_px(const CsOut &k, int y, int cb, int cr) {
+PICDEV uint32_t cs_px(const CsOut &k, int y, int cb, int cr) {
     const int tr = __mul24(k.rv, cr) + k.kr, tg = k.kg - __mul24(k.gu, cb) - __mul24(k.gv, cr), tb = __mul24(k.bu, cb) + k.kb;
     return cs_sat_shr8(__mul24(k.iy, y) + tr) | (cs_sat_shr8(__mul24(k.iy, y) + tg) << 8) | (cs_sat_shr8(__mul24(k.iy, y) + tb) << 16) |
            0xff000000u;
@@ -168,7 +167,7 @@ CDEV uint32_t cs_px(const CsOut &k, int y, int cb, int cr) {
 // m[j], t[j], b[j] = columns c0 - 1 + j (clamped to the picture) of the chroma rows cy, cy - 1 and cy + 1 (clamped).
 // REPEAT reads m[1..4] only
 template <bool BIL>
-CDEV void cs_out_chroma(const int (&m)[6], const int (&t)[6], const int (&b)[6], int (&o)[2][8]) {
+PICDEV void cs_out_chroma(const int (&m)[6], const int (&t)[6], const int (&b)[6], int (&o)[2][8]) {
     if (!BIL) {
 #pragma unroll
         for (int i = 0; i < 8; i++) o[0][i] = o[1][i] = m[1 + (i >> 1)];
@@ -193,7 +192,7 @@ CDEV void cs_out_chroma(const int (&m)[6], const int (&t)[6], const int (&b)[6],
 
 // 6 samples of the chroma row at `row` (cw samples) around columns c0 .. c0 + 3: c0 - 1 + j clamped to 0 .. cw - 1
 template <bool VEC>
-CDEV void cs_row6(const uint8_t *row, int c0, int cw, int (&o)[6]) {
+PICDEV void cs_row6(const uint8_t *row, int c0, int cw, int (&o)[6]) {
     if (VEC) {  // c0 + 3 < cw and row + c0 is 4-byte aligned
         const uint32_t d = *(const uint32_t *)(row + c0);
         o[0] = row[max(c0 - 1, 0)];
@@ -211,7 +210,7 @@ struct CsPic { const uint8_t *Y, *U, *V; int ys, uvs, w, h; uint8_t *rgba; };
 // Unit u of a picture. VEC: the wide accesses; else 4-byte RGBA pixels and plane bytes, ending at the row's end. The
 // arithmetic between the loads and the stores is the same code on the same values
 template <bool BIL, bool VEC>
-CDEV void cs_out_unit(const CsOut &k, const CsPic &p, int u) {
+PICDEV void cs_out_unit(const CsOut &k, const CsPic &p, int u) {
     const int cw = p.w >> 1, ch = p.h >> 1, upr = (p.w + 7) >> 3;
     const int by = u / upr, x = (u - by * upr) * 8, c0 = x >> 1;
     const int np = VEC ? 8 : min(8, p.w - x);
@@ -264,7 +263,7 @@ CDEV void cs_out_unit(const CsOut &k, const CsPic &p, int u) {
 // of the picture. Shared by the batched kernel and the decoder's read-out. Chroma indices clamp to w/2 x h/2. The path
 // is chosen once a picture, outside the loop: inside it the compiler would weave the two into one body
 template <bool BIL>
-CDEV void i420_to_rgba_cs_picture(const CsOut &k, const uint8_t *__restrict__ Y, const uint8_t *__restrict__ U, const uint8_t *__restrict__ V,
+PICDEV void i420_to_rgba_cs_picture(const CsOut &k, const uint8_t *__restrict__ Y, const uint8_t *__restrict__ U, const uint8_t *__restrict__ V,
                                   int ys, int uvs, int w, int h, uint8_t *__restrict__ rgba, int u0, int ustep) {
     const int units = ((w + 7) >> 3) * (h >> 1);
     const CsPic p{Y, U, V, ys, uvs, w, h, rgba};

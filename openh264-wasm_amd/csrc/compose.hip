@@ -6,8 +6,8 @@
 // A cell takes a crop of one source frame to a rectangle of one canvas. Per plane that is §5.3's area average with
 // pw x ph = the crop's size in the plane and qw x qh = the rectangle's (scale.hip's header has the formula): exact
 // unsigned 32-bit integers for pw, ph <= 4096, the same bytes whatever the order of evaluation.
-// The walk is scale_kernel's: a wave owns a strip of 64 output columns and a segment of H264MI_COMPOSE_ROWS output rows
-// of one plane of one cell and walks the overlapping source rows downward, H264MI_COMPOSE_BATCH rows at a time, a lane
+// The walk is scale_kernel's, picture_dev.h's area_average: a wave owns a strip of 64 output columns and a segment of PIC_AREA_ROWS output rows
+// of one plane of one cell and walks the overlapping source rows downward, PIC_AREA_BATCH rows at a time, a lane
 // per output column. What differs:
 //  * geometry is per cell. The launch's arguments hold the cells and a prefix table of waves per cell; a wave finds its
 //    cell by a binary search of that table (all of it scalar), then plane, strip and segment as the scaler does.
@@ -22,20 +22,16 @@
 //    lie inside the rectangle; everything else as bytes. Nothing is written outside the rectangle, nothing is read
 //    outside the source frame.
 //
-// A translation unit and a code object of its own, as quality.hip and scale.hip are: the library's other kernels stay
-// byte for byte what they were. The host runtime (capi_enc.inc) reaches it through the functions picture_host.h declares;
+// A translation unit and a code object of its own, as quality.hip and scale.hip are. The host runtime (capi_enc.inc) reaches it through the functions picture_host.h declares;
 // the checks of a cell list and the cell table of a launch are there too.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define CDEV __device__ __forceinline__
-
-#define H264MI_COMPOSE_ROWS 16          // output rows per wave
-#define H264MI_COMPOSE_BATCH 8          // source rows whose loads are in flight together
 #define H264MI_COMPOSE_CELLS 64         // cells per launch: the argument block is 1.9 KB
 
 typedef PictureCell ComposeCell;  // a cell as the kernel reads it, 24 bytes (picture_host.h)
@@ -50,49 +46,6 @@ struct ComposeLaunch {
 };
 static_assert(sizeof(ComposeLaunch) < 2048, "the argument block stays well below 4 KB");
 
-// the horizontal sums of one output column on H264MI_COMPOSE_BATCH source plane rows: wf p[i0] + qw (p[i0+1] + .. +
-// p[i1-1]) + wl p[i1] each (wl = 0 when i1 == i0), i0 and i1 columns of the plane row, from byte loads. The rows' loads
-// of one tap are independent of each other and issued together.
-CDEV void compose_hsum_bytes(uint32_t *h, const uint8_t *S, const uint32_t *row, int i0, int i1, uint32_t wf, uint32_t wl, uint32_t qw) {
-    uint32_t mid[H264MI_COMPOSE_BATCH];
-#pragma unroll
-    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) mid[r] = 0;
-    for (int i = i0 + 1; i < i1; i++) {
-#pragma unroll
-        for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) mid[r] += S[row[r] + i];
-    }
-#pragma unroll
-    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) h[r] = wf * S[row[r] + i0] + qw * mid[r] + wl * S[row[r] + i1];
-}
-// the same from the aligned dwords i0 / 4 .. i1 / 4 of plane rows that start at a multiple of 4 and are a multiple of
-// 4 long: the taps between the first and the last are summed by v_sad_u8 under a byte mask, which the rows share.
-// Bytes of those dwords below i0 or above i1 (outside the crop, inside the row) are under no mask and in no shift.
-CDEV void compose_hsum_dwords(uint32_t *h, const uint8_t *S, const uint32_t *row, int i0, int i1, uint32_t wf, uint32_t wl, uint32_t qw) {
-    const int d0 = i0 >> 2, d1 = i1 >> 2;
-    uint32_t mid[H264MI_COMPOSE_BATCH], first[H264MI_COMPOSE_BATCH], last[H264MI_COMPOSE_BATCH];
-#pragma unroll
-    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) mid[r] = first[r] = last[r] = 0;
-    for (int d = d0; d <= d1; d++) {
-        uint32_t v[H264MI_COMPOSE_BATCH];
-#pragma unroll
-        for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) v[r] = *(const uint32_t *)(S + row[r] + 4 * d);
-        const int lo = max(i0 + 1 - 4 * d, 0), hi = min(i1 - 1 - 4 * d, 3);  // the dword's bytes between the end taps
-        const uint32_t m = lo <= hi ? (0xffffffffu >> (8 * (3 - hi))) & (0xffffffffu << (8 * lo)) : 0u;
-#pragma unroll
-        for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) {
-            mid[r] = __builtin_amdgcn_sad_u8(v[r] & m, 0u, mid[r]);
-            if (d == d0) first[r] = (v[r] >> (8 * (i0 & 3))) & 255u;
-            if (d == d1) last[r] = (v[r] >> (8 * (i1 & 3))) & 255u;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) h[r] = wf * first[r] + qw * mid[r] + wl * last[r];
-}
-
-// waves across and down a qw x qh rectangle of one plane
-__host__ __device__ static inline int compose_nstrip(int qw) { return (qw + 63) / 64; }
-__host__ __device__ static inline int compose_nseg(int qh) { return (qh + H264MI_COMPOSE_ROWS - 1) / H264MI_COMPOSE_ROWS; }
-
 __global__ __launch_bounds__(256) void compose_kernel(ComposeLaunch a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // scalar: what follows from it is per wave
@@ -105,7 +58,7 @@ __global__ __launch_bounds__(256) void compose_kernel(ComposeLaunch a) {
         }
         const ComposeCell c = a.cell[lo_c];
         int k = it - a.first[lo_c];  // the wave's index within the cell
-        const int lw = compose_nstrip(c.dw) * compose_nseg(c.dh), cwv = compose_nstrip(c.dw >> 1) * compose_nseg(c.dh >> 1);
+        const int lw = area_nstrip(c.dw) * area_nseg(c.dh), cwv = area_nstrip(c.dw >> 1) * area_nseg(c.dh >> 1);
         int p = 0;
         if (k >= lw) { k -= lw; p = 1; if (k >= cwv) { k -= cwv; p = 2; } }
         const int sh1 = p != 0;  // chroma: every size and origin halved
@@ -120,63 +73,8 @@ __global__ __launch_bounds__(256) void compose_kernel(ComposeLaunch a) {
                      (c.dx >> sh1);
         const int x0 = c.sx >> sh1;
         const bool wide = ((((uintptr_t)P) | (uintptr_t)spitch) & 3) == 0;
-        const int nstrip = compose_nstrip(qw);
-        const int strip = k % nstrip, seg = k / nstrip;
-        const int ox = strip * 64 + lane;
-        const bool act = ox < qw;
-        // the lane's taps: columns i0..i1 of the plane row, weights wf, qw, .., qw, wl
-        int i0 = x0, i1 = x0;
-        uint32_t wf = 0, wl = 0;
-        if (act) {
-            const int lo = ox * pw, hi = lo + pw;  // the output column in units of 1 / (pw qw)
-            const int t0 = lo / qw, t1 = (hi + qw - 1) / qw - 1;
-            wf = (uint32_t)(min((t0 + 1) * qw, hi) - lo);
-            wl = t1 > t0 ? (uint32_t)(hi - t1 * qw) : 0u;
-            i0 = x0 + t0;
-            i1 = x0 + t1;
-        }
-        const uint32_t area = (uint32_t)pw * (uint32_t)ph, half = area >> 1;
-        const int oy0 = seg * H264MI_COMPOSE_ROWS, oy1 = min(oy0 + H264MI_COMPOSE_ROWS, qh);
-        const int y0 = (oy0 * ph) / qh, y1 = (oy1 * ph + qh - 1) / qh - 1;  // crop rows y0..y1
-        int oy = oy0;
-        uint32_t acc = 0;
-        for (int yb0 = y0; yb0 <= y1; yb0 += H264MI_COMPOSE_BATCH) {  // a batch of source rows: its loads, then the rows in order
-            uint32_t hs[H264MI_COMPOSE_BATCH];
-#pragma unroll
-            for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) hs[r] = 0;
-            if (act) {
-                uint32_t row[H264MI_COMPOSE_BATCH];  // byte offsets from S; rows beyond y1 read row y1 again and are not used
-#pragma unroll
-                for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) row[r] = (uint32_t)(min(yb0 + r, y1) * spitch);
-                if (wide) compose_hsum_dwords(hs, S, row, i0, i1, wf, wl, (uint32_t)qw);
-                else compose_hsum_bytes(hs, S, row, i0, i1, wf, wl, (uint32_t)qw);
-            }
-#pragma unroll
-            for (int r = 0; r < H264MI_COMPOSE_BATCH; r++) {
-            const int y = yb0 + r;
-            if (y > y1) break;
-            const uint32_t h = hs[r];
-            const int top = oy * ph, bot = top + ph, ya = y * qh, yb = ya + qh;  // the same in every lane
-            acc += (uint32_t)(min(yb, bot) - max(ya, top)) * h;
-            if (yb >= bot) {  // output row oy is complete
-                const uint32_t v = (acc + half) / area;
-                uint8_t *o = D + (size_t)oy * dpitch + strip * 64;  // the strip's first sample of the row
-                if (((uintptr_t)o & 3) == 0) {
-                    uint32_t q = v | (__shfl_down(v, 1) << 8);
-                    q |= __shfl_down(q, 2) << 16;  // lanes 4j: the bytes of lanes 4j .. 4j + 3
-                    if (act) {
-                        const int base = ox & ~3;
-                        if (base + 3 < qw) { if ((lane & 3) == 0) *(uint32_t *)(o + lane) = q; }
-                        else o[lane] = (uint8_t)v;
-                    }
-                } else if (act) {
-                    o[lane] = (uint8_t)v;
-                }
-                oy++;
-                acc = (uint32_t)(yb - bot) * h;  // the rest of a straddling row opens the next one
-            }
-            }
-        }
+        const int nstrip = area_nstrip(qw);
+        area_average(D, dpitch, S, spitch, wide, x0, pw, ph, qw, qh, k % nstrip, k / nstrip, lane);
     }
 }
 
@@ -232,7 +130,7 @@ int launch_fill_i420(uint8_t *dst, int w, int h, int n, int y, int cb, int cr, h
 }
 
 static int compose_cell_waves(int dw, int dh) {
-    return compose_nstrip(dw) * compose_nseg(dh) + 2 * compose_nstrip(dw / 2) * compose_nseg(dh / 2);
+    return area_nstrip(dw) * area_nseg(dh) + 2 * area_nstrip(dw / 2) * area_nseg(dh / 2);
 }
 // cells (as cells_ok accepts them without enlarging) into the canvases at dst, H264MI_COMPOSE_CELLS to a launch
 int launch_compose_i420(uint8_t *dst, int cw, int ch, const uint8_t *src, int src_w, int src_h, const h264mi_cell *cells, int ncells,

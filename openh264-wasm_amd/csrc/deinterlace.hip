@@ -43,10 +43,9 @@
 #include <string.h>
 #include "../../include/h264mi.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define NDEV __device__ __forceinline__
-
 #define H264MI_DEINT_STRIP 256  // samples across a strip
 #define H264MI_DEINT_ROWS 16    // rows of a row group: 8 line pairs
 
@@ -66,7 +65,7 @@ struct DeintLaunch {
 struct Seg { uint32_t lo, hi; };
 
 // the nb <= 8 bytes at p: one 8-byte word (nb == 8, p a multiple of 8) or bytes
-NDEV Seg load_seg(const uint8_t *p, int nb, bool wide) {
+PICDEV Seg load_seg(const uint8_t *p, int nb, bool wide) {
     Seg s{0, 0};
     if (wide) {
         const uint2 v = *(const uint2 *)p;
@@ -79,7 +78,7 @@ NDEV Seg load_seg(const uint8_t *p, int nb, bool wide) {
     }
     return s;
 }
-NDEV void store_seg(uint8_t *p, uint32_t lo, uint32_t hi, int nb, bool wide) {
+PICDEV void store_seg(uint8_t *p, uint32_t lo, uint32_t hi, int nb, bool wide) {
     if (wide) {
         *(uint2 *)p = make_uint2(lo, hi);
     } else {
@@ -87,7 +86,7 @@ NDEV void store_seg(uint8_t *p, uint32_t lo, uint32_t hi, int nb, bool wide) {
     }
 }
 // bytes nb .. 7 of a segment take the value of byte nb - 1 (the clamp at a row's end); returns that byte four times
-NDEV uint32_t fill_tail(Seg &s, int nb) {
+PICDEV uint32_t fill_tail(Seg &s, int nb) {
     const uint32_t rep = (((nb > 4 ? s.hi : s.lo) >> (8 * ((nb - 1) & 3))) & 255u) * 0x01010101u;
     if (nb < 4) {
         const uint32_t m = (1u << (8 * nb)) - 1u;
@@ -102,28 +101,23 @@ NDEV uint32_t fill_tail(Seg &s, int nb) {
     return rep;
 }
 // the two bytes in front of a segment at row[x0], x0 >= 8, in the upper half of a dword
-NDEV uint32_t load_left(const uint8_t *row, int x0, bool wide) {
+PICDEV uint32_t load_left(const uint8_t *row, int x0, bool wide) {
     if (wide) return *(const uint32_t *)(row + x0 - 4);
     return ((uint32_t)row[x0 - 2] << 16) | ((uint32_t)row[x0 - 1] << 24);
 }
 // the two bytes behind a segment, x0 + 8 < pw, clamped to the row, in the lower half of a dword
-NDEV uint32_t load_right(const uint8_t *row, int x0, int pw, bool wide) {
+PICDEV uint32_t load_right(const uint8_t *row, int x0, int pw, bool wide) {
     if (wide) return *(const uint32_t *)(row + x0 + 8);
     return (uint32_t)row[x0 + 8] | ((uint32_t)row[min(x0 + 9, pw - 1)] << 8);
 }
 // a window of 16 bytes: W[0] the dword in front of the segment, W[1], W[2] the segment, W[3] the dword behind it.
 // Three bytes from byte `pos` on (a constant after unrolling), the fourth masked; one byte
-NDEV uint32_t take3(const uint32_t (&W)[4], int pos) {
+PICDEV uint32_t take3(const uint32_t (&W)[4], int pos) {
     const int q = pos >> 2, o = pos & 3;
     const uint32_t v = o ? (W[q] >> (8 * o)) | (W[q + 1] << (32 - 8 * o)) : W[q];
     return v & 0x00FFFFFFu;
 }
-NDEV int byte_at(const uint32_t (&W)[4], int pos) { return (int)((W[pos >> 2] >> (8 * (pos & 3))) & 255u); }
-
-NDEV uint32_t deint_wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+PICDEV int byte_at(const uint32_t (&W)[4], int pos) { return (int)((W[pos >> 2] >> (8 * (pos & 3))) & 255u); }
 
 __global__ __launch_bounds__(256) void deinterlace_kernel(DeintLaunch a) {
     const int t = threadIdx.x, b = t & 31, lr = t >> 5;
@@ -143,14 +137,7 @@ __global__ __launch_bounds__(256) void deinterlace_kernel(DeintLaunch a) {
         const int sy = k / nsx, sx = k - sy * nsx;
         if (a.stats && f != sf) {
             if (sf >= 0) {
-                const uint32_t v0 = deint_wave_sum(s_miss), v1 = deint_wave_sum(s_comb), v2 = deint_wave_sum(s_y), v3 = deint_wave_sum(s_c);
-                if ((t & 63) == 0) {
-                    uint32_t *st = a.stats + 4 * sf;
-                    if (v0) atomicAdd(st + 0, v0);
-                    if (v1) atomicAdd(st + 1, v1);
-                    if (v2) atomicAdd(st + 2, v2);
-                    if (v3) atomicAdd(st + 3, v3);
-                }
+                wave_add_counters(a.stats + 4 * sf, t & 63, s_miss, s_comb, s_y, s_c);
             }
             sf = f; s_miss = s_comb = s_y = s_c = 0;
         }
@@ -258,14 +245,7 @@ __global__ __launch_bounds__(256) void deinterlace_kernel(DeintLaunch a) {
         }
     }
     if (a.stats && sf >= 0) {
-        const uint32_t v0 = deint_wave_sum(s_miss), v1 = deint_wave_sum(s_comb), v2 = deint_wave_sum(s_y), v3 = deint_wave_sum(s_c);
-        if ((t & 63) == 0) {
-            uint32_t *st = a.stats + 4 * sf;
-            if (v0) atomicAdd(st + 0, v0);
-            if (v1) atomicAdd(st + 1, v1);
-            if (v2) atomicAdd(st + 2, v2);
-            if (v3) atomicAdd(st + 3, v3);
-        }
+        wave_add_counters(a.stats + 4 * sf, t & 63, s_miss, s_comb, s_y, s_c);
     }
 }
 

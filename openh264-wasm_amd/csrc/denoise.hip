@@ -32,7 +32,8 @@
 // The double-buffered sad[] needs one barrier an item: item i + 2 writes the buffer of item i only after every thread
 // has passed the barrier of item i + 1, that is after its reads of item i.
 // Statistics (optional): {moving blocks, blocks, sum m luma, sum m chroma} per frame. A thread keeps the sums of the
-// frame it works on and adds them to memory (one atomic a wave and word) when the frame changes and at the end.
+// frame it works on and adds them to memory (one atomic a wave and word, picture_dev.h's wave_add_counters) when the
+// frame changes and at the end.
 //
 // A translation unit and a code object of its own, as orient.hip is: the library's other kernels stay byte for byte
 // what they were. The host runtime (enc_input.inc, capi_enc.inc) reaches it through the functions picture_host.h declares.
@@ -43,10 +44,9 @@
 #include <string.h>
 #include "../../include/h264mi.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define NDEV __device__ __forceinline__
-
 #define H264MI_DENOISE_STRIP 256  // luma samples across a strip
 
 struct DenoiseLaunch {
@@ -63,7 +63,7 @@ struct DenoiseLaunch {
 };
 
 // one dword of a static block: O from C and P, the sum of m added to *sum
-NDEV uint32_t denoise_dword(uint32_t c4, uint32_t p4, const uint8_t *mt, uint32_t *sum) {
+PICDEV uint32_t denoise_dword(uint32_t c4, uint32_t p4, const uint8_t *mt, uint32_t *sum) {
     if (c4 == p4) return c4;
     uint32_t o4 = 0;
 #pragma unroll
@@ -75,11 +75,6 @@ NDEV uint32_t denoise_dword(uint32_t c4, uint32_t p4, const uint8_t *mt, uint32_
         o4 |= (uint32_t)(d < 0 ? c + m : c - m) << (8 * j);
     }
     return o4;
-}
-
-NDEV uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 __global__ __launch_bounds__(256) void denoise_kernel(DenoiseLaunch a) {
@@ -107,14 +102,7 @@ __global__ __launch_bounds__(256) void denoise_kernel(DenoiseLaunch a) {
         const int sy = k / a.nsx, sx = k - sy * a.nsx;
         if (a.stats && f != sf) {
             if (sf >= 0) {
-                const uint32_t v0 = wave_sum(s_mov), v1 = wave_sum(s_blk), v2 = wave_sum(s_y), v3 = wave_sum(s_c);
-                if ((t & 63) == 0) {
-                    uint32_t *st = a.stats + 4 * sf;
-                    if (v0) atomicAdd(st + 0, v0);
-                    if (v1) atomicAdd(st + 1, v1);
-                    if (v2) atomicAdd(st + 2, v2);
-                    if (v3) atomicAdd(st + 3, v3);
-                }
+                wave_add_counters(a.stats + 4 * sf, t & 63, s_mov, s_blk, s_y, s_c);
             }
             sf = f; s_mov = s_blk = s_y = s_c = 0;
         }
@@ -193,14 +181,7 @@ __global__ __launch_bounds__(256) void denoise_kernel(DenoiseLaunch a) {
         }
     }
     if (a.stats && sf >= 0) {
-        const uint32_t v0 = wave_sum(s_mov), v1 = wave_sum(s_blk), v2 = wave_sum(s_y), v3 = wave_sum(s_c);
-        if ((t & 63) == 0) {
-            uint32_t *st = a.stats + 4 * sf;
-            if (v0) atomicAdd(st + 0, v0);
-            if (v1) atomicAdd(st + 1, v1);
-            if (v2) atomicAdd(st + 2, v2);
-            if (v3) atomicAdd(st + 3, v3);
-        }
+        wave_add_counters(a.stats + 4 * sf, t & 63, s_mov, s_blk, s_y, s_c);
     }
 }
 

@@ -51,10 +51,9 @@
 #include <string.h>
 #include "../../include/h264mi.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define ODEV __device__ __forceinline__
-
 #define H264MI_ORIENT_TILE 64        // tile kernel: samples each way
 #define H264MI_ORIENT_PITCH 18       // dwords between two slots of the LDS image
 #define H264MI_ORIENT_ROW_W 256      // rows kernel: samples across
@@ -74,7 +73,7 @@ struct OrientLaunch {
 
 // item `it` of a launch: its frame's plane pointers, the plane's geometry and the tile's index in the plane
 struct OrientItem { const uint8_t *S; uint8_t *D; OrientPlane g; int tx, ty; };
-ODEV OrientItem orient_item(const OrientLaunch &a, long long it) {
+PICDEV OrientItem orient_item(const OrientLaunch &a, long long it) {
     const long long f = it / a.ntiles;
     int k = (int)(it - f * a.ntiles);
     const int lt = a.pl[0].ntx * a.pl[0].nty, ct = a.pl[1].ntx * a.pl[1].nty;
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(256) void orient_rows_kernel(OrientLaunch a) {
 
 // r[a] holds the samples (row a, columns 0..3) of a 4 x 4 block, column j in byte j; afterwards r[b] holds
 // (column b, rows 0..3), row a in byte a. v_perm_b32: selector bytes 0..3 take the second operand's bytes, 4..7 the first's
-ODEV void transpose_4x4_bytes(uint32_t *r) {
+PICDEV void transpose_4x4_bytes(uint32_t *r) {
     const uint32_t lo01 = __builtin_amdgcn_perm(r[1], r[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(r[1], r[0], 0x07030602u);
     const uint32_t lo23 = __builtin_amdgcn_perm(r[3], r[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(r[3], r[2], 0x07030602u);
     r[0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);

@@ -22,24 +22,22 @@
 //  * a row segment is read as dwords when its first address is a multiple of 4 -- tested per row and per pointer,
 //    since with odd pitches (a 19-byte chroma pitch) it changes from row to row -- and then only the groups of four
 //    samples that lie inside the segment; everything else as bytes. Stores likewise (compose's rule: only groups wholly
-//    inside the rectangle). Nothing is read outside the crop, nothing is read or written outside the rectangle.
+//    inside the rectangle; picture_dev.h's seg_pack and seg_store, apart because a chroma row's pointer differs by lane). Nothing is read outside the crop, nothing is read or written outside the rectangle.
 // Order: placements may overlap and the last one is on top. The host cuts the list into launches so that no two
 // placements of one launch share a sample of one canvas (overlay_launch_end); launches go to the stream in list
 // order, so stream order is z-order and the waves of one launch never touch the same byte. No atomics, no device
 // allocation, no copies.
 //
-// A translation unit and a code object of its own, as quality.hip, scale.hip and compose.hip are: the library's other
-// kernels stay byte for byte what they were. The host runtime (enc_input.inc, capi_enc.inc) reaches it through the functions
+// A translation unit and a code object of its own, as quality.hip, scale.hip and compose.hip are. The host runtime (enc_input.inc, capi_enc.inc) reaches it through the functions
 // picture_host.h declares.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define ODEV __device__ __forceinline__
-
 #define H264MI_OVERLAY_ROWS 16          // luma rows per wave
 
 struct OverlayItem {  // a placement as the kernel reads it, 24 bytes
@@ -58,15 +56,15 @@ struct OverlayLaunch {
 static_assert(sizeof(OverlayLaunch) < 2048, "the argument block stays well below 4 KB");
 
 // (x + 127) / 255 for x in 0..65025
-ODEV uint32_t div255(uint32_t x) {
+PICDEV uint32_t div255(uint32_t x) {
     const uint32_t t = x + 128;
     return (t + (t >> 8)) >> 8;
 }
-ODEV uint32_t blend(uint32_t d, uint32_t s, uint32_t a) { return div255(d * (255u - a) + s * a); }
+PICDEV uint32_t blend(uint32_t d, uint32_t s, uint32_t a) { return div255(d * (255u - a) + s * a); }
 
 // sample i of the n-sample row segment at p (0 for i >= n): from the aligned dword that holds it when the segment
 // starts at a multiple of 4 and the dword lies inside the segment, else a byte
-ODEV uint32_t seg_load(const uint8_t *p, int i, int n) {
+PICDEV uint32_t seg_load(const uint8_t *p, int i, int n) {
     uint32_t v = 0;
     if (i < n) {
         if ((((uintptr_t)p) & 3) == 0 && (i | 3) < n) v = (*(const uint32_t *)(p + (i & ~3)) >> (8 * (i & 3))) & 255u;
@@ -74,19 +72,6 @@ ODEV uint32_t seg_load(const uint8_t *p, int i, int n) {
     }
     return v;
 }
-// the other way. q: in lanes whose i is a multiple of 4, the samples of i .. i + 3 (seg_pack, which every lane runs)
-ODEV uint32_t seg_pack(uint32_t v) {
-    uint32_t q = v | (__shfl_down(v, 1) << 8);
-    q |= __shfl_down(q, 2) << 16;
-    return q;
-}
-ODEV void seg_store(uint8_t *p, int i, int n, uint32_t v, uint32_t q) {
-    if (i < n) {
-        if ((((uintptr_t)p) & 3) == 0 && (i | 3) < n) { if ((i & 3) == 0) *(uint32_t *)(p + i) = q; }
-        else p[i] = (uint8_t)v;
-    }
-}
-
 // waves across and down a w x h placement
 __host__ __device__ static inline int overlay_nstrip(int w) { return (w + 63) / 64; }
 __host__ __device__ static inline int overlay_nseg(int h) { return (h + H264MI_OVERLAY_ROWS - 1) / H264MI_OVERLAY_ROWS; }
@@ -147,19 +132,19 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayLaunch a) {
 }
 
 // One RGBA pixel (R | G << 8 | B << 16 | A << 24) to Y, Cb, Cr: the wrapper's formulas, as color.inc has them
-ODEV uint32_t o_rgb_y(uint32_t p) {
+PICDEV uint32_t o_rgb_y(uint32_t p) {
     const int r = p & 255, g = (p >> 8) & 255, b = (p >> 16) & 255;
     return (uint8_t)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16);
 }
-ODEV uint32_t o_rgb_u(uint32_t p) {
+PICDEV uint32_t o_rgb_u(uint32_t p) {
     const int r = p & 255, g = (p >> 8) & 255, b = (p >> 16) & 255;
     return (uint8_t)((uint8_t)((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128);
 }
-ODEV uint32_t o_rgb_v(uint32_t p) {
+PICDEV uint32_t o_rgb_v(uint32_t p) {
     const int r = p & 255, g = (p >> 8) & 255, b = (p >> 16) & 255;
     return (uint8_t)((uint8_t)((112 * r - 94 * g - 18 * b + 128) >> 8) + 128);
 }
-ODEV uint32_t o_pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return a | (b << 8) | (c << 16) | (d << 24); }
+PICDEV uint32_t o_pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return a | (b << 8) | (c << 16) | (d << 24); }
 
 // n tight RGBA frames (4-byte aligned) -> n tight I420A sprites at any alignment. blockIdx.y strides the frames; a
 // thread owns a unit of 4 pixels on 2 rows (2 pixels where w % 4 == 2 ends the row): one 16-byte RGBA access a row

@@ -456,7 +456,7 @@ int launch_spatial_i420(uint8_t *dst, const uint8_t *src, int w, int h, int n, c
 void spatial_frame_host(uint8_t *out, const uint8_t *src, int w, int h, const h264mi_spatial &p);
 int launch_privacy_i420(uint8_t *frames, int w, int h, const h264mi_privacy *list, int nlist, hipStream_t s);
 void privacy_frames_host(uint8_t *frames, int w, int h, const h264mi_privacy *list, int nlist);
-// pixfmt.hip
+// pixfmt.hip, pixdeep.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);
 int launch_pixdeep_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int depth, int w, int h, int n, hipStream_t s);
@@ -465,6 +465,18 @@ int launch_dec_output_pixdeep(int S, int cw, int ch, int w, int h, const DecDesc
                               hipStream_t s);
 int launch_dec_output_pix(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in, const h264mi_pix_layout &L,
                           hipStream_t s);
+// the two together: pixdeep.hip for its formats, pixfmt.hip (which reads no depth rule) for the others
+static inline int launch_layout_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int depth, int w, int h, int n,
+                                        hipStream_t s) {
+    return pix_is_deep(L.pix) ? launch_pixdeep_to_i420(d_i420, d_src, L, depth, w, h, n, s) : launch_pix_to_i420(d_i420, d_src, L, w, h, n, s);
+}
+static inline int launch_i420_to_layout(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s) {
+    return pix_is_deep(L.pix) ? launch_i420_to_pixdeep(d_dst, L, d_i420, w, h, n, s) : launch_i420_to_pix(d_dst, L, d_i420, w, h, n, s);
+}
+static inline int launch_dec_output_layout(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in,
+                                           const h264mi_pix_layout &L, hipStream_t s) {
+    return pix_is_deep(L.pix) ? launch_dec_output_pixdeep(S, cw, ch, w, h, desc, in, L, s) : launch_dec_output_pix(S, cw, ch, w, h, desc, in, L, s);
+}
 // colorspace.hip: a good specification, even sides within PIC_MAX_SIDE; alpha: I420A sprites out (A = the fourth byte)
 int launch_rgba_to_i420_cs(uint8_t *d_out, const uint8_t *d_rgba, int w, int h, int n, const h264mi_colorspec &spec, bool alpha, hipStream_t s);
 int launch_i420_to_rgba_cs(uint8_t *d_rgba, const uint8_t *d_i420, int w, int h, int n, const h264mi_colorspec &spec, hipStream_t s);

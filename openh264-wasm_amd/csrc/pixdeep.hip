@@ -1,10 +1,12 @@
 // pixdeep.hip -- the deeper and wider pixel layouts to and from tight I420 on the device (gfx950): I422, I444, NV16, Y800,
 // P010, I010, P210, I210 and V210 (ids 16..24), as include/h264mi.h (h264mi_pix_layout, h264mi_pixopt) defines them.
-// DESIGN.md §5.17. The five formats of pixfmt.hip stay there, in their own code object, byte for byte.
-//   pixdeep_kernel<false>     : n frames in a layout -> n tight I420 frames (h264mi_pix_to_i420_opt_dev, h264mi_enc_encode_pix)
-//   pixdeep_kernel<true>      : n tight I420 frames -> n frames in a layout (h264mi_i420_to_pix_dev)
-//   dec_output_pixdeep_kernel : the batch decoder's per-frame read-out into a layout, as pixfmt.hip's dec_output_pix_kernel
-// One definition for all three (deep_row_pair). The work split is §5.10's: a wave owns a row pair (luma rows 2r, 2r + 1,
+// DESIGN.md §5.17. The five formats of pixfmt.hip stay there, in their own code object.
+//   pix_rows_kernel<deep_row_pair<false>>       : n frames in a layout -> n tight I420 frames (h264mi_pix_to_i420_opt_dev,
+//                                                 h264mi_enc_encode_pix)
+//   pix_rows_kernel<deep_row_pair<true>>        : n tight I420 frames -> n frames in a layout (h264mi_i420_to_pix_dev)
+//   dec_output_rows_kernel<deep_row_pair<true>> : the batch decoder's per-frame read-out into a layout
+// The kernels, their launchers, the frame, the 8-bit row move and byte average are pix_rows.h's, shared with pixfmt.hip;
+// this file owns the row functions of its nine formats. One definition for all three kernels (deep_row_pair). The work split is §5.10's: a wave owns a row pair (luma rows 2r, 2r + 1,
 // I420 chroma row r, and whatever rows of the layout hold them), a block of four waves a strip, blocks stride over
 // (frame, strip); inside a row the lanes take consecutive pieces and loop.
 //
@@ -35,95 +37,49 @@
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
-#include "h264mi_types.h"
-#include "picture_host.h"
+#include "pix_rows.h"
 
 namespace h264mi {
-#define DDEV __device__ __forceinline__
-
-#define H264MI_DEEP_STRIP 4   // row pairs per block, one per wave
-
-// v_perm_b32 selectors: bytes 0..3 name the second operand's bytes, 4..7 the first's, 0x0c is the constant 0
-#define DEEP_SEL_ZIP_LO 0x05010400u    // (hi, lo) -> lo.0 hi.0 lo.1 hi.1
-#define DEEP_SEL_ZIP_HI 0x07030602u    // (hi, lo) -> lo.2 hi.2 lo.3 hi.3
-#define DEEP_SEL_EVEN 0x06040200u      // (hi, lo) -> lo.0 lo.2 hi.0 hi.2
-#define DEEP_SEL_ODD 0x07050301u       // (hi, lo) -> lo.1 lo.3 hi.1 hi.3
-#define DEEP_SEL_WIDE_LO 0x0c010c00u   // (-, x) -> x.0 0 x.1 0
-#define DEEP_SEL_WIDE_HI 0x0c030c02u   // (-, x) -> x.2 0 x.3 0
+// v_perm_b32 selectors beside pix_rows.h's
 #define DEEP_SEL_HIGH_LO 0x010c000cu   // (-, x) -> 0 x.0 0 x.1
 #define DEEP_SEL_HIGH_HI 0x030c020cu   // (-, x) -> 0 x.2 0 x.3
 
 typedef unsigned short deep_pk __attribute__((ext_vector_type(2)));  // two 16-bit fields of a dword: v_pk_* arithmetic
-DDEV deep_pk deep_as_pk(uint32_t x) { return __builtin_bit_cast(deep_pk, x); }
-DDEV uint32_t deep_as_u32(deep_pk x) { return __builtin_bit_cast(uint32_t, x); }
-
-struct DeepFrame {
-    uint8_t *p[3];
-    int pp[3];
-    uint8_t *y, *u, *v;
-    int ys, cs;
-    int w, h, pix, depth;
-};
-
-DDEV bool deep_al(const void *a, const void *b, unsigned mask) { return ((((uintptr_t)a) | ((uintptr_t)b)) & mask) == 0; }
+PICDEV deep_pk deep_as_pk(uint32_t x) { return __builtin_bit_cast(deep_pk, x); }
+PICDEV uint32_t deep_as_u32(deep_pk x) { return __builtin_bit_cast(uint32_t, x); }
 
 // the depth rule's addends for the output samples at even and odd x of output row y, as the fields of a dword
-DDEV uint32_t deep_addend(int depth, int y) {
+PICDEV uint32_t deep_addend(int depth, int y) {
     if (depth == H264MI_DEPTH_DITHER) return (y & 1) ? 0x00010003u : 0x00020000u;  // D = {{0, 2}, {3, 1}}
     return depth == H264MI_DEPTH_TRUNC ? 0u : 0x00020002u;
 }
-DDEV uint32_t deep_add_at(uint32_t add, int x) { return (x & 1) ? add >> 16 : add & 0xffffu; }
-DDEV uint32_t deep_narrow1(uint32_t v10, uint32_t add) { return min(255u, (v10 + add) >> 2); }
+PICDEV uint32_t deep_add_at(uint32_t add, int x) { return (x & 1) ? add >> 16 : add & 0xffffu; }
+PICDEV uint32_t deep_narrow1(uint32_t v10, uint32_t add) { return min(255u, (v10 + add) >> 2); }
 
 // the 10-bit values of a dword's two words
 template <bool MSB>
-DDEV deep_pk deep_val2(uint32_t x) { return MSB ? deep_as_pk(x) >> (unsigned short)6 : deep_as_pk(x) & (unsigned short)1023; }
+PICDEV deep_pk deep_val2(uint32_t x) { return MSB ? deep_as_pk(x) >> (unsigned short)6 : deep_as_pk(x) & (unsigned short)1023; }
 // two 10-bit values to two 8-bit ones, in place in their fields
-DDEV uint32_t deep_narrow2(deep_pk v, uint32_t add) {
+PICDEV uint32_t deep_narrow2(deep_pk v, uint32_t add) {
     const deep_pk t = (v + deep_as_pk(add)) >> (unsigned short)2;
     return deep_as_u32(__builtin_elementwise_min(t, (deep_pk)(unsigned short)255));
 }
 // (a + b + 1) >> 1 of two pairs of 10-bit values
-DDEV deep_pk deep_avg2(deep_pk a, deep_pk b) { return (a + b + (unsigned short)1) >> (unsigned short)1; }
+PICDEV deep_pk deep_avg2(deep_pk a, deep_pk b) { return (a + b + (unsigned short)1) >> (unsigned short)1; }
 // bytes 0, 1 (LO) or 2, 3 (HI) of x as two words of a deep format
 template <bool MSB, bool HI>
-DDEV uint32_t deep_widen2(uint32_t x) {
+PICDEV uint32_t deep_widen2(uint32_t x) {
     if (MSB) return __builtin_amdgcn_perm(0u, x, HI ? DEEP_SEL_HIGH_HI : DEEP_SEL_HIGH_LO);
-    return __builtin_amdgcn_perm(0u, x, HI ? DEEP_SEL_WIDE_HI : DEEP_SEL_WIDE_LO) << 2;
+    return __builtin_amdgcn_perm(0u, x, HI ? PIX_SEL_WIDE_HI : PIX_SEL_WIDE_LO) << 2;
 }
 template <bool MSB>
-DDEV uint32_t deep_val1(uint16_t x) { return MSB ? x >> 6 : x & 1023; }
+PICDEV uint32_t deep_val1(uint16_t x) { return MSB ? x >> 6 : x & 1023; }
 template <bool MSB>
-DDEV uint16_t deep_word1(uint32_t v8) { return (uint16_t)(MSB ? v8 << 8 : v8 << 2); }
-
-// (x + y + 1) >> 1 of the four bytes of x and y
-DDEV uint32_t deep_avg4(uint32_t x, uint32_t y) {
-    const uint32_t lo = __builtin_amdgcn_perm(0u, x, DEEP_SEL_WIDE_LO) + __builtin_amdgcn_perm(0u, y, DEEP_SEL_WIDE_LO) + 0x00010001u;
-    const uint32_t hi = __builtin_amdgcn_perm(0u, x, DEEP_SEL_WIDE_HI) + __builtin_amdgcn_perm(0u, y, DEEP_SEL_WIDE_HI) + 0x00010001u;
-    return __builtin_amdgcn_perm(hi >> 1, lo >> 1, DEEP_SEL_EVEN);
-}
-
-// rows (1 or 2) rows of nb bytes from s (pitch sp) to d (pitch dp)
-DDEV void deep_move_rows(uint8_t *d, int dp, const uint8_t *s, int sp, int nb, int rows, int lane) {
-    const bool wide = deep_al(d, s, 15) && (rows == 1 || deep_al(d + dp, s + sp, 15));
-    for (int x = 16 * lane; x < nb; x += 16 * 64) {
-        if (wide && x + 16 <= nb) {
-            const uint4 a = *(const uint4 *)(s + x);
-            if (rows == 2) {
-                const uint4 b = *(const uint4 *)(s + sp + x);
-                *(uint4 *)(d + dp + x) = b;
-            }
-            *(uint4 *)(d + x) = a;
-        } else {
-            for (int r = 0; r < rows; r++)
-                for (int j = 0; j < 16 && x + j < nb; j++) d[(size_t)r * dp + x + j] = s[(size_t)r * sp + x + j];
-        }
-    }
-}
+PICDEV uint16_t deep_word1(uint32_t v8) { return (uint16_t)(MSB ? v8 << 8 : v8 << 2); }
 
 // nb bytes of value 128 at d (Y800's chroma)
-DDEV void deep_fill_row(uint8_t *d, int nb, int lane) {
-    const bool wide = deep_al(d, d, 15);
+PICDEV void deep_fill_row(uint8_t *d, int nb, int lane) {
+    const bool wide = pix_al(d, d, 15);
     for (int x = 16 * lane; x < nb; x += 16 * 64) {
         if (wide && x + 16 <= nb) *(uint4 *)(d + x) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
         else for (int j = 0; j < 16 && x + j < nb; j++) d[x + j] = 128;
@@ -132,8 +88,8 @@ DDEV void deep_fill_row(uint8_t *d, int nb, int lane) {
 
 // I422 chroma: the 8-bit rows a, b (rows 2r, 2r + 1, n bytes) from (PACK) or to the I420 row c
 template <bool PACK>
-DDEV void deep_422_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, int lane) {
-    const bool wide = deep_al(a, b, 15) && deep_al(c, c, 15);
+PICDEV void deep_422_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, int lane) {
+    const bool wide = pix_al(a, b, 15) && pix_al(c, c, 15);
     for (int x = 16 * lane; x < n; x += 16 * 64) {
         if (wide && x + 16 <= n) {
             if (PACK) {
@@ -142,7 +98,7 @@ DDEV void deep_422_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, int lane) {
                 *(uint4 *)(b + x) = s;
             } else {
                 const uint4 s = *(const uint4 *)(a + x), t = *(const uint4 *)(b + x);
-                *(uint4 *)(c + x) = make_uint4(deep_avg4(s.x, t.x), deep_avg4(s.y, t.y), deep_avg4(s.z, t.z), deep_avg4(s.w, t.w));
+                *(uint4 *)(c + x) = make_uint4(pix_avg4(s.x, t.x), pix_avg4(s.y, t.y), pix_avg4(s.z, t.z), pix_avg4(s.w, t.w));
             }
         } else {
             for (int j = 0; j < 16 && x + j < n; j++) {
@@ -154,28 +110,28 @@ DDEV void deep_422_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, int lane) {
 }
 
 // the sum of the four samples of each 2x2 of two dwords of two rows, + 2, >> 2: two bytes in two 16-bit fields
-DDEV uint32_t deep_box2(uint32_t s, uint32_t t) {
+PICDEV uint32_t deep_box2(uint32_t s, uint32_t t) {
     const deep_pk m = (deep_pk)(unsigned short)0x00ff;
     const deep_pk sum = (deep_as_pk(s) & m) + (deep_as_pk(s) >> (unsigned short)8) + (deep_as_pk(t) & m) + (deep_as_pk(t) >> (unsigned short)8);
     return deep_as_u32((sum + (unsigned short)2) >> (unsigned short)2);
 }
 // I444 chroma: the 8-bit rows a, b (2n bytes each) from (PACK) or to the I420 row c (n bytes)
 template <bool PACK>
-DDEV void deep_444_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, int lane) {
-    const bool wide = deep_al(a, b, 15) && deep_al(c, c, 7);
+PICDEV void deep_444_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, int lane) {
+    const bool wide = pix_al(a, b, 15) && pix_al(c, c, 7);
     for (int x = 8 * lane; x < n; x += 8 * 64) {
         if (wide && x + 8 <= n) {
             if (PACK) {
                 const uint2 s = *(const uint2 *)(c + x);
-                const uint4 o = make_uint4(__builtin_amdgcn_perm(s.x, s.x, DEEP_SEL_ZIP_LO), __builtin_amdgcn_perm(s.x, s.x, DEEP_SEL_ZIP_HI),
-                                           __builtin_amdgcn_perm(s.y, s.y, DEEP_SEL_ZIP_LO), __builtin_amdgcn_perm(s.y, s.y, DEEP_SEL_ZIP_HI));
+                const uint4 o = make_uint4(__builtin_amdgcn_perm(s.x, s.x, PIX_SEL_ZIP_LO), __builtin_amdgcn_perm(s.x, s.x, PIX_SEL_ZIP_HI),
+                                           __builtin_amdgcn_perm(s.y, s.y, PIX_SEL_ZIP_LO), __builtin_amdgcn_perm(s.y, s.y, PIX_SEL_ZIP_HI));
                 *(uint4 *)(a + 2 * x) = o;
                 *(uint4 *)(b + 2 * x) = o;
             } else {
                 const uint4 s = *(const uint4 *)(a + 2 * x), t = *(const uint4 *)(b + 2 * x);  // both rows before the average
                 uint2 o;
-                o.x = __builtin_amdgcn_perm(deep_box2(s.y, t.y), deep_box2(s.x, t.x), DEEP_SEL_EVEN);
-                o.y = __builtin_amdgcn_perm(deep_box2(s.w, t.w), deep_box2(s.z, t.z), DEEP_SEL_EVEN);
+                o.x = __builtin_amdgcn_perm(deep_box2(s.y, t.y), deep_box2(s.x, t.x), PIX_SEL_EVEN);
+                o.y = __builtin_amdgcn_perm(deep_box2(s.w, t.w), deep_box2(s.z, t.z), PIX_SEL_EVEN);
                 *(uint2 *)(c + x) = o;
             }
         } else {
@@ -190,21 +146,21 @@ DDEV void deep_444_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, int lane) {
 
 // NV16 chroma: the interleaved 8-bit rows a, b (cw Cb Cr pairs each) from (PACK) or to the I420 rows u, v
 template <bool PACK>
-DDEV void deep_nv16_rows(uint8_t *a, uint8_t *b, uint8_t *u, uint8_t *v, int cw, int lane) {
-    const bool wide = deep_al(a, b, 15) && deep_al(u, v, 7);
+PICDEV void deep_nv16_rows(uint8_t *a, uint8_t *b, uint8_t *u, uint8_t *v, int cw, int lane) {
+    const bool wide = pix_al(a, b, 15) && pix_al(u, v, 7);
     for (int c = 8 * lane; c < cw; c += 8 * 64) {
         if (wide && c + 8 <= cw) {
             if (PACK) {
                 const uint2 cu = *(const uint2 *)(u + c), cv = *(const uint2 *)(v + c);
-                const uint4 o = make_uint4(__builtin_amdgcn_perm(cv.x, cu.x, DEEP_SEL_ZIP_LO), __builtin_amdgcn_perm(cv.x, cu.x, DEEP_SEL_ZIP_HI),
-                                           __builtin_amdgcn_perm(cv.y, cu.y, DEEP_SEL_ZIP_LO), __builtin_amdgcn_perm(cv.y, cu.y, DEEP_SEL_ZIP_HI));
+                const uint4 o = make_uint4(__builtin_amdgcn_perm(cv.x, cu.x, PIX_SEL_ZIP_LO), __builtin_amdgcn_perm(cv.x, cu.x, PIX_SEL_ZIP_HI),
+                                           __builtin_amdgcn_perm(cv.y, cu.y, PIX_SEL_ZIP_LO), __builtin_amdgcn_perm(cv.y, cu.y, PIX_SEL_ZIP_HI));
                 *(uint4 *)(a + 2 * c) = o;
                 *(uint4 *)(b + 2 * c) = o;
             } else {
                 const uint4 s = *(const uint4 *)(a + 2 * c), t = *(const uint4 *)(b + 2 * c);
-                const uint32_t m0 = deep_avg4(s.x, t.x), m1 = deep_avg4(s.y, t.y), m2 = deep_avg4(s.z, t.z), m3 = deep_avg4(s.w, t.w);
-                *(uint2 *)(u + c) = make_uint2(__builtin_amdgcn_perm(m1, m0, DEEP_SEL_EVEN), __builtin_amdgcn_perm(m3, m2, DEEP_SEL_EVEN));
-                *(uint2 *)(v + c) = make_uint2(__builtin_amdgcn_perm(m1, m0, DEEP_SEL_ODD), __builtin_amdgcn_perm(m3, m2, DEEP_SEL_ODD));
+                const uint32_t m0 = pix_avg4(s.x, t.x), m1 = pix_avg4(s.y, t.y), m2 = pix_avg4(s.z, t.z), m3 = pix_avg4(s.w, t.w);
+                *(uint2 *)(u + c) = make_uint2(__builtin_amdgcn_perm(m1, m0, PIX_SEL_EVEN), __builtin_amdgcn_perm(m3, m2, PIX_SEL_EVEN));
+                *(uint2 *)(v + c) = make_uint2(__builtin_amdgcn_perm(m1, m0, PIX_SEL_ODD), __builtin_amdgcn_perm(m3, m2, PIX_SEL_ODD));
             }
         } else {
             for (int j = 0; j < 8 && c + j < cw; j++) {
@@ -219,8 +175,8 @@ DDEV void deep_nv16_rows(uint8_t *a, uint8_t *b, uint8_t *u, uint8_t *v, int cw,
 // planar 16-bit rows: n words at a, and at b when there are two (4:2:2 chroma rows 2r, 2r + 1; nullptr otherwise), from
 // (PACK) or to the n bytes at c; add is deep_addend of c's row
 template <bool PACK, bool MSB>
-DDEV void deep_planar_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, uint32_t add, int lane) {
-    const bool wide = deep_al(a, b, 15) && deep_al(c, c, 7);  // a null b adds nothing
+PICDEV void deep_planar_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, uint32_t add, int lane) {
+    const bool wide = pix_al(a, b, 15) && pix_al(c, c, 7);  // a null b adds nothing
     for (int x = 8 * lane; x < n; x += 8 * 64) {
         if (wide && x + 8 <= n) {
             if (PACK) {
@@ -238,8 +194,8 @@ DDEV void deep_planar_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, uint32_t a
                     v2 = deep_avg2(v2, deep_val2<MSB>(t.z)); v3 = deep_avg2(v3, deep_val2<MSB>(t.w));
                 }
                 uint2 o;
-                o.x = __builtin_amdgcn_perm(deep_narrow2(v1, add), deep_narrow2(v0, add), DEEP_SEL_EVEN);
-                o.y = __builtin_amdgcn_perm(deep_narrow2(v3, add), deep_narrow2(v2, add), DEEP_SEL_EVEN);
+                o.x = __builtin_amdgcn_perm(deep_narrow2(v1, add), deep_narrow2(v0, add), PIX_SEL_EVEN);
+                o.y = __builtin_amdgcn_perm(deep_narrow2(v3, add), deep_narrow2(v2, add), PIX_SEL_EVEN);
                 *(uint2 *)(c + x) = o;
             }
         } else {
@@ -262,14 +218,14 @@ DDEV void deep_planar_rows(uint8_t *a, uint8_t *b, uint8_t *c, int n, uint32_t a
 // interleaved 16-bit rows: cw Cb Cr word pairs at a, and at b when there are two (nullptr otherwise), from (PACK) or to
 // the cw bytes each at u and v; add is deep_addend of the chroma row
 template <bool PACK, bool MSB>
-DDEV void deep_il_rows(uint8_t *a, uint8_t *b, uint8_t *u, uint8_t *v, int cw, uint32_t add, int lane) {
-    const bool wide = deep_al(a, b, 15) && deep_al(u, v, 3);
+PICDEV void deep_il_rows(uint8_t *a, uint8_t *b, uint8_t *u, uint8_t *v, int cw, uint32_t add, int lane) {
+    const bool wide = pix_al(a, b, 15) && pix_al(u, v, 3);
     const uint32_t add_e = (add & 0xffffu) * 0x00010001u, add_o = (add >> 16) * 0x00010001u;  // a dword is one position
     for (int c = 4 * lane; c < cw; c += 4 * 64) {
         if (wide && c + 4 <= cw) {
             if (PACK) {
                 const uint32_t cu = *(const uint32_t *)(u + c), cv = *(const uint32_t *)(v + c);
-                const uint32_t uv0 = __builtin_amdgcn_perm(cv, cu, DEEP_SEL_ZIP_LO), uv1 = __builtin_amdgcn_perm(cv, cu, DEEP_SEL_ZIP_HI);
+                const uint32_t uv0 = __builtin_amdgcn_perm(cv, cu, PIX_SEL_ZIP_LO), uv1 = __builtin_amdgcn_perm(cv, cu, PIX_SEL_ZIP_HI);
                 const uint4 o = make_uint4(deep_widen2<MSB, false>(uv0), deep_widen2<MSB, true>(uv0), deep_widen2<MSB, false>(uv1),
                                            deep_widen2<MSB, true>(uv1));
                 *(uint4 *)(a + 4 * c) = o;
@@ -283,10 +239,10 @@ DDEV void deep_il_rows(uint8_t *a, uint8_t *b, uint8_t *u, uint8_t *v, int cw, u
                     v2 = deep_avg2(v2, deep_val2<MSB>(t.z)); v3 = deep_avg2(v3, deep_val2<MSB>(t.w));
                 }
                 // Cb Cr Cb Cr of positions c, c + 1 and of c + 2, c + 3, then the split
-                const uint32_t p01 = __builtin_amdgcn_perm(deep_narrow2(v1, add_o), deep_narrow2(v0, add_e), DEEP_SEL_EVEN);
-                const uint32_t p23 = __builtin_amdgcn_perm(deep_narrow2(v3, add_o), deep_narrow2(v2, add_e), DEEP_SEL_EVEN);
-                *(uint32_t *)(u + c) = __builtin_amdgcn_perm(p23, p01, DEEP_SEL_EVEN);
-                *(uint32_t *)(v + c) = __builtin_amdgcn_perm(p23, p01, DEEP_SEL_ODD);
+                const uint32_t p01 = __builtin_amdgcn_perm(deep_narrow2(v1, add_o), deep_narrow2(v0, add_e), PIX_SEL_EVEN);
+                const uint32_t p23 = __builtin_amdgcn_perm(deep_narrow2(v3, add_o), deep_narrow2(v2, add_e), PIX_SEL_EVEN);
+                *(uint32_t *)(u + c) = __builtin_amdgcn_perm(p23, p01, PIX_SEL_EVEN);
+                *(uint32_t *)(v + c) = __builtin_amdgcn_perm(p23, p01, PIX_SEL_ODD);
             }
         } else {
             uint16_t *wa = (uint16_t *)a, *wb = (uint16_t *)b;
@@ -308,10 +264,10 @@ DDEV void deep_il_rows(uint8_t *a, uint8_t *b, uint8_t *u, uint8_t *v, int cw, u
 
 // ---- V210. A group's twelve fields in order are Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 Cb2 Y4 Cr2 Y5: field f is bits
 // 10 (f % 3) .. + 9 of word f / 3; Yk is field 2k + 1, Cbk field 4k, Crk field 4k + 2
-DDEV uint32_t v210_get(const uint32_t *wd, int f) { return (wd[f / 3] >> (10 * (f % 3))) & 1023u; }
+PICDEV uint32_t v210_get(const uint32_t *wd, int f) { return (wd[f / 3] >> (10 * (f % 3))) & 1023u; }
 // the words a, b of one group of rows 2r, 2r + 1 to six luma samples a row and three averaged Cb, Cr; gpar: the parity
 // of the group's index in its row (its first chroma position is 3 * index)
-DDEV void v210_unpack_group(const uint32_t *a, const uint32_t *b, uint32_t *s0, uint32_t *s1, uint32_t *cu, uint32_t *cv, uint32_t add0,
+PICDEV void v210_unpack_group(const uint32_t *a, const uint32_t *b, uint32_t *s0, uint32_t *s1, uint32_t *cu, uint32_t *cv, uint32_t add0,
                             uint32_t add1, uint32_t addc, int gpar) {
 #pragma unroll
     for (int k = 0; k < 6; k++) {
@@ -326,7 +282,7 @@ DDEV void v210_unpack_group(const uint32_t *a, const uint32_t *b, uint32_t *s0, 
     }
 }
 // the other way: v << 2 in each field, bits 31..30 zero; a sample that is 0 leaves its field 0
-DDEV void v210_pack_group(uint32_t *a, uint32_t *b, const uint32_t *s0, const uint32_t *s1, const uint32_t *cu, const uint32_t *cv) {
+PICDEV void v210_pack_group(uint32_t *a, uint32_t *b, const uint32_t *s0, const uint32_t *s1, const uint32_t *cu, const uint32_t *cv) {
 #pragma unroll
     for (int k = 0; k < 4; k++) a[k] = b[k] = 0;
 #pragma unroll
@@ -346,9 +302,9 @@ DDEV void v210_pack_group(uint32_t *a, uint32_t *b, const uint32_t *s0, const ui
 
 // the V210 rows q0, q1 of a row pair from (PACK) or to the luma rows y0, y1 and the chroma rows u, v
 template <bool PACK>
-DDEV void v210_row_pair(uint8_t *q0, uint8_t *q1, uint8_t *y0, uint8_t *y1, uint8_t *u, uint8_t *v, int w, int r, int depth, int lane) {
+PICDEV void v210_row_pair(uint8_t *q0, uint8_t *q1, uint8_t *y0, uint8_t *y1, uint8_t *u, uint8_t *v, int w, int r, int depth, int lane) {
     const uint32_t add0 = deep_addend(depth, 2 * r), add1 = deep_addend(depth, 2 * r + 1), addc = deep_addend(depth, r);
-    const bool wide = deep_al(q0, q1, 15) && deep_al(y0, y1, 15) && deep_al(u, v, 7);
+    const bool wide = pix_al(q0, q1, 15) && pix_al(y0, y1, 15) && pix_al(u, v, 7);
     const int ngroups = (w + 5) / 6, nruns = wide ? w / 48 : 0;  // a run: eight whole groups
     for (int j = lane; j < nruns; j += 64) {
         uint8_t *pa = q0 + 128 * (size_t)j, *pb = q1 + 128 * (size_t)j;
@@ -443,7 +399,7 @@ DDEV void v210_row_pair(uint8_t *q0, uint8_t *q1, uint8_t *y0, uint8_t *y1, uint
 
 // luma of the deep planar and semi-planar formats: rows 2r and 2r + 1, one row each call
 template <bool PACK, bool MSB>
-DDEV void deep_luma(const DeepFrame &f, int r, uint8_t *y0, int lane) {
+PICDEV void deep_luma(const PixFrame &f, int r, uint8_t *y0, int lane) {
     uint8_t *l0 = f.p[0] + (size_t)(2 * r) * f.pp[0];
     deep_planar_rows<PACK, MSB>(l0, nullptr, y0, f.w, deep_addend(f.depth, 2 * r), lane);
     deep_planar_rows<PACK, MSB>(l0 + f.pp[0], nullptr, y0 + f.ys, f.w, deep_addend(f.depth, 2 * r + 1), lane);
@@ -451,7 +407,7 @@ DDEV void deep_luma(const DeepFrame &f, int r, uint8_t *y0, int lane) {
 
 // row pair r (luma rows 2r, 2r + 1, I420 chroma row r) of a frame, one wave
 template <bool PACK>
-DDEV void deep_row_pair(const DeepFrame &f, int r, int lane) {
+PICDEV void deep_row_pair(const PixFrame &f, int r, int lane) {
     uint8_t *y0 = f.y + (size_t)(2 * r) * f.ys, *u = f.u + (size_t)r * f.cs, *v = f.v + (size_t)r * f.cs;
     const int cw = f.w / 2;
     const uint32_t addc = deep_addend(f.depth, r);
@@ -477,8 +433,8 @@ DDEV void deep_row_pair(const DeepFrame &f, int r, int lane) {
     }
     default: break;
     }
-    if (PACK) deep_move_rows(l0, f.pp[0], y0, f.ys, f.w, 2, lane);
-    else deep_move_rows(y0, f.ys, l0, f.pp[0], f.w, 2, lane);
+    if (PACK) pix_move_rows(l0, f.pp[0], y0, f.ys, f.w, 2, lane);
+    else pix_move_rows(y0, f.ys, l0, f.pp[0], f.w, 2, lane);
     if (f.pix == H264MI_PIX_Y800) {
         if (!PACK) { deep_fill_row(u, cw, lane); deep_fill_row(v, cw, lane); }
         return;
@@ -498,88 +454,15 @@ DDEV void deep_row_pair(const DeepFrame &f, int r, int lane) {
     }
 }
 
-struct DeepLaunch {
-    uint8_t *pk;          // the layout side: frame f at pk + f * pk_fs, plane p at + off[p], pitch[p]
-    uint8_t *i420;        // the I420 side, tight: frame f at i420 + f * fb
-    int64_t pk_fs, off[3];
-    size_t fb;
-    int pitch[3];
-    int pix, w, h, n, nstrip, depth;
-};
-
-template <bool PACK>
-__global__ __launch_bounds__(256) void pixdeep_kernel(DeepLaunch a) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long long items = (long long)a.n * a.nstrip;
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long long fi = it / a.nstrip;
-        const int r = (int)(it - fi * a.nstrip) * H264MI_DEEP_STRIP + wv;
-        if (r >= a.h / 2) continue;
-        DeepFrame f;
-        uint8_t *pk = a.pk + fi * a.pk_fs, *fr = a.i420 + (size_t)fi * a.fb;
-        for (int p = 0; p < 3; p++) { f.p[p] = pk + a.off[p]; f.pp[p] = a.pitch[p]; }
-        f.y = fr; f.u = fr + (size_t)a.w * a.h; f.v = f.u + (size_t)(a.w / 2) * (a.h / 2);
-        f.ys = a.w; f.cs = a.w / 2;
-        f.w = a.w; f.h = a.h; f.pix = a.pix; f.depth = a.depth;
-        deep_row_pair<PACK>(f, r, lane);
-    }
-}
-
-// Read-out of a batched decode call into a deep layout: pixfmt.hip's dec_output_pix_kernel with deep_row_pair. A frame
-// whose base I.out is no multiple of the format's unit is reported in got but not written (the host cannot see it)
-struct DecDeepLaunch { int S, cw, ch, w, h, nstrip, unit; const DecDesc *desc; const DecInput *in; h264mi_pix_layout lay; };
-__global__ __launch_bounds__(256) void dec_output_pixdeep_kernel(DecDeepLaunch a) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int items = a.S * a.nstrip;
-    for (int it = blockIdx.x; it < items; it += gridDim.x) {
-        const int s = it / a.nstrip, k = it - s * a.nstrip;
-        const DecState *st = a.desc[s].st;
-        const DecInput &I = a.in[s];
-        const int ok = st->got_pic && !st->err;
-        if (I.got && k == 0 && threadIdx.x == 0) *I.got = ok;
-        if (!ok || !I.out || (((uintptr_t)I.out) & (uintptr_t)(a.unit - 1))) continue;
-        const int c0 = st->ps.crop[0], c1 = st->ps.crop[1], c2 = st->ps.crop[2], c3 = st->ps.crop[3];
-        const int W = a.cw - 2 * (c0 + c1), H = a.ch - 2 * (c2 + c3), x0 = 2 * c0, y0 = 2 * c2;
-        const int r = k * H264MI_DEEP_STRIP + wv;
-        if (W != a.w || H != a.h || r >= H / 2) continue;
-        uint8_t *const *pic = a.desc[s].pic[st->outpar & 1];
-        DeepFrame f;
-        for (int p = 0; p < 3; p++) { f.p[p] = I.out + a.lay.offset[p]; f.pp[p] = a.lay.pitch[p]; }
-        f.ys = a.cw; f.cs = a.cw / 2;
-        f.y = pic[0] + (size_t)y0 * f.ys + x0;
-        f.u = pic[1] + (size_t)(y0 / 2) * f.cs + x0 / 2;
-        f.v = pic[2] + (size_t)(y0 / 2) * f.cs + x0 / 2;
-        f.w = W; f.h = H; f.pix = a.lay.pix; f.depth = 0;
-        deep_row_pair<true>(f, r, lane);
-    }
-}
-
 // ---- host
-static int deep_nstrip(int h) { return (h / 2 + H264MI_DEEP_STRIP - 1) / H264MI_DEEP_STRIP; }
-// n frames between the deep layout L at pk and tight I420 at i420; arguments as pix_args_ok accepts them
-static int launch_deep(bool pack, uint8_t *pk, const h264mi_pix_layout &L, uint8_t *i420, int depth, int w, int h, int n, hipStream_t s) {
-    DeepLaunch a{};
-    a.pk = pk; a.i420 = i420; a.pk_fs = L.frame_stride; a.fb = i420_bytes(w, h);
-    for (int p = 0; p < 3; p++) { a.off[p] = L.offset[p]; a.pitch[p] = L.pitch[p]; }
-    a.pix = L.pix; a.w = w; a.h = h; a.n = n; a.nstrip = deep_nstrip(h); a.depth = depth;  // at most 1024 strips a frame
-    const unsigned blocks = (unsigned)std::min((long long)n * a.nstrip, (long long)PIC_MAX_BLOCKS);
-    (void)hipGetLastError();
-    if (pack) hipLaunchKernelGGL(pixdeep_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(pixdeep_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 int launch_pixdeep_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int depth, int w, int h, int n, hipStream_t s) {
-    return launch_deep(false, const_cast<uint8_t *>(d_src), L, d_i420, depth, w, h, n, s);  // the layout side is only read
+    return launch_pix_rows<deep_row_pair<false>>(d_src, L, d_i420, depth, w, h, n, s);
 }
 int launch_i420_to_pixdeep(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s) {
-    return launch_deep(true, d_dst, L, const_cast<uint8_t *>(d_i420), 0, w, h, n, s);  // the I420 side is only read
+    return launch_pix_rows<deep_row_pair<true>>(d_dst, L, d_i420, 0, w, h, n, s);
 }
 int launch_dec_output_pixdeep(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in, const h264mi_pix_layout &L,
                               hipStream_t s) {
-    DecDeepLaunch a{S, cw, ch, w, h, deep_nstrip(h), pix_unit(L.pix), desc, in, L};
-    const unsigned blocks = (unsigned)std::min(S * a.nstrip, PIC_MAX_BLOCKS);  // S <= 256 streams of <= 1024 strips
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(dec_output_pixdeep_kernel, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_dec_output_rows<deep_row_pair<true>>(S, cw, ch, w, h, desc, in, L, s);
 }
 }  // namespace h264mi

@@ -1,10 +1,13 @@
 // pixfmt.hip -- frames in other memory layouts to and from tight I420 on the device (gfx950): NV12, NV21, YUY2, UYVY
 // and I420 with pitches, as include/h264mi.h (h264mi_pix_layout) defines them. DESIGN.md §5.10.
-//   pix_kernel<false>     : n frames in a layout -> n tight I420 frames (h264mi_pix_to_i420_dev, h264mi_enc_encode_pix)
-//   pix_kernel<true>      : n tight I420 frames -> n frames in a layout (h264mi_i420_to_pix_dev)
-//   dec_output_pix_kernel : the batch decoder's per-frame read-out into a layout (h264mi_dec_set_output_layout): the
-//                           cropped picture read where it lies (coded strides, crop origin), as dec_output_rgba_kernel
-// One definition for all three (pix_row_pair): the "layout side" of a frame is up to three planes with a pitch each,
+//   pix_rows_kernel<pix_row_pair<false>>       : n frames in a layout -> n tight I420 frames (h264mi_pix_to_i420_dev,
+//                                                h264mi_enc_encode_pix)
+//   pix_rows_kernel<pix_row_pair<true>>        : n tight I420 frames -> n frames in a layout (h264mi_i420_to_pix_dev)
+//   dec_output_rows_kernel<pix_row_pair<true>> : the batch decoder's per-frame read-out into a layout
+//                           (h264mi_dec_set_output_layout): the cropped picture read where it lies (coded strides, crop
+//                           origin), as dec_output_rgba_kernel
+// The kernels, their launchers, the frame and the plain row move are pix_rows.h's, shared with pixdeep.hip; this file
+// owns the row functions of its five formats. One definition for all three kernels (pix_row_pair): the "layout side" of a frame is up to three planes with a pitch each,
 // the "I420 side" three plane pointers with a luma and a chroma pitch (tight for the conversions, the coded strides for
 // the decoder). Samples are moved; the one computed value is the 4:2:2 -> 4:2:0 chroma, (a + b + 1) >> 1 of rows 2y, 2y+1.
 //
@@ -36,61 +39,18 @@
 // An aligned piece that ends inside the row never leaves it, and the byte path stops at the row's end: no access leaves
 // the rows the layout names, on either side, and pitch padding and gaps are never written.
 //
-// A translation unit and a code object of its own, as orient.hip is: the library's other kernels stay byte for byte
-// what they were. The host runtime (capi_enc.inc, runtime_dec.inc) reaches it through the functions picture_host.h
+// A translation unit and a code object of its own, as orient.hip is. The host runtime (capi_enc.inc, runtime_dec.inc) reaches it through the functions picture_host.h
 // declares; the layout rules are host code there (pix_span, pix_layout_ok).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include "../../include/h264mi.h"
-#include "h264mi_types.h"
-#include "picture_host.h"
+#include "pix_rows.h"
 
 namespace h264mi {
-#define PDEV __device__ __forceinline__
-
-#define H264MI_PIX_STRIP 4   // row pairs per block, one per wave
-
-// v_perm_b32 selectors: bytes 0..3 name the second operand's bytes, 4..7 the first's, 0x0c is the constant 0
-#define PIX_SEL_ZIP_LO 0x05010400u   // (hi, lo) -> lo.0 hi.0 lo.1 hi.1
-#define PIX_SEL_ZIP_HI 0x07030602u   // (hi, lo) -> lo.2 hi.2 lo.3 hi.3
-#define PIX_SEL_EVEN 0x06040200u     // (hi, lo) -> lo.0 lo.2 hi.0 hi.2
-#define PIX_SEL_ODD 0x07050301u      // (hi, lo) -> lo.1 lo.3 hi.1 hi.3
-#define PIX_SEL_WIDE_LO 0x0c010c00u  // (-, x) -> x.0 0 x.1 0
-#define PIX_SEL_WIDE_HI 0x0c030c02u  // (-, x) -> x.2 0 x.3 0
-
-// one frame, both sides resolved: the layout side's planes p[] with pitches pp[], the I420 side's planes with pitches
-struct PixFrame {
-    uint8_t *p[3];
-    int pp[3];
-    uint8_t *y, *u, *v;
-    int ys, cs;
-    int w, h, pix;
-};
-
-PDEV bool pix_al(const void *a, const void *b, unsigned mask) { return ((((uintptr_t)a) | ((uintptr_t)b)) & mask) == 0; }
-
-// rows (1 or 2) rows of nb bytes from s (pitch sp) to d (pitch dp)
-PDEV void pix_move_rows(uint8_t *d, int dp, const uint8_t *s, int sp, int nb, int rows, int lane) {
-    const bool wide = pix_al(d, s, 15) && (rows == 1 || pix_al(d + dp, s + sp, 15));
-    for (int x = 16 * lane; x < nb; x += 16 * 64) {
-        if (wide && x + 16 <= nb) {
-            const uint4 a = *(const uint4 *)(s + x);
-            if (rows == 2) {
-                const uint4 b = *(const uint4 *)(s + sp + x);
-                *(uint4 *)(d + dp + x) = b;
-            }
-            *(uint4 *)(d + x) = a;
-        } else {
-            for (int r = 0; r < rows; r++)
-                for (int j = 0; j < 16 && x + j < nb; j++) d[(size_t)r * dp + x + j] = s[(size_t)r * sp + x + j];
-        }
-    }
-}
-
 // one interleaved chroma row il (cw pairs: a[i] at byte 2i, b[i] at 2i + 1) from (PACK) or to the planar rows a, b
 template <bool PACK>
-PDEV void pix_nv_row(uint8_t *il, uint8_t *a, uint8_t *b, int cw, int lane) {
+PICDEV void pix_nv_row(uint8_t *il, uint8_t *a, uint8_t *b, int cw, int lane) {
     const bool wide = pix_al(il, il, 15) && pix_al(a, b, 7);
     for (int c = 8 * lane; c < cw; c += 8 * 64) {
         if (wide && c + 8 <= cw) {
@@ -121,17 +81,10 @@ PDEV void pix_nv_row(uint8_t *il, uint8_t *a, uint8_t *b, int cw, int lane) {
     }
 }
 
-// (x + y + 1) >> 1 of the four bytes of x and y
-PDEV uint32_t pix_avg4(uint32_t x, uint32_t y) {
-    const uint32_t lo = __builtin_amdgcn_perm(0u, x, PIX_SEL_WIDE_LO) + __builtin_amdgcn_perm(0u, y, PIX_SEL_WIDE_LO) + 0x00010001u;
-    const uint32_t hi = __builtin_amdgcn_perm(0u, x, PIX_SEL_WIDE_HI) + __builtin_amdgcn_perm(0u, y, PIX_SEL_WIDE_HI) + 0x00010001u;
-    return __builtin_amdgcn_perm(hi >> 1, lo >> 1, PIX_SEL_EVEN);  // the low byte of each 16-bit field: sums are below 512
-}
-
 // the packed rows q0, q1 (2w bytes each) of a row pair from (PACK) or to the luma rows y0, y1 and the chroma rows u, v.
 // yo: 0 YUY2 (luma in the even bytes), 1 UYVY (in the odd ones)
 template <bool PACK>
-PDEV void pix_422_row_pair(uint8_t *q0, uint8_t *q1, uint8_t *y0, uint8_t *y1, uint8_t *u, uint8_t *v, int w, int yo, int lane) {
+PICDEV void pix_422_row_pair(uint8_t *q0, uint8_t *q1, uint8_t *y0, uint8_t *y1, uint8_t *u, uint8_t *v, int w, int yo, int lane) {
     const bool wide = pix_al(q0, q1, 15) && pix_al(y0, y1, 7) && pix_al(u, v, 3);
     const uint32_t ysel = yo ? PIX_SEL_ODD : PIX_SEL_EVEN, csel = yo ? PIX_SEL_EVEN : PIX_SEL_ODD;
     for (int x = 8 * lane; x < w; x += 8 * 64) {
@@ -186,7 +139,7 @@ PDEV void pix_422_row_pair(uint8_t *q0, uint8_t *q1, uint8_t *y0, uint8_t *y1, u
 
 // row pair r (luma rows 2r, 2r + 1, chroma row r) of a frame, one wave
 template <bool PACK>
-PDEV void pix_row_pair(const PixFrame &f, int r, int lane) {
+PICDEV void pix_row_pair(const PixFrame &f, int r, int lane) {
     uint8_t *y0 = f.y + (size_t)(2 * r) * f.ys, *u = f.u + (size_t)r * f.cs, *v = f.v + (size_t)r * f.cs;
     if (f.pix == H264MI_PIX_YUY2 || f.pix == H264MI_PIX_UYVY) {
         uint8_t *q0 = f.p[0] + (size_t)(2 * r) * f.pp[0];
@@ -207,90 +160,15 @@ PDEV void pix_row_pair(const PixFrame &f, int r, int lane) {
     }
 }
 
-struct PixLaunch {
-    uint8_t *pk;          // the layout side: frame f at pk + f * pk_fs, plane p at + off[p], pitch[p]
-    uint8_t *i420;        // the I420 side, tight: frame f at i420 + f * fb
-    int64_t pk_fs, off[3];
-    size_t fb;
-    int pitch[3];
-    int pix, w, h, n, nstrip;
-};
-
-template <bool PACK>
-__global__ __launch_bounds__(256) void pix_kernel(PixLaunch a) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long long items = (long long)a.n * a.nstrip;
-    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
-        const long long fi = it / a.nstrip;
-        const int r = (int)(it - fi * a.nstrip) * H264MI_PIX_STRIP + wv;
-        if (r >= a.h / 2) continue;
-        PixFrame f;
-        uint8_t *pk = a.pk + fi * a.pk_fs, *fr = a.i420 + (size_t)fi * a.fb;
-        for (int p = 0; p < 3; p++) { f.p[p] = pk + a.off[p]; f.pp[p] = a.pitch[p]; }
-        f.y = fr; f.u = fr + (size_t)a.w * a.h; f.v = f.u + (size_t)(a.w / 2) * (a.h / 2);
-        f.ys = a.w; f.cs = a.w / 2;
-        f.w = a.w; f.h = a.h; f.pix = a.pix;
-        pix_row_pair<PACK>(f, r, lane);
-    }
-}
-
-// Read-out of a batched decode call into a layout (after dec_end_kernel of frame f): what dec_output_kernel does for
-// tight I420 -- got, and the picture pic[outpar] cropped by its SPS, read where it lies -- written in layout lay to
-// in[s].out. lay was checked for w x h; a picture of another cropped size is not written
-struct DecPixLaunch { int S, cw, ch, w, h, nstrip; const DecDesc *desc; const DecInput *in; h264mi_pix_layout lay; };
-__global__ __launch_bounds__(256) void dec_output_pix_kernel(DecPixLaunch a) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int items = a.S * a.nstrip;
-    for (int it = blockIdx.x; it < items; it += gridDim.x) {
-        const int s = it / a.nstrip, k = it - s * a.nstrip;
-        const DecState *st = a.desc[s].st;
-        const DecInput &I = a.in[s];
-        const int ok = st->got_pic && !st->err;
-        if (I.got && k == 0 && threadIdx.x == 0) *I.got = ok;
-        if (!ok || !I.out) continue;
-        const int c0 = st->ps.crop[0], c1 = st->ps.crop[1], c2 = st->ps.crop[2], c3 = st->ps.crop[3];
-        const int W = a.cw - 2 * (c0 + c1), H = a.ch - 2 * (c2 + c3), x0 = 2 * c0, y0 = 2 * c2;
-        const int r = k * H264MI_PIX_STRIP + wv;
-        if (W != a.w || H != a.h || r >= H / 2) continue;
-        uint8_t *const *pic = a.desc[s].pic[st->outpar & 1];
-        PixFrame f;
-        for (int p = 0; p < 3; p++) { f.p[p] = I.out + a.lay.offset[p]; f.pp[p] = a.lay.pitch[p]; }
-        f.ys = a.cw; f.cs = a.cw / 2;
-        f.y = pic[0] + (size_t)y0 * f.ys + x0;
-        f.u = pic[1] + (size_t)(y0 / 2) * f.cs + x0 / 2;
-        f.v = pic[2] + (size_t)(y0 / 2) * f.cs + x0 / 2;
-        f.w = W; f.h = H; f.pix = a.lay.pix;
-        pix_row_pair<true>(f, r, lane);
-    }
-}
-
 // ---- host
-static int pix_nstrip(int h) { return (h / 2 + H264MI_PIX_STRIP - 1) / H264MI_PIX_STRIP; }
-// n frames between layout L at pk and tight I420 at i420; arguments as pix_args_ok accepts them
-static int launch_pix(bool pack, uint8_t *pk, const h264mi_pix_layout &L, uint8_t *i420, int w, int h, int n, hipStream_t s) {
-    PixLaunch a{};
-    a.pk = pk; a.i420 = i420; a.pk_fs = L.frame_stride; a.fb = i420_bytes(w, h);
-    for (int p = 0; p < 3; p++) { a.off[p] = L.offset[p]; a.pitch[p] = L.pitch[p]; }
-    a.pix = L.pix; a.w = w; a.h = h; a.n = n; a.nstrip = pix_nstrip(h);  // at most 1024 strips a frame
-    const unsigned blocks = (unsigned)std::min((long long)n * a.nstrip, (long long)PIC_MAX_BLOCKS);
-    (void)hipGetLastError();
-    if (pack) hipLaunchKernelGGL(pix_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(pix_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s) {
-    return launch_pix(false, const_cast<uint8_t *>(d_src), L, d_i420, w, h, n, s);  // the layout side is only read
+    return launch_pix_rows<pix_row_pair<false>>(d_src, L, d_i420, 0, w, h, n, s);
 }
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s) {
-    return launch_pix(true, d_dst, L, const_cast<uint8_t *>(d_i420), w, h, n, s);  // the I420 side is only read
+    return launch_pix_rows<pix_row_pair<true>>(d_dst, L, d_i420, 0, w, h, n, s);
 }
-// frame f's S entries of desc / in, as DecOutLaunch holds them; L good for w x h (h264mi_dec_set_output_layout)
 int launch_dec_output_pix(int S, int cw, int ch, int w, int h, const DecDesc *desc, const DecInput *in, const h264mi_pix_layout &L,
                           hipStream_t s) {
-    DecPixLaunch a{S, cw, ch, w, h, pix_nstrip(h), desc, in, L};
-    const unsigned blocks = (unsigned)std::min(S * a.nstrip, PIC_MAX_BLOCKS);  // S <= 256 streams of <= 1024 strips
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(dec_output_pix_kernel, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_dec_output_rows<pix_row_pair<true>>(S, cw, ch, w, h, desc, in, L, s);
 }
 }  // namespace h264mi

@@ -31,10 +31,9 @@
 #include "../../include/h264mi.h"
 #include "h264mi_types.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define QDEV __device__ __forceinline__
-
 #define H264MI_QUAL_ROWS 16     // block rows (of windows) per wave
 #define H264MI_QUAL_COLS 63     // block columns (of windows) per wave: 64 lanes, the last one lends its block
 #define H264MI_QUAL_MAX_PAIRS_Y 32768
@@ -52,11 +51,11 @@ struct QualLaunch {
     QualPlane pl[2];         // luma, chroma
 };
 
-QDEV uint32_t qual_ld4(const uint8_t *p, bool narrow) {
+PICDEV uint32_t qual_ld4(const uint8_t *p, bool narrow) {
     if (narrow) return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
     return *(const uint32_t *)p;
 }
-QDEV uint64_t qual_wave_sum(uint64_t v) {
+PICDEV uint64_t qual_wave_sum(uint64_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
     return v;  // lane 0
 }

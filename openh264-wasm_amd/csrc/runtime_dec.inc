@@ -339,8 +339,7 @@ static int dec_frames(DecCtx *c, int n, const DecInput *in, const hipEvent_t *re
         if (streamed && f == 0) HIPCHECK(hipStreamWaitEvent(c->stream, c->ev_parsed[g], 0));
         hipLaunchKernelGGL(dec_end_kernel, dim3((S + 63) / 64), dim3(64), 0, c->stream, DecEndLaunch{S, df, streamed});
         if (outputs && in[0].fmt == H264MI_FMT_LAYOUT) {  // the layout in force travels by value in the launch
-            const auto launch = pix_is_deep(c->out_lay.pix) ? launch_dec_output_pixdeep : launch_dec_output_pix;  // pixdeep.hip, pixfmt.hip
-            if (launch(S, c->cw, c->ch, c->w, c->h, df, c->d_in + (size_t)(slot0 + f) * S, c->out_lay, c->stream) != 0) return -1;
+            if (launch_dec_output_layout(S, c->cw, c->ch, c->w, c->h, df, c->d_in + (size_t)(slot0 + f) * S, c->out_lay, c->stream) != 0) return -1;
         } else if (outputs && in[0].fmt == H264MI_FMT_RGBA && !colorspec_default(c->out_cs)) {  // likewise the specification in force
             if (launch_dec_output_rgba_cs(S, c->cw, c->ch, df, c->d_in + (size_t)(slot0 + f) * S, c->out_cs, c->stream) != 0) return -1;
         } else if (outputs && in[0].fmt == H264MI_FMT_RGBA) {  // every frame's picture to the caller (DecInput::out / got)

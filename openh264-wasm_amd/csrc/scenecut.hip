@@ -33,7 +33,7 @@
 // The double-buffered part[] needs one barrier an item: item i + 2 writes the buffer of item i only after every thread
 // has passed the barrier of item i + 1, that is after its reads of item i.
 // Statistics: a thread keeps the sums of the frame it works on and adds them to memory (one atomic a wave and word,
-// none for a zero) when the frame changes and at the end.
+// none for a zero: picture_dev.h's wave_add_counters) when the frame changes and at the end.
 //
 // A translation unit and a code object of its own, as denoise.hip is: the library's other kernels stay byte for byte
 // what they were. The host runtime (enc_input.inc, capi_enc.inc) reaches it through the functions picture_host.h declares.
@@ -45,10 +45,9 @@
 #include "../../include/h264mi.h"
 #include "h264mi_types.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define NDEV __device__ __forceinline__
-
 #define H264MI_SCENECUT_STRIP 512  // luma samples across a strip: 128 cells, 16 thumbnail blocks
 
 struct ScenecutLaunch {
@@ -61,23 +60,6 @@ struct ScenecutLaunch {
     int level, compensate;
     long long items, per;        // n * nsx * nby; items a block
 };
-
-NDEV uint32_t scenecut_wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-NDEV void scenecut_flush(uint32_t *st, int t, uint32_t s_chg, uint32_t s_blk, uint32_t s_sad, uint32_t s_tc, uint32_t s_tp) {
-    const uint32_t v0 = scenecut_wave_sum(s_chg), v1 = scenecut_wave_sum(s_blk), v2 = scenecut_wave_sum(s_sad),
-                   v3 = scenecut_wave_sum(s_tc), v4 = scenecut_wave_sum(s_tp);
-    if ((t & 63) == 0) {
-        if (v0) atomicAdd(st + 0, v0);
-        if (v1) atomicAdd(st + 1, v1);
-        if (v2) atomicAdd(st + 2, v2);
-        if (v3) atomicAdd(st + 3, v3);
-        if (v4) atomicAdd(st + 4, v4);
-    }
-}
 
 __global__ __launch_bounds__(256) void scenecut_kernel(ScenecutLaunch a) {
     __shared__ uint32_t part[2][3][8][32];  // sad, sum Tc, sum Tp of a thread's four cells: [cell row][16-byte column]
@@ -92,7 +74,7 @@ __global__ __launch_bounds__(256) void scenecut_kernel(ScenecutLaunch a) {
         const int k = (int)(it - f * per_frame);
         const int by = k / a.nsx, sx = k - by * a.nsx;
         if (a.stats && f != sf) {
-            if (sf >= 0) scenecut_flush(a.stats + 8 * sf, t, s_chg, s_blk, s_sad, s_tc, s_tp);
+            if (sf >= 0) wave_add_counters(a.stats + 8 * sf, t & 63, s_chg, s_blk, s_sad, s_tc, s_tp);
             sf = f; s_chg = s_blk = s_sad = s_tc = s_tp = 0;
         }
         const uint8_t *cf = a.cur + (size_t)f * a.fb;
@@ -183,7 +165,7 @@ __global__ __launch_bounds__(256) void scenecut_kernel(ScenecutLaunch a) {
             }
         }
     }
-    if (a.stats && sf >= 0) scenecut_flush(a.stats + 8 * sf, t, s_chg, s_blk, s_sad, s_tc, s_tp);
+    if (a.stats && sf >= 0) wave_add_counters(a.stats + 8 * sf, t & 63, s_chg, s_blk, s_sad, s_tc, s_tp);
 }
 
 // the policy of include/h264mi.h for S streams, one thread each. words: a stream's sixteen -- the frame's eight

@@ -29,7 +29,7 @@
 //
 // Pixelate: a wave owns one cell of one plane of one rectangle. The launch's arguments hold the rectangles and a prefix
 // table of waves per rectangle (overlay.hip's scheme). The lanes read the cell (64 / cw rows at a time), the sum meets
-// in a butterfly of the wave, and every lane stores the mean to the samples it read: a cell reads only what it writes,
+// in a butterfly of the wave (picture_dev.h's wave_sum), and every lane stores the mean to the samples it read: a cell reads only what it writes,
 // so in place needs no scratch and no order. FILL is the same walk with 64 x 64 cells, no read and the fill value.
 //
 // A translation unit and a code object of its own, as denoise.hip is: the library's other kernels stay byte for byte
@@ -41,10 +41,9 @@
 #include <string.h>
 #include "../../include/h264mi.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define NDEV __device__ __forceinline__
-
 #define SP_TW 256                   // samples across a tile
 #define SP_TH 32                    // rows of a tile
 #define SP_ROWS (SP_TH + 2 * 3)     // with the halo rows of the largest radius
@@ -66,17 +65,17 @@ struct SpatialLaunch {
     long long items, per;  // n * per_frame; items a block
 };
 
-NDEV int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+PICDEV int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // the bytes o and o + 1 (o = 1..9) of the twelve bytes d0 d1 d2 in the low bytes of the two halves of a register
-NDEV us2 byte_pair(uint32_t d0, uint32_t d1, uint32_t d2, int o) {
+PICDEV us2 byte_pair(uint32_t d0, uint32_t d1, uint32_t d2, int o) {
     const int j = o >> 2, b = o & 3;
     const uint32_t lo = j == 0 ? d0 : j == 1 ? d1 : d2, hi = j == 0 ? d1 : j == 1 ? d2 : 0u;
     const uint32_t sel = (uint32_t)b | 0x0c00u | ((uint32_t)(b + 1) << 16) | 0x0c000000u;
     return __builtin_bit_cast(us2, __builtin_amdgcn_perm(hi, lo, sel));
 }
 
-NDEV void copy_tile(const uint8_t *S, uint8_t *D, int pw, int x0, int y0, int tw, int th, bool wide, int t) {
+PICDEV void copy_tile(const uint8_t *S, uint8_t *D, int pw, int x0, int y0, int tw, int th, bool wide, int t) {
     const int c = 4 * (t & 63);
     if (c >= tw) return;
     for (int i = t >> 6; i < th; i += 4) {
@@ -90,7 +89,7 @@ NDEV void copy_tile(const uint8_t *S, uint8_t *D, int pw, int x0, int y0, int tw
 }
 
 template <int R>
-NDEV void filter_tile(uint8_t (*sb)[SP_PITCH], uint16_t (*hs)[SP_TW], const uint8_t *S, uint8_t *D, int pw, int ph, int x0, int y0, int tw,
+PICDEV void filter_tile(uint8_t (*sb)[SP_PITCH], uint16_t (*hs)[SP_TW], const uint8_t *S, uint8_t *D, int pw, int ph, int x0, int y0, int tw,
                       int th, bool wide, int amount, int core, int t) {
     const int q = t & 63, wv = t >> 6, c = 4 * q;
     const int nrows = th + 2 * R;
@@ -208,11 +207,6 @@ static inline int privacy_side(const h264mi_privacy &m) { return m.mode == H264M
 static inline int privacy_waves(const h264mi_privacy &m) {
     const int B = privacy_side(m);
     return 3 * ((m.w + B - 1) / B) * ((m.h + B - 1) / B);
-}
-
-NDEV uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 __global__ __launch_bounds__(256) void privacy_kernel(PrivacyLaunch a) {

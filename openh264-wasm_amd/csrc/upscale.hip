@@ -17,12 +17,11 @@
 // row after the window is loaded one step ahead, so its latency lies under the rows that need no load.
 // Bytes are loaded one by one (neighbouring lanes share them when enlarging: a wave's row is 64 p / q + 3 bytes); an
 // output row segment is stored as dwords where its first address is a multiple of 4 and the group of four lies inside
-// the rectangle, else as bytes (compose's rule). Nothing is read outside the crop, nothing written outside the
-// rectangle. No atomics, no device allocation, no host-to-device copy.
+// the rectangle, else as bytes (compose's rule, picture_dev.h's seg_put). Nothing is read outside the crop, nothing
+// written outside the rectangle. No atomics, no device allocation, no host-to-device copy.
 //
-// A translation unit and a code object of its own, as quality.hip, scale.hip, compose.hip and overlay.hip are: the
-// library's other kernels stay byte for byte what they were. Shrinking cells of a compose_any call go to compose.hip's
-// launch_compose_i420 as they are. The host runtime (capi_enc.inc) reaches this file through the functions
+// A translation unit and a code object of its own, as quality.hip, scale.hip, compose.hip and overlay.hip are.
+// Shrinking cells of a compose_any call go to compose.hip's launch_compose_i420 as they are. The host runtime (capi_enc.inc) reaches this file through the functions
 // picture_host.h declares; the checks of a cell list and the cell table of a launch are there too.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -30,10 +29,9 @@
 #include <stdint.h>
 #include "../../include/h264mi.h"
 #include "picture_host.h"
+#include "picture_dev.h"
 
 namespace h264mi {
-#define CDEV __device__ __forceinline__
-
 #define H264MI_UPSCALE_ROWS 32          // output rows per wave
 #define H264MI_UPSCALE_MAX_ITEMS (1 << 30)  // waves' worth of work in one launch
 
@@ -74,7 +72,7 @@ __host__ __device__ static inline int upscale_nseg(int qh) { return (qh + H264MI
 
 struct UpTaps { uint32_t t[4]; };
 // a lane's four taps of one plane row (two for bilinear, whose outer weights are 0)
-CDEV UpTaps up_load(const uint8_t *row, const int *xi, bool cubic) {
+PICDEV UpTaps up_load(const uint8_t *row, const int *xi, bool cubic) {
     UpTaps r;
     r.t[1] = row[xi[1]];
     r.t[2] = row[xi[2]];
@@ -82,7 +80,7 @@ CDEV UpTaps up_load(const uint8_t *row, const int *xi, bool cubic) {
     r.t[3] = cubic ? row[xi[3]] : 0u;
     return r;
 }
-CDEV int up_hfilter(const UpTaps &r, const int *wx) {
+PICDEV int up_hfilter(const UpTaps &r, const int *wx) {
     const int h = wx[0] * (int)r.t[0] + wx[1] * (int)r.t[1] + wx[2] * (int)r.t[2] + wx[3] * (int)r.t[3];
     return (h + 16) >> 5;  // 8 fractional bits, -8160 .. 73440
 }
@@ -117,7 +115,6 @@ __global__ __launch_bounds__(256) void upscale_kernel(UpscaleLaunch a) {
         const int nstrip = upscale_nstrip(qw);
         const int strip = k % nstrip, seg = k / nstrip;
         const int ox = strip * 64 + lane;
-        const bool act = ox < qw;
         // the lane's taps, columns of the crop, and their weights; a lane beyond the rectangle takes the last column's
         int xi[4], wx[4];
         {
@@ -145,18 +142,7 @@ __global__ __launch_bounds__(256) void upscale_kernel(UpscaleLaunch a) {
             up_weights(P & 15, cubic, wy);
             const int acc = wy[0] * H[0] + wy[1] * H[1] + wy[2] * H[2] + wy[3] * H[3];
             const uint32_t v = (uint32_t)min(max((acc + (1 << 20)) >> 21, 0), 255);
-            uint8_t *o = D + (size_t)oy * dpitch + strip * 64;  // the strip's first sample of the row
-            if (((uintptr_t)o & 3) == 0) {
-                uint32_t q = v | (__shfl_down(v, 1) << 8);
-                q |= __shfl_down(q, 2) << 16;  // lanes 4j: the bytes of lanes 4j .. 4j + 3
-                if (act) {
-                    const int base = ox & ~3;
-                    if (base + 3 < qw) { if ((lane & 3) == 0) *(uint32_t *)(o + lane) = q; }
-                    else o[lane] = (uint8_t)v;
-                }
-            } else if (act) {
-                o[lane] = (uint8_t)v;
-            }
+            seg_put(D + (size_t)oy * dpitch + strip * 64, lane, qw - strip * 64, v);  // from the strip's first sample of the row
         }
     }
 }

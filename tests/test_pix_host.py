@@ -270,9 +270,9 @@ def test_device_calls_refuse_bad_arguments_without_a_device(libpath):
             assert to_i420(pa, pb, r, w, h, n, None) == -1 and to_pix(pa, r, pb, w, h, n, None) == -1
         for bw, bh in ((31, 16), (32, 15), (0, 16), (8194, 16), (34, 16)):  # 34: the pitch falls below the row bytes
             assert to_i420(pa, pb, r, bw, bh, 1, None) == -1 and to_pix(pa, r, pb, bw, bh, 1, None) == -1, (bw, bh)
-        for L, _, _, ok in _directed()[:12]:
+        for L, lw, lh, ok in _directed()[:12]:  # at the case's own size: the tight layout is refused for 37x18, not for 36x18
             if not ok and L.pix == pix:
-                assert to_i420(pa, pb, ctypes.byref(_c(L)), 36, 18, 1, None) == -1
+                assert to_i420(pa, pb, ctypes.byref(_c(L)), lw, lh, 1, None) == -1
         # overlapping byte ranges: n * frame_stride on the layout's side, n tight frames on the other
         fs = t.frame_stride
         for n in (1, 3):
