@@ -985,7 +985,7 @@ int h264mi_i420_deinterlace_host(void *dst, const void *cur, const void *prev, i
    previous unfiltered input, device memory allocated when the filter is turned on, freed when it is turned off and at
    destroy -- and h264mi_enc_encode (which then copies the caller's frames into the input area as with an overlay
    list), _encode_rgba and _encode_pix run, on the encoder's stream and in this order: the deinterlacer, the denoiser,
-   the key-frame policy, the overlay list, the frame step. The deinterlacer is one launch in place over the input area
+   the levels stage, the spatial filter, the privacy masks, the key-frame policy, the overlay list, the frame step. The deinterlacer is one launch in place over the input area
    with d_prev = d_prev_out = the state; the first frame after the filter was turned on has no d_prev: it is spatial
    only and stores the state.
      * The filter is only meaningful before any vertical resampling: while it is on, h264mi_enc_encode_scaled,
@@ -1056,7 +1056,7 @@ int h264mi_i420_privacy_host(void *frames, int w, int h, int nframes, const h264
 /* the encoder's spatial filter and privacy masks. Every entry point that codes the input area (h264mi_enc_encode, which
    then copies the caller's frames into the input area as with an overlay list, _rgba, _scaled, _oriented, _pix,
    _composed, _composed_any) runs, on the encoder's stream and in this order: the deinterlacer, the denoiser, the
-   spatial filter, the privacy masks, the key-frame policy, the overlay list, the frame step.
+   levels stage (below), the spatial filter, the privacy masks, the key-frame policy, the overlay list, the frame step.
      * The spatial filter (NULL or an inert setting: off) owns nstreams frames of device memory to filter *into* --
        allocated when it is turned on, freed when it is turned off and at destroy. The later stages and the frame step
        work on that buffer: the denoiser's state never holds a sharpened or masked frame, and sharpen-after-downscale
@@ -1074,6 +1074,112 @@ int h264mi_enc_set_spatial(h264mi_encoder *e, const h264mi_spatial *p);
 int h264mi_enc_spatial(h264mi_encoder *e, h264mi_spatial *out);
 int h264mi_enc_set_privacy(h264mi_encoder *e, const h264mi_privacy *list, int n);
 int h264mi_enc_privacy(h264mi_encoder *e);
+
+/* Histograms, level tables and automatic levels of a picture on the device: what a recorder with
+   dim cameras, washed-out webcams and mislabelled ranges needs in front of the encoder, and the 768 words that exposure
+   monitoring, black-frame and flash detection start from. The library's own rules, exact integers, the same bytes on any
+   host (tests/levelsref.py restates them in numpy). A frame is tight I420, w x h, both sides even, 2..8192.
+   Histogram. H[plane][v] is the number of samples of plane `plane` (0 Y, 1 Cb, 2 Cr) with value v: 768 uint32_t a frame,
+     plane after plane. The largest count is 8192 * 8192 = 2^26. The counts are sums of integers: the order of
+     accumulation does not matter.
+   LUT. A table set is 768 bytes, T[0] for Y, T[1] for Cb, T[2] for Cr. C the source sample, O the output: O = T[plane][C].
+   Levels. A linear stretch of luma between two ends, measured (AUTO) or given (FIXED), and a chroma gain about 128.
+     mode              H264MI_LEVELS_AUTO or H264MI_LEVELS_FIXED
+     clip_lo, clip_hi  0..4096   AUTO: the share of the luma samples, in 1/65536, that may fall below / above the measured end
+     in_lo, in_hi      0..255    FIXED: in_lo < in_hi; ignored in AUTO
+     out_lo, out_hi    0..255    out_lo < out_hi: the range the ends are mapped to (16, 235 for limited range)
+     max_gain          64..1024  AUTO: the largest stretch, in 1/64 units
+     speed             1..256    AUTO: the share of 256 by which the smoothed ends follow the measured ones; 256 = no memory
+     sat               0..255    chroma gain about 128 in 1/64 units; 64 leaves chroma as it is
+   Fields a mode ignores must still be in their ranges.
+     Measured ends (AUTO): npix = w * h, H the luma histogram. k_lo = (clip_lo * npix) >> 16, k_hi = (clip_hi * npix) >> 16,
+       in 64 bits. lo_m is the smallest v with sum_{u <= v} H[u] > k_lo, hi_m the largest v with sum_{u >= v} H[u] > k_hi.
+       Both exist (the whole sum is npix > k). lo_m <= hi_m: were hi_m < lo_m, then sum_{u < lo_m} H[u] <= k_lo (lo_m is the
+       smallest) and sum_{u >= lo_m} H[u] <= sum_{u > hi_m} H[u] <= k_hi (hi_m is the largest), so npix <= k_lo + k_hi
+       <= 2 * 4096 * npix / 65536 = npix / 8, which is false.
+     Smoothed ends, in 1/256 of a level. The state is 4 int32_t a stream: {has, lo_s, hi_s, 0}. With has == 0:
+       lo_s = lo_m << 8, hi_s = hi_m << 8, has = 1. Otherwise lo_s += (((lo_m << 8) - lo_s) * speed) >> 8 and the same
+       for hi_s; the shift is arithmetic (floor). So a downward difference always moves the end (by at least 1/256), an
+       upward one of d with d * speed < 256 moves nothing: the end stalls up to (256 - 1) / speed below its target. The
+       update is monotone in the end and in the target, so lo_s <= hi_s holds from frame to frame. The fourth word is
+       written 0. A state is the library's own: words that no call produced give tables without meaning, never a fault.
+     Gain limit: R = out_hi - out_lo, min_span = max(16, (R * 64 * 256) / max_gain) (floor; at most 65280). If
+       hi_s - lo_s < min_span then lo_e = (lo_s + hi_s - min_span) >> 1 (arithmetic), hi_e = lo_e + min_span; otherwise
+       lo_e = lo_s, hi_e = hi_s. lo_e may be negative (at least -32640), hi_e may exceed 65280 (at most 97920).
+     FIXED: lo_e = in_lo << 8, hi_e = in_hi << 8. No histogram, no state.
+     Luma table: t = (v << 8) - lo_e, span = hi_e - lo_e (at least 16). t <= 0: T[0][v] = out_lo. Otherwise
+       T[0][v] = min(out_hi, out_lo + (t * R + span / 2) / span). Bounds: 0 < t <= 65280 + 32640 = 97920, R <= 255,
+       span <= 65280, so t * R + span / 2 <= 24969600 + 32640 < 2^25: every operand is non-negative and below 2^31.
+       The table never decreases with v.
+     Chroma tables: T[1][v] = T[2][v] = clip(0, 255, 128 + (((v - 128) * sat + 32) >> 6)), the shift arithmetic.
+       sat == 64 gives the identity.
+     Record, optional, 8 int32_t a frame: {lo_m, hi_m, lo_s, hi_s, lo_e, hi_e, below, above}; below is the number of luma
+       samples with (v << 8) < lo_e, above the number with (v << 8) > hi_e. In FIXED mode, where no histogram is made,
+       the record is {0, 0, 0, 0, lo_e, hi_e, 0, 0}.
+   A FIXED setting with in_lo == out_lo, in_hi == out_hi and sat == 64 is inert: its tables are the identity between the
+   ends and on chroma (luma outside in_lo..in_hi would be clamped to the ends, and only that). An encoder takes an inert
+   setting as "off": nothing is launched and no sample changes. The standalone call applies the tables as they are.
+   Not provided: gamma or any curve but the linear one (callers pass their own tables to the LUT call), chroma that
+   follows the luma gain, a reset at a scene cut, per-stream parameters, decoder-side use, the N-API and JS surfaces. */
+#define H264MI_LEVELS_AUTO 0
+#define H264MI_LEVELS_FIXED 1
+typedef struct { int32_t mode, clip_lo, clip_hi, in_lo, in_hi, out_lo, out_hi, max_gain, speed, sat; } h264mi_levels; /* 40 bytes */
+/* host only: 0 when every field of *p is in its range, -1 otherwise (a null pointer included) */
+int h264mi_levels_ok(const h264mi_levels *p);
+/* async on hip_stream: the 768 words of each of the n >= 1 frames at d_frames into d_hist (n * 768 uint32_t, frame after
+   frame), which the call zeroes on the stream and then accumulates: one memset and one launch. The frames at any
+   alignment. Returns 0, or -1 before anything is enqueued on: a null pointer, an odd side or one outside 2..8192,
+   n < 1, d_hist not at a multiple of 4, any byte d_hist shares with the frames. */
+int h264mi_i420_hist_dev(void *d_hist, const void *d_frames, int w, int h, int n, void *hip_stream);
+/* async on hip_stream: O = T[plane][C] for the n frames at d_src into the n frames at d_dst, one launch. d_dst == d_src
+   exactly (in place: a lane reads its samples before it writes them) or the two share no byte. per_frame 0: the one
+   table set at d_luts serves all n frames; 1: n sets, frame f uses d_luts + 768 f. Any alignment of everything.
+   Nothing outside the n destination frames is written. Returns 0, or -1 before anything is enqueued on: a null pointer,
+   a bad side, n < 1, per_frame other than 0 or 1, a partial overlap of d_dst and d_src, any byte the tables share with
+   the destination. */
+int h264mi_i420_lut_dev(void *d_dst, const void *d_src, int w, int h, int n, const void *d_luts, int per_frame, void *hip_stream);
+/* the bytes of d_work for n frames: n * (768 * 4 + 768), the histograms and then the table sets (a multiple of 4 as it is) */
+size_t h264mi_levels_work_bytes(int n);
+/* async on hip_stream: the levels of n frames that are n independent streams, d_src into d_dst (equal or disjoint as
+   above). d_state: null (every frame is a first frame) or n * 4 int32_t, read and advanced (AUTO only). d_record: null
+   or n * 8 int32_t. d_work: the caller's memory, h264mi_levels_work_bytes(n) bytes; the words and tables stay there
+   after the call. d_state, d_record and d_work at multiples of 4. AUTO launches the histogram (and its memset), the
+   decide kernel and the apply kernel; FIXED the decide kernel, whose tables come from the parameters alone, and the
+   apply kernel. Returns 0, or -1 before anything is enqueued on: a null d_dst, d_src, p or d_work, a bad side, n < 1,
+   parameters h264mi_levels_ok refuses, a misaligned word buffer, a partial overlap of d_dst and d_src, any byte that
+   d_state, d_record or d_work share with each other or with the frames. */
+int h264mi_i420_levels_dev(void *d_dst, const void *d_src, int w, int h, int n, const h264mi_levels *p, void *d_state,
+                           void *d_record, void *d_work, void *hip_stream);
+/* host only: the same rules for one frame in host memory as plain loops (the restatements the device is tested
+   against). _hist_host: hist receives 768 words. _lut_host: dst may be src. h264mi_levels_lut_host: the decision for
+   one frame -- hist_y the 256 luma words (AUTO; ignored in FIXED, may be null there), state4 null (a first frame) or the
+   stream's four words, advanced (AUTO); record8 null or the frame's eight words. Return 0, or -1 on a null pointer
+   that is needed, a bad side or parameter. */
+int h264mi_i420_hist_host(uint32_t *hist, const void *frame, int w, int h);
+int h264mi_i420_lut_host(void *dst, const void *src, int w, int h, const uint8_t *lut768);
+int h264mi_levels_lut_host(uint8_t *lut768, const uint32_t *hist_y, int w, int h, const h264mi_levels *p, int32_t *state4, int32_t *record8);
+/* the encoder's levels stage (NULL or an inert setting: off). It runs behind the denoiser and in front of the spatial
+   filter, in place on the input area: the order is the deinterlacer, the denoiser, the levels stage, the spatial
+   filter, the privacy masks, the key-frame policy, the overlay list, the frame step. So the deinterlacer's and the
+   denoiser's states never hold a levelled frame -- they compare frames of the same exposure even while the ends move --,
+   the sharpening works on the stretched picture, and masks, the key-frame policy, labels and quality records see what
+   is coded. On, the encoder owns per stream 768 histogram words, 768 table bytes, 4 state words and 8 record words,
+   allocated when the stage is turned on, freed when it is turned off and at destroy. AUTO: three launches a frame step.
+   FIXED: the tables are written once by the setter, on the encoder's stream; a frame step adds the apply launch only.
+     * The state advances on every submitted frame: also on one the rate control skips and on a frame step that fails.
+     * h264mi_enc_force_idr does not reset it. Turning the stage off drops the state: on again, the next frame is a
+       first frame. Setting other parameters while it is on keeps the state.
+     * No entry point is refused. Off (the default) nothing changes: no launch, no allocation. The drop-in functions
+       never use it.
+   h264mi_enc_set_levels returns 0, or -1 with the setting in force unchanged on a null encoder, parameters
+   h264mi_levels_ok refuses, or a failed allocation or launch; h264mi_enc_levels returns 1 (on, *out filled when out is
+   not null), 0 (off, *out untouched) or -1 (a null encoder). h264mi_enc_levels_record copies the eight record words of
+   each of the nstreams streams (nstreams must be the encoder's) as of the last submitted frame to out and synchronises
+   the encoder's stream, like h264mi_enc_scenecut_state; before the first frame the words are 0 (AUTO) or the setter's
+   (FIXED). It returns 0, or -1 on a null pointer, the stage off or another stream count. */
+int h264mi_enc_set_levels(h264mi_encoder *e, const h264mi_levels *p);
+int h264mi_enc_levels(h264mi_encoder *e, h264mi_levels *out);
+int h264mi_enc_levels_record(h264mi_encoder *e, int32_t *out, int nstreams);
 
 /* library self-description */
 const char *h264mi_version(void);

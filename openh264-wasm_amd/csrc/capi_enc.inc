@@ -248,6 +248,45 @@ int h264mi_enc_set_spatial(h264mi_encoder *e, const h264mi_spatial *p) { return 
 int h264mi_enc_spatial(h264mi_encoder *e, h264mi_spatial *out) { return e ? stage_get(e->c->in.sp, out) : -1; }
 int h264mi_enc_set_privacy(h264mi_encoder *e, const h264mi_privacy *list, int n) { return e ? enc_set_privacy(e->c, list, n) : -1; }
 int h264mi_enc_privacy(h264mi_encoder *e) { return e ? (int)e->c->in.pv.list.size() : -1; }
+// Histograms, level tables and automatic levels (DESIGN.md §5.19; levels.hip; the checks: picture_host.h)
+int h264mi_levels_ok(const h264mi_levels *p) { return levels_ok(p) ? 0 : -1; }
+int h264mi_i420_hist_dev(void *d_hist, const void *d_frames, int w, int h, int n, void *hip_stream) {
+    if (!hist_args_ok(d_hist, d_frames, w, h, n)) return -1;
+    return launch_hist_i420((uint32_t *)d_hist, (const uint8_t *)d_frames, w, h, n, (hipStream_t)hip_stream);
+}
+int h264mi_i420_lut_dev(void *d_dst, const void *d_src, int w, int h, int n, const void *d_luts, int per_frame, void *hip_stream) {
+    if (!lut_args_ok(d_dst, d_src, w, h, n, d_luts, per_frame)) return -1;
+    return launch_lut_i420((uint8_t *)d_dst, (const uint8_t *)d_src, w, h, n, (const uint8_t *)d_luts, per_frame, (hipStream_t)hip_stream);
+}
+size_t h264mi_levels_work_bytes(int n) { return n < 1 ? 0 : levels_work_bytes(n); }
+int h264mi_i420_levels_dev(void *d_dst, const void *d_src, int w, int h, int n, const h264mi_levels *p, void *d_state, void *d_record,
+                           void *d_work, void *hip_stream) {
+    if (!levels_args_ok(d_dst, d_src, w, h, n, p, d_state, d_record, d_work)) return -1;
+    return launch_levels_i420((uint8_t *)d_dst, (const uint8_t *)d_src, w, h, n, *p, (int32_t *)d_state, (int32_t *)d_record, (uint8_t *)d_work,
+                              (hipStream_t)hip_stream);
+}
+int h264mi_i420_hist_host(uint32_t *hist, const void *frame, int w, int h) {
+    if (!hist || !frame || !canvas_ok(w, h)) return -1;
+    hist_frame_host(hist, (const uint8_t *)frame, w, h);
+    return 0;
+}
+int h264mi_i420_lut_host(void *dst, const void *src, int w, int h, const uint8_t *lut768) {
+    if (!dst || !src || !lut768 || !canvas_ok(w, h)) return -1;
+    lut_frame_host((uint8_t *)dst, (const uint8_t *)src, w, h, lut768);
+    return 0;
+}
+int h264mi_levels_lut_host(uint8_t *lut768, const uint32_t *hist_y, int w, int h, const h264mi_levels *p, int32_t *state4, int32_t *record8) {
+    if (!lut768 || !canvas_ok(w, h) || !levels_ok(p) || (p->mode == H264MI_LEVELS_AUTO && !hist_y)) return -1;
+    levels_lut_host(lut768, hist_y, w, h, *p, state4, record8);
+    return 0;
+}
+int h264mi_enc_set_levels(h264mi_encoder *e, const h264mi_levels *p) { return e ? enc_set_levels(e->c, p) : -1; }
+int h264mi_enc_levels(h264mi_encoder *e, h264mi_levels *out) { return e ? stage_get(e->c->in.lv, out) : -1; }
+int h264mi_enc_levels_record(h264mi_encoder *e, int32_t *out, int nstreams) {
+    if (!e || !out || !e->c->in.lv.on || nstreams != e->c->S) return -1;
+    if (hipMemcpyAsync(out, e->c->in.lv.record(e->c->S), 32 * (size_t)e->c->S, hipMemcpyDeviceToHost, e->c->stream) != hipSuccess) return -1;
+    return hipStreamSynchronize(e->c->stream) == hipSuccess ? 0 : -1;
+}
 // The scene-cut detector (DESIGN.md §5.14; scenecut.hip; the checks: picture_host.h): n frames, one launch
 int h264mi_scenecut_ok(const h264mi_scenecut *p) { return scenecut_ok(p) ? 0 : -1; }
 int h264mi_thumb_size(int w, int h, int *tw, int *th) {

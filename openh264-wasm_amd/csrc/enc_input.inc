@@ -20,7 +20,7 @@ template <class T> static int state_ensure(T *&p, size_t bytes) {
 }
 // enc_free's part. Nothing waits here: h264mi_enc_destroy has synchronised the stream, the wrapper's encoder has no stage
 static void enc_input_release(EncCtx *c) {
-    state_free(c->in.di.d_prev); state_free(c->in.dn.d_prev); state_free(c->in.sp.d_buf); state_free(c->in.sc.d_words);
+    state_free(c->in.di.d_prev); state_free(c->in.dn.d_prev); state_free(c->in.lv.d_mem); state_free(c->in.sp.d_buf); state_free(c->in.sc.d_words);
     state_free(c->in.sc.d_thumb);
 }
 
@@ -29,7 +29,10 @@ static void enc_input_release(EncCtx *c) {
 // deinterlace.hip; nothing when off) -- in place against the previous unfiltered frames, which the same launch
 // replaces; the first frame spatial only --, the pre-filter in force (DESIGN.md §5.13; denoise.hip;
 // nothing when off) -- the first frame only copied to the state, every later one filtered in place against the state,
-// which receives the same bytes --, the spatial filter in force (DESIGN.md §5.18; spatial.hip; nothing when off) -- out
+// which receives the same bytes --, the levels stage in force (DESIGN.md §5.19; levels.hip; nothing when off) -- in place
+// on the input area: AUTO the histogram, the decision, which advances the stream's ends, and the tables' application,
+// FIXED the application of the tables the setter wrote; the two states in front of it never hold a levelled frame --,
+// the spatial filter in force (DESIGN.md §5.18; spatial.hip; nothing when off) -- out
 // of place into the stage's own frames, which are the current frames `cur` of everything behind it, so the denoiser's
 // state never holds a sharpened frame --, the privacy masks in force (the same unit; nothing without a list) in place
 // on the current frames, the key-frame policy in force (below), the overlay list in force blended into them
@@ -50,6 +53,15 @@ static int enc_code_input(EncCtx *c) {
         } else if (launch_denoise_i420(c->d_src, in.dn.d_prev, c->d_src, in.dn.d_prev, c->w, c->h, c->S, in.dn.p, nullptr, c->stream) != 0) {
             return -1;
         }
+    }
+    if (in.lv.on) {
+        EncInput::Levels &l = in.lv;
+        if (l.p.mode == H264MI_LEVELS_AUTO) {
+            if (launch_hist_i420(l.hist(), c->d_src, c->w, c->h, c->S, c->stream) != 0 ||
+                launch_levels_decide(l.luts(c->S), l.hist(), l.state(c->S), l.record(c->S), c->w, c->h, c->S, l.p, c->stream) != 0)
+                return -1;
+        }
+        if (launch_lut_i420(c->d_src, c->d_src, c->w, c->h, c->S, l.luts(c->S), 1, c->stream) != 0) return -1;
     }
     if (in.sp.on) {
         if (launch_spatial_i420(in.sp.d_buf, cur, c->w, c->h, c->S, in.sp.p, c->stream) != 0) return -1;
@@ -76,7 +88,7 @@ static int enc_code_input(EncCtx *c) {
     return enc_frame(c, cur);
 }
 // h264mi_enc_encode: with every stage off the caller's frames are coded where they lie; with the deinterlacer, the
-// pre-filter, the spatial filter or the key-frame policy on or a mask or overlay list in force they are copied into the input area, filtered,
+// pre-filter, the levels stage, the spatial filter or the key-frame policy on or a mask or overlay list in force they are copied into the input area, filtered,
 // looked at and blended there and coded from there
 static int enc_encode(EncCtx *c, const void *d_frames) {
     if (!c->in.any()) return enc_frame(c, (const uint8_t *)d_frames);
@@ -117,6 +129,25 @@ static int enc_set_denoise(EncCtx *c, const h264mi_denoise *p) {
 static int enc_set_deinterlace(EncCtx *c, const h264mi_deinterlace *p) {
     if (p && !deinterlace_ok(p)) return -1;
     return set_prev_frame_stage(c, c->in.di, p, !p);
+}
+// the levels stage: NULL or an inert setting turn it off and free its words. They are allocated, and the state and the
+// record zeroed on the stream, when it is turned on; a change of the parameters keeps them. FIXED: the tables and the
+// record come from the parameters alone and are written here, once, in stream order behind the frames submitted so far
+static int enc_set_levels(EncCtx *c, const h264mi_levels *p) {
+    if (p && !levels_ok(p)) return -1;
+    EncInput::Levels &l = c->in.lv;
+    if (!p || levels_inert(*p)) { state_drop(c, l.d_mem); l.on = false; return 0; }
+    if (!canvas_ok(c->w, c->h)) return -1;
+    const int fresh = state_ensure(l.d_mem, EncInput::Levels::bytes(c->S));
+    if (fresh < 0) return -1;
+    if ((fresh && hipMemsetAsync(l.state(c->S), 0, 48 * (size_t)c->S, c->stream) != hipSuccess) ||
+        (p->mode == H264MI_LEVELS_FIXED &&
+         launch_levels_decide(l.luts(c->S), nullptr, nullptr, l.record(c->S), c->w, c->h, c->S, *p, c->stream) != 0)) {
+        if (fresh) { state_drop(c, l.d_mem); l.on = false; }  // an earlier setting's words stay, and stay in force
+        return -1;
+    }
+    l.p = *p; l.on = true;
+    return 0;
 }
 // the spatial filter: NULL or an inert setting turn it off and free the frames it filtered into
 static int enc_set_spatial(EncCtx *c, const h264mi_spatial *p) {

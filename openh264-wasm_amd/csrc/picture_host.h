@@ -1,5 +1,5 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip, pixdeep.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, pixdeep.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip, levels.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
@@ -332,6 +332,71 @@ static inline bool privacy_ok(const h264mi_privacy *list, int n, int w, int h, i
     return true;
 }
 
+// ---- histograms, level tables and automatic levels (include/h264mi.h)
+constexpr int LEVELS_MAX_CLIP = 4096, LEVELS_MIN_GAIN = 64, LEVELS_MAX_GAIN = 1024, LEVELS_MAX_SPEED = 256;
+constexpr size_t LEVELS_HIST_BYTES = 768 * sizeof(uint32_t), LEVELS_LUT_BYTES = 768;
+static inline bool levels_ok(const h264mi_levels *p) {
+    if (!p || (p->mode != H264MI_LEVELS_AUTO && p->mode != H264MI_LEVELS_FIXED)) return false;
+    if (p->clip_lo < 0 || p->clip_lo > LEVELS_MAX_CLIP || p->clip_hi < 0 || p->clip_hi > LEVELS_MAX_CLIP) return false;
+    if ((uint32_t)p->in_lo > 255 || (uint32_t)p->in_hi > 255 || (uint32_t)p->out_lo > 255 || (uint32_t)p->out_hi > 255) return false;
+    if (p->out_lo >= p->out_hi || (p->mode == H264MI_LEVELS_FIXED && p->in_lo >= p->in_hi)) return false;
+    return p->max_gain >= LEVELS_MIN_GAIN && p->max_gain <= LEVELS_MAX_GAIN && p->speed >= 1 && p->speed <= LEVELS_MAX_SPEED &&
+           (uint32_t)p->sat <= 255;
+}
+// a good setting whose tables are the identity between the ends and on chroma: "off" for an encoder
+static inline bool levels_inert(const h264mi_levels &p) {
+    return p.mode == H264MI_LEVELS_FIXED && p.in_lo == p.out_lo && p.in_hi == p.out_hi && p.sat == 64;
+}
+// the thresholds of the measured ends: the only 64-bit arithmetic of the rule
+static inline uint32_t levels_clip_count(int clip, int w, int h) { return (uint32_t)(((uint64_t)clip * ((uint64_t)w * h)) >> 16); }
+// a smoothed end after a frame whose measured end is m
+__host__ __device__ static inline int levels_follow(int s, int m, int speed) { return s + ((((m << 8) - s) * speed) >> 8); }
+// the effective ends of AUTO from the smoothed ones
+__host__ __device__ static inline void levels_limit(int lo_s, int hi_s, int R, int max_gain, int &lo_e, int &hi_e) {
+    int min_span = (R * 64 * 256) / max_gain;
+    if (min_span < 16) min_span = 16;
+    if (hi_s - lo_s < min_span) { lo_e = (lo_s + hi_s - min_span) >> 1; hi_e = lo_e + min_span; }
+    else { lo_e = lo_s; hi_e = hi_s; }
+}
+// the table entries of value v
+__host__ __device__ static inline int levels_luma(int v, int lo_e, int hi_e, int out_lo, int out_hi) {
+    const int t = (v << 8) - lo_e, span = hi_e - lo_e, R = out_hi - out_lo;
+    if (t <= 0) return out_lo;
+    const int o = out_lo + (t * R + span / 2) / span;
+    return o < out_hi ? o : out_hi;
+}
+__host__ __device__ static inline int levels_chroma(int v, int sat) {
+    const int o = 128 + (((v - 128) * sat + 32) >> 6);
+    return o < 0 ? 0 : o > 255 ? 255 : o;
+}
+// arguments of the three calls, the pointers' values included. dst == src, or no byte in common
+static inline bool hist_args_ok(const void *hist, const void *frames, int w, int h, int n) {
+    if (!hist || !frames || n < 1 || !canvas_ok(w, h) || ((uintptr_t)hist & 3)) return false;
+    return !byte_ranges_overlap(hist, (size_t)n * LEVELS_HIST_BYTES, frames, (size_t)n * i420_bytes(w, h));
+}
+static inline bool lut_args_ok(const void *dst, const void *src, int w, int h, int n, const void *luts, int per_frame) {
+    if (!dst || !src || !luts || n < 1 || !canvas_ok(w, h) || (per_frame != 0 && per_frame != 1)) return false;
+    const size_t nb = (size_t)n * i420_bytes(w, h);
+    if (dst != src && byte_ranges_overlap(dst, nb, src, nb)) return false;
+    return !byte_ranges_overlap(dst, nb, luts, (per_frame ? (size_t)n : 1) * LEVELS_LUT_BYTES);
+}
+static inline size_t levels_work_bytes(int n) { return (size_t)n * (LEVELS_HIST_BYTES + LEVELS_LUT_BYTES); }
+static inline bool levels_args_ok(const void *dst, const void *src, int w, int h, int n, const h264mi_levels *p, const void *state,
+                                  const void *record, const void *work) {
+    if (!dst || !src || !work || n < 1 || !canvas_ok(w, h) || !levels_ok(p)) return false;
+    if ((((uintptr_t)state) | ((uintptr_t)record) | ((uintptr_t)work)) & 3) return false;
+    const size_t nb = (size_t)n * i420_bytes(w, h);
+    if (dst != src && byte_ranges_overlap(dst, nb, src, nb)) return false;
+    const void *r[5] = {dst, src, work, state, record};
+    const size_t rb[5] = {nb, nb, levels_work_bytes(n), 16 * (size_t)n, 32 * (size_t)n};
+    for (int a = 0; a < 5; a++)
+        for (int b = (a == 0 ? 2 : a + 1); b < 5; b++) {  // dst against src is settled above
+            if (!r[a] || !r[b]) continue;
+            if (byte_ranges_overlap(r[a], rb[a], r[b], rb[b])) return false;
+        }
+    return true;
+}
+
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
 static inline int cell_kind(const h264mi_cell &c) {
@@ -456,6 +521,17 @@ int launch_spatial_i420(uint8_t *dst, const uint8_t *src, int w, int h, int n, c
 void spatial_frame_host(uint8_t *out, const uint8_t *src, int w, int h, const h264mi_spatial &p);
 int launch_privacy_i420(uint8_t *frames, int w, int h, const h264mi_privacy *list, int nlist, hipStream_t s);
 void privacy_frames_host(uint8_t *frames, int w, int h, const h264mi_privacy *list, int nlist);
+// levels.hip: arguments as hist_args_ok / lut_args_ok / levels_args_ok accept them. The decide launch: hist null in FIXED
+// mode, state and record may be null; luts receives n table sets. The _host functions: the same rules as plain loops
+int launch_hist_i420(uint32_t *hist, const uint8_t *frames, int w, int h, int n, hipStream_t s);
+int launch_lut_i420(uint8_t *dst, const uint8_t *src, int w, int h, int n, const uint8_t *luts, int per_frame, hipStream_t s);
+int launch_levels_decide(uint8_t *luts, const uint32_t *hist, int32_t *state, int32_t *record, int w, int h, int n, const h264mi_levels &p,
+                         hipStream_t s);
+int launch_levels_i420(uint8_t *dst, const uint8_t *src, int w, int h, int n, const h264mi_levels &p, int32_t *state, int32_t *record,
+                       uint8_t *work, hipStream_t s);
+void hist_frame_host(uint32_t *hist, const uint8_t *frame, int w, int h);
+void lut_frame_host(uint8_t *dst, const uint8_t *src, int w, int h, const uint8_t *lut768);
+void levels_lut_host(uint8_t *lut768, const uint32_t *hist_y, int w, int h, const h264mi_levels &p, int32_t *state4, int32_t *record8);
 // pixfmt.hip, pixdeep.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);

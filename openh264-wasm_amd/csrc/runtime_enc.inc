@@ -163,6 +163,15 @@ struct EncInput {
         bool on = false, has = false; h264mi_denoise p = {};
         uint8_t *d_prev = nullptr;  // the S previous filtered frames
     } dn;
+    struct Levels {  // the levels stage: h264mi_enc_set_levels; levels.hip. The state's first word is the stream's `has`
+        bool on = false; h264mi_levels p = {};
+        uint8_t *d_mem = nullptr;  // per stream 768 histogram words, then 768 table bytes, 4 state words, 8 record words
+        uint32_t *hist() const { return (uint32_t *)d_mem; }
+        uint8_t *luts(int S) const { return d_mem + (size_t)S * 3072; }
+        int32_t *state(int S) const { return (int32_t *)(d_mem + (size_t)S * 3840); }
+        int32_t *record(int S) const { return (int32_t *)(d_mem + (size_t)S * 3856); }
+        static size_t bytes(int S) { return (size_t)S * 3888; }
+    } lv;
     struct Spatial {  // the sharpen/blur filter: h264mi_enc_set_spatial; spatial.hip
         bool on = false; h264mi_spatial p = {};
         uint8_t *d_buf = nullptr;  // the S frames it filters into: what the later stages and the frame step work on
@@ -180,7 +189,7 @@ struct EncInput {
         const uint8_t *sprites = nullptr;
         int w = 0, h = 0;  // the sprites' size
     } ov;
-    bool any() const { return di.on || dn.on || sp.on || !pv.list.empty() || sc.on || !ov.list.empty(); }
+    bool any() const { return di.on || dn.on || lv.on || sp.on || !pv.list.empty() || sc.on || !ov.list.empty(); }
 };
 
 struct EncCtx {

@@ -203,6 +203,17 @@ def lib():
             'h264mi_enc_spatial': (i, [vp, vp]),
             'h264mi_enc_set_privacy': (i, [vp, vp, i]),
             'h264mi_enc_privacy': (i, [vp]),
+            'h264mi_levels_ok': (i, [vp]),
+            'h264mi_i420_hist_dev': (i, [vp, vp, i, i, i, vp]),
+            'h264mi_i420_lut_dev': (i, [vp, vp, i, i, i, vp, i, vp]),
+            'h264mi_levels_work_bytes': (ctypes.c_size_t, [i]),
+            'h264mi_i420_levels_dev': (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp]),
+            'h264mi_i420_hist_host': (i, [vp, vp, i, i]),
+            'h264mi_i420_lut_host': (i, [vp, vp, i, i, vp]),
+            'h264mi_levels_lut_host': (i, [vp, vp, i, i, vp, vp, vp]),
+            'h264mi_enc_set_levels': (i, [vp, vp]),
+            'h264mi_enc_levels': (i, [vp, vp]),
+            'h264mi_enc_levels_record': (i, [vp, vp, i]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -554,6 +565,29 @@ class BatchEncoder:
     def denoise(self):
         """the pre-filter in force: a Denoise (a copy), or None when it is off (h264mi_enc_denoise)"""
         return self._get_stage('denoise', Denoise)
+
+    def set_levels(self, params):
+        """the levels stage of every encode*() from its next call on (h264mi_enc_set_levels): a Levels, a (mode, clip_lo,
+        clip_hi, in_lo, in_hi, out_lo, out_hi, max_gain, speed, sat) tuple, or None for off (a FIXED setting whose
+        tables are the identity is off too). On, the encoder owns per stream 768 histogram words, 768 table bytes, 4
+        state words and 8 record words and levels the input area in place behind the denoiser and in front of the
+        spatial filter, the privacy masks, the key-frame policy and the overlay list; encode() then codes a copy of the
+        caller's frames. The smoothed ends advance on every submitted frame; a change of the parameters keeps them, off
+        drops them. ValueError, with the setting in force unchanged, on parameters levels_ok refuses."""
+        self._set_stage('levels', Levels, params)
+
+    def levels(self):
+        """the levels setting in force: a Levels (a copy), or None when the stage is off (h264mi_enc_levels)"""
+        return self._get_stage('levels', Levels)
+
+    def levels_record(self):
+        """the S streams' records of the last submitted frame (h264mi_enc_levels_record; waits for the encoder's
+        stream): a list of S lists {lo_m, hi_m, lo_s, hi_s, lo_e, hi_e, below, above}. RuntimeError with the stage off."""
+        out = (ctypes.c_int32 * (8 * self.S))()
+        if self._L.h264mi_enc_levels_record(self._e, out, self.S) != 0:
+            raise RuntimeError('h264mi_enc_levels_record failed')
+        v = list(out)
+        return [v[8 * s:8 * s + 8] for s in range(self.S)]
 
     def set_spatial(self, params):
         """the sharpen/blur filter of every encode*() from its next call on (h264mi_enc_set_spatial): a Spatial, a
@@ -1411,6 +1445,80 @@ def i420_spatial(dst, src, w, h, n, params, stream=None):
     assert dst.numel() >= need and src.numel() >= need
     d = Spatial._of(params)
     if lib().h264mi_i420_spatial_dev(_ptr(dst), _ptr(src), w, h, n, _byref(d), _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
+
+
+LEVELS_AUTO = 0   # H264MI_LEVELS_AUTO: the ends are measured from each frame's luma histogram and smoothed
+LEVELS_FIXED = 1  # H264MI_LEVELS_FIXED: the ends are in_lo and in_hi
+LEVELS_RECORD = ('lo_m', 'hi_m', 'lo_s', 'hi_s', 'lo_e', 'hi_e', 'below', 'above')  # a frame's eight record words
+
+
+class Levels(_Record):
+    """h264mi_levels (include/h264mi.h): mode LEVELS_AUTO or LEVELS_FIXED, clip_lo, clip_hi 0..4096 (AUTO: the share of
+    the luma samples, in 1/65536, that may fall below / above the measured end), in_lo < in_hi 0..255 (FIXED), out_lo <
+    out_hi 0..255 (the range the ends are mapped to), max_gain 64..1024 (AUTO, in 1/64 units), speed 1..256 (AUTO; 256 =
+    no memory), sat 0..255 (chroma gain about 128 in 1/64 units; 64 leaves chroma as it is). 40 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('mode', 'clip_lo', 'clip_hi', 'in_lo', 'in_hi', 'out_lo', 'out_hi', 'max_gain', 'speed', 'sat')]
+
+
+def levels_ok(params):
+    """0 when every field of params (a Levels or ten integers) is in its range, else -1 (None included);
+    h264mi_levels_ok, host only"""
+    return lib().h264mi_levels_ok(_byref(Levels._of(params)))
+
+
+def levels_work_bytes(n):
+    """the bytes of i420_levels' work tensor for n frames (h264mi_levels_work_bytes): n histograms, then n table sets"""
+    return int(lib().h264mi_levels_work_bytes(int(n)))
+
+
+def _assert_dev_words(t, nbytes):
+    """t is None or a contiguous device tensor of at least nbytes bytes"""
+    if t is not None:
+        assert t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= nbytes
+
+
+def i420_hist(hist, frames, w, h, n, stream=None):
+    """the histograms of n tight w x h I420 frames (uint8 CUDA tensor frames, any alignment) into hist (a CUDA tensor of
+    768 n 32-bit words at a multiple of 4: per frame 256 counts of Y, of Cb, of Cr), zeroed and then accumulated on the
+    stream; one launch, async on stream (default: the current one); h264mi_i420_hist_dev. The words equal
+    tests/levelsref.py's. ValueError on a bad argument."""
+    _assert_dev_u8(frames)
+    ok = n > 0 and min(w, h) > 0
+    assert frames.numel() >= (n * _i420_bytes(w, h) if ok else 0)
+    _assert_dev_words(hist, 3072 * max(n, 0))
+    if lib().h264mi_i420_hist_dev(_ptr(hist), _ptr(frames), w, h, n, _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}')
+
+
+def i420_lut(dst, src, w, h, n, luts, per_frame=False, stream=None):
+    """n tight w x h I420 frames (uint8 CUDA tensor src, any alignment) through table sets of 768 bytes (T[0] for Y, T[1]
+    for Cb, T[2] for Cr: O = T[plane][C]) into dst, which may be src itself; luts: one set for all frames, or with
+    per_frame n sets; one launch, async on stream (default: the current one); h264mi_i420_lut_dev. The bytes equal
+    tests/levelsref.py's. ValueError on a bad argument (dst and src that overlap in part, tables inside dst)."""
+    _assert_dev_u8(dst, src, luts)
+    need = 0 if n <= 0 or min(w, h) <= 0 else n * _i420_bytes(w, h)
+    assert dst.numel() >= need and src.numel() >= need and luts.numel() >= 768 * (max(n, 1) if per_frame else 1)
+    if lib().h264mi_i420_lut_dev(_ptr(dst), _ptr(src), w, h, n, _ptr(luts), 1 if per_frame else 0, _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {w}x{h}, per_frame={per_frame}')
+
+
+def i420_levels(dst, src, w, h, n, params, work, state=None, record=None, stream=None):
+    """the levels of n tight w x h I420 frames that are n independent streams (uint8 CUDA tensor src, any alignment) into
+    dst, which may be src itself; async on stream (default: the current one); h264mi_i420_levels_dev. params: a Levels
+    or its ten integers. work: a CUDA tensor of levels_work_bytes(n) bytes at a multiple of 4. state: None (every frame
+    is a first frame) or 4 n int32 words, read and advanced in AUTO mode; record: None or 8 n int32 words (LEVELS_RECORD).
+    AUTO is the histogram, the decision and the tables' application; FIXED the last two. Bytes and words equal
+    tests/levelsref.py's. ValueError on a bad argument."""
+    _assert_dev_u8(dst, src)
+    need = 0 if n <= 0 or min(w, h) <= 0 else n * _i420_bytes(w, h)
+    assert dst.numel() >= need and src.numel() >= need
+    _assert_dev_words(work, levels_work_bytes(n))
+    _assert_dev_words(state, 16 * max(n, 0))
+    _assert_dev_words(record, 32 * max(n, 0))
+    d = Levels._of(params)
+    if lib().h264mi_i420_levels_dev(_ptr(dst), _ptr(src), w, h, n, _byref(d), _ptr(state), _ptr(record), _ptr(work),
+                                    _hip_stream(stream)) != 0:
         raise ValueError(f'bad arguments: {n} frames {w}x{h}, {d!r}')
 
 

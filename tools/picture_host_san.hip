@@ -1,12 +1,13 @@
 // picture_host_san.hip -- the host rules of the picture calls (csrc/picture_host.h and the host halves of scale.hip,
-// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
+// compose.hip, overlay.hip, upscale.hip, orient.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip, levels.hip) run under AddressSanitizer and UBSan on the CPU. A program of its own: nothing
 // is loaded into Python, no kernel is launched, no device is needed.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=all tools/picture_host_san.hip openh264-wasm_amd/csrc/scale.hip \
 //         openh264-wasm_amd/csrc/compose.hip openh264-wasm_amd/csrc/overlay.hip openh264-wasm_amd/csrc/upscale.hip \
 //         openh264-wasm_amd/csrc/orient.hip openh264-wasm_amd/csrc/denoise.hip openh264-wasm_amd/csrc/scenecut.hip \
-//         openh264-wasm_amd/csrc/deinterlace.hip openh264-wasm_amd/csrc/spatial.hip -o picture_host_san && ./picture_host_san
+//         openh264-wasm_amd/csrc/deinterlace.hip openh264-wasm_amd/csrc/spatial.hip openh264-wasm_amd/csrc/levels.hip \
+//         -o picture_host_san && ./picture_host_san
 //
 // It runs, with every table in a heap block of exactly the size the call may touch:
 //   * cells_ok (both values of may_enlarge) on valid lists and on every field of a cell made odd, negative, one past the
@@ -43,6 +44,11 @@
 //     parameter sets against a restatement that sums columns first and floors without a shift, the masks of three lists
 //     on three frames against a per-sample restatement; spatial_ok, spatial_args_ok and privacy_ok at their limits and
 //     one past each, lists of 4096 entries and one more.
+//   * levels.hip's host restatements hist_frame_host, lut_frame_host and levels_lut_host on heap blocks of exactly the
+//     frame's, the histogram's, the tables', the state's and the record's bytes at six sizes x three contents x eight
+//     parameter sets, without a state, as a first and as a later frame, against a second statement (counts from sorted
+//     samples, sums taken afresh in 64 bits, the division as a search); levels_ok one past every limit, the clip counts
+//     at the limits, hist_args_ok, lut_args_ok and levels_args_ok at the edges of every overlap and alignment rule.
 // Prints one line per group and "ok"; exits 1 at the first difference.
 #include <cstdio>
 #include <cstdlib>
@@ -987,7 +993,136 @@ static void check_spatial() {
            frames, nlists);
 }
 
+// ---- levels.hip's host restatements against a second statement of the rules: counts by sorting the samples, the ends
+// from sums taken afresh for every bin in 64 bits, the table entries in 64 bits with the division written as a search
+static void check_levels() {
+    const int sizes[6][2] = {{2, 2}, {4, 4}, {16, 16}, {36, 18}, {130, 66}, {64, 48}};
+    const h264mi_levels sets[8] = {{0, 0, 0, 0, 0, 0, 255, 1024, 256, 64},  {0, 0, 0, 0, 0, 16, 235, 64, 256, 64},  {0, 2048, 2048, 0, 0, 16, 235, 256, 37, 64},
+                                   {0, 4096, 4096, 0, 0, 0, 255, 1024, 37, 0}, {0, 0, 4096, 0, 0, 0, 255, 64, 255, 80}, {0, 4096, 0, 0, 0, 0, 1, 1024, 1, 255},
+                                   {1, 0, 0, 16, 235, 0, 255, 64, 1, 64},    {1, 4096, 4096, 100, 101, 0, 255, 1024, 256, 255}};
+    uint32_t seed = 99;
+    auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return seed >> 24; };
+    int frames = 0;
+    for (const auto &sz : sizes) {
+        const int w = sz[0], h = sz[1];
+        const size_t nb = i420_bytes(w, h), ly = (size_t)w * h, lc = (size_t)(w / 2) * (h / 2);
+        for (int content = 0; content < 3; content++) {
+            std::unique_ptr<uint8_t[]> src(new uint8_t[nb]), out(new uint8_t[nb]), want(new uint8_t[nb]);
+            for (size_t i = 0; i < nb; i++) src[i] = content == 0 ? (uint8_t)rnd() : content == 1 ? (uint8_t)(20 + rnd() % 41) : (uint8_t)(i < ly / 32 ? 0 : i + ly / 32 + 1 >= ly && i < ly ? 255 : 77);
+            std::unique_ptr<uint32_t[]> hist(new uint32_t[768]);
+            hist_frame_host(hist.get(), src.get(), w, h);
+            const size_t len[3] = {ly, lc, lc};
+            size_t at = 0;
+            for (int pl = 0; pl < 3; at += len[pl], pl++) {
+                std::vector<uint8_t> sorted(src.get() + at, src.get() + at + len[pl]);
+                std::sort(sorted.begin(), sorted.end());
+                for (int v = 0; v < 256; v++)
+                    CHECK(hist[256 * pl + v] == (uint32_t)(std::upper_bound(sorted.begin(), sorted.end(), (uint8_t)v) - std::lower_bound(sorted.begin(), sorted.end(), (uint8_t)v)));
+            }
+            std::unique_ptr<int32_t[]> state(new int32_t[4]), rec(new int32_t[8]);
+            std::unique_ptr<uint8_t[]> lut(new uint8_t[768]);
+            for (const auto &p : sets) {
+                CHECK(levels_ok(&p));
+                for (int pass = 0; pass < 3; pass++) {  // no state, a first frame, a later frame
+                    const int32_t st0[4] = {pass == 2 ? 1 : 0, 31 * 256 + 7, 200 * 256 - 9, 5};
+                    memcpy(state.get(), st0, sizeof st0);
+                    levels_lut_host(lut.get(), p.mode == H264MI_LEVELS_AUTO ? hist.get() : nullptr, w, h, p, pass ? state.get() : nullptr, rec.get());
+                    int64_t lo_e, hi_e;
+                    if (p.mode == H264MI_LEVELS_FIXED) {
+                        lo_e = 256 * (int64_t)p.in_lo; hi_e = 256 * (int64_t)p.in_hi;
+                        CHECK(rec[0] == 0 && rec[1] == 0 && rec[2] == 0 && rec[3] == 0 && rec[6] == 0 && rec[7] == 0);
+                        CHECK(!pass || memcmp(state.get(), st0, sizeof st0) == 0);
+                    } else {
+                        const int64_t npix = (int64_t)w * h, k_lo = p.clip_lo * npix / 65536, k_hi = p.clip_hi * npix / 65536;
+                        int lo_m = -1, hi_m = -1;
+                        for (int v = 0; v < 256; v++) {
+                            int64_t le = 0, ge = 0;
+                            for (int u = 0; u <= v; u++) le += hist[u];
+                            for (int u = v; u < 256; u++) ge += hist[u];
+                            if (le > k_lo && lo_m < 0) lo_m = v;
+                            if (ge > k_hi) hi_m = v;
+                        }
+                        CHECK(lo_m >= 0 && lo_m <= hi_m && rec[0] == lo_m && rec[1] == hi_m);
+                        int64_t lo_s = 256 * lo_m, hi_s = 256 * hi_m;
+                        if (pass == 2) {
+                            auto floor_div = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+                            lo_s = st0[1] + floor_div((256 * (int64_t)lo_m - st0[1]) * p.speed, 256);
+                            hi_s = st0[2] + floor_div((256 * (int64_t)hi_m - st0[2]) * p.speed, 256);
+                        }
+                        CHECK(rec[2] == lo_s && rec[3] == hi_s);
+                        if (pass) CHECK(state[0] == 1 && state[1] == lo_s && state[2] == hi_s && state[3] == 0);
+                        const int64_t R = p.out_hi - p.out_lo, min_span = std::max<int64_t>(16, R * 16384 / p.max_gain);
+                        lo_e = lo_s; hi_e = hi_s;
+                        if (hi_s - lo_s < min_span) {
+                            const int64_t sum = lo_s + hi_s - min_span;
+                            lo_e = sum >= 0 ? sum / 2 : -((-sum + 1) / 2);
+                            hi_e = lo_e + min_span;
+                        }
+                        int64_t below = 0, above = 0;
+                        for (int v = 0; v < 256; v++) { below += 256 * v < lo_e ? hist[v] : 0; above += 256 * v > hi_e ? hist[v] : 0; }
+                        CHECK(rec[6] == below && rec[7] == above);
+                    }
+                    CHECK(rec[4] == lo_e && rec[5] == hi_e && hi_e - lo_e >= 16);
+                    const int64_t R = p.out_hi - p.out_lo, span = hi_e - lo_e;
+                    for (int v = 0; v < 256; v++) {
+                        const int64_t t = 256 * v - lo_e;
+                        int64_t y = p.out_lo;
+                        if (t > 0) {
+                            int64_t q = 0;  // the largest q with q span <= t R + span / 2
+                            while ((q + 1) * span <= t * R + span / 2 && q < R) q++;
+                            y = p.out_lo + q;
+                        }
+                        CHECK(lut[v] == y);
+                        const int64_t g = (int64_t)(v - 128) * p.sat + 32, c = 128 + (g >= 0 ? g / 64 : -((-g + 63) / 64));
+                        CHECK(lut[256 + v] == std::min<int64_t>(255, std::max<int64_t>(0, c)) && lut[512 + v] == lut[256 + v]);
+                    }
+                    lut_frame_host(out.get(), src.get(), w, h, lut.get());
+                    at = 0;
+                    for (int pl = 0; pl < 3; at += len[pl], pl++)
+                        for (size_t i = 0; i < len[pl]; i++) want[at + i] = lut[256 * pl + src[at + i]];
+                    CHECK(memcmp(out.get(), want.get(), nb) == 0);
+                    memcpy(out.get(), src.get(), nb);
+                    lut_frame_host(out.get(), out.get(), w, h, lut.get());  // in place
+                    CHECK(memcmp(out.get(), want.get(), nb) == 0);
+                }
+            }
+            frames++;
+        }
+    }
+    // the ok-function one past every limit, the clip counts at the limit, the calls' argument checks
+    const h264mi_levels good = {0, 100, 100, 10, 20, 16, 235, 256, 37, 64};
+    CHECK(levels_ok(&good) && !levels_ok(nullptr) && !levels_inert(good));
+    const int lim[9][2] = {{0, 4096}, {0, 4096}, {0, 255}, {0, 255}, {0, 255}, {0, 255}, {64, 1024}, {1, 256}, {0, 255}};
+    for (int k = 0; k < 9; k++)
+        for (int e = 0; e < 2; e++) {
+            h264mi_levels b = good;
+            (&b.clip_lo)[k] = lim[k][e] + (e ? 1 : -1);
+            CHECK(!levels_ok(&b));
+        }
+    { h264mi_levels b = good; b.mode = 2; CHECK(!levels_ok(&b)); b.mode = -1; CHECK(!levels_ok(&b)); }
+    { h264mi_levels b = good; b.out_hi = b.out_lo; CHECK(!levels_ok(&b)); b.mode = 1; b.out_hi = 235; b.in_hi = b.in_lo; CHECK(!levels_ok(&b)); b.in_hi = b.in_lo + 1; CHECK(levels_ok(&b)); }
+    { h264mi_levels b = {1, 7, 7, 16, 235, 16, 235, 99, 9, 64}; CHECK(levels_ok(&b) && levels_inert(b)); b.sat = 65; CHECK(!levels_inert(b)); }
+    CHECK(levels_clip_count(4096, 8192, 8192) == (1u << 22) && levels_clip_count(0, 8192, 8192) == 0 && levels_clip_count(4096, 2, 2) == 0 && levels_clip_count(4096, 4, 4) == 1);
+    CHECK(levels_work_bytes(1) == 3840 && levels_work_bytes(128) == 128 * 3840);
+    alignas(16) static uint8_t arena[1 << 16];
+    uint8_t *A = arena;
+    const size_t fb = i420_bytes(32, 16);
+    CHECK(hist_args_ok(A, A + 8192, 32, 16, 2) && !hist_args_ok(A + 1, A + 8192, 32, 16, 2) && !hist_args_ok(A, A + 6140, 32, 16, 2) && hist_args_ok(A, A + 6144, 32, 16, 2));
+    CHECK(!hist_args_ok(nullptr, A, 32, 16, 1) && !hist_args_ok(A, nullptr, 32, 16, 1) && !hist_args_ok(A, A + 8192, 32, 16, 0) && !hist_args_ok(A, A + 8192, 31, 16, 1));
+    CHECK(lut_args_ok(A, A, 32, 16, 2, A + 8192, 1) && lut_args_ok(A, A + 2 * fb, 32, 16, 2, A + 8192, 0) && !lut_args_ok(A, A + 1, 32, 16, 2, A + 8192, 1));
+    CHECK(!lut_args_ok(A, A, 32, 16, 2, A + 2 * fb - 1, 0) && lut_args_ok(A, A, 32, 16, 2, A + 2 * fb, 0) && !lut_args_ok(A + 767, A + 8192, 32, 16, 1, A, 1));
+    CHECK(lut_args_ok(A + 768, A + 8192, 32, 16, 1, A, 0) && !lut_args_ok(A + 768, A + 8192, 32, 16, 1, A, 2) && !lut_args_ok(A, A, 32, 16, 2, nullptr, 0));
+    uint8_t *W = A + 16384, *S = A + 32768, *Rc = A + 40960;
+    CHECK(levels_args_ok(A, A, 32, 16, 2, &good, S, Rc, W) && levels_args_ok(A, A + 2 * fb, 32, 16, 2, &good, nullptr, nullptr, W));
+    CHECK(!levels_args_ok(A, A + 4, 32, 16, 2, &good, S, Rc, W) && !levels_args_ok(A, A, 32, 16, 2, &good, S + 2, Rc, W) && !levels_args_ok(A, A, 32, 16, 2, &good, S, Rc + 1, W));
+    CHECK(!levels_args_ok(A, A, 32, 16, 2, &good, S, Rc, W + 3) && !levels_args_ok(A, A, 32, 16, 2, &good, S, Rc, nullptr) && !levels_args_ok(A, A, 32, 16, 2, nullptr, S, Rc, W));
+    CHECK(!levels_args_ok(A, A, 32, 16, 2, &good, S, S + 28, W) && levels_args_ok(A, A, 32, 16, 2, &good, S, S + 32, W) && !levels_args_ok(A, A, 32, 16, 2, &good, W + 7676, Rc, W));
+    CHECK(levels_args_ok(A, A, 32, 16, 2, &good, W + 7680, Rc, W) && !levels_args_ok(A, A, 32, 16, 2, &good, S, Rc, A + 2 * fb - 4) && !levels_args_ok(W, A, 32, 16, 2, &good, S, Rc, W));
+    printf("levels: %d frames at 6 sizes x 8 parameter sets x (no state, first frame, later frame): histogram, decision, tables, lookup in place and out; ok-function, clip counts and argument checks\n", frames);
+}
+
 int main() {
+    check_levels();
     check_spatial();
     check_deinterlace();
     check_scenecut();
