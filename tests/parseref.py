@@ -425,6 +425,7 @@ class _Picture:
         self.why = [np.zeros(a.shape, np.int8) for a in self.tc]
         self.done = np.zeros(mbw * mbh, bool)
         self.words = {}     # macroblock address -> its logged code words
+        self.span = {}      # macroblock address -> (first bit, one past the last bit) of its macroblock_layer()
         self.nslices = 0
 
 
@@ -436,6 +437,12 @@ class Parsed:
     def __init__(self, pic, size, counts, ref_idc):
         self.syntax, self.geometry, self.size, self.counts, self.ref_idc = pic.syntax, (pic.mbw, pic.mbh), size, counts, ref_idc
         self._words = pic.words
+        self._span = pic.span
+
+    def layer_span(self, mb):
+        """(first bit, one past the last bit) of macroblock mb's macroblock_layer() in its slice's RBSP, the mb_skip_run in
+        front of it not included; None for a skipped macroblock, which has no macroblock_layer()"""
+        return self._span.get(mb)
 
     def words(self, mb):
         """the logged code words of macroblock mb: (name, first bit, one past the last bit, value), positions in its
@@ -626,7 +633,9 @@ class _Slice:
                         raise ParseError('slice data past the end of the picture')
             r.log = pic.words.setdefault(addr, [])
             r.log.extend(pending)
+            layer = r.p
             self.macroblock_layer(addr)
+            pic.span[addr] = (layer, r.p)
             bits = r.p - start
             if bits > 16 * 32:
                 c[('mb_dwords', 'gt16')] += 1
