@@ -1181,6 +1181,93 @@ int h264mi_enc_set_levels(h264mi_encoder *e, const h264mi_levels *p);
 int h264mi_enc_levels(h264mi_encoder *e, h264mi_levels *out);
 int h264mi_enc_levels_record(h264mi_encoder *e, int32_t *out, int nstreams);
 
+/* Warping along a mesh on the device: a wide-angle room camera's barrel distortion removed, a
+   whiteboard camera's keystone taken out, a handheld camera's per-frame stabilising shift and rotation, a ceiling
+   camera a few degrees off level. The one picture call that moves samples along lines other than the axes. Exact
+   integers, int32 throughout on the device; the project's own rule.
+   Mesh. The destination picture is dw x dh, the source sw x sh, both tight I420 with even sides in 2..8192; the two
+   sizes are independent. A mesh has a pitch of G = 1 << grid_log2 destination luma samples, grid_log2 in 3..5, and
+   mw x mh control points, mw = ((dw + G - 1) >> grid_log2) + 1, mh likewise from dh (h264mi_warp_mesh_size). Point
+   (i, j) belongs to destination luma position (i G, j G); it is two int32_t, x then y: the source luma position in
+   sixteenths of a sample, 0 the centre of sample 0. A value is clamped to -2^18 .. 2^18 as it is read, so any bytes
+   form a valid mesh. Row-major, mw points a row, at an address that is a multiple of 4; one mesh for all n frames
+   (mesh_per_frame 0) or n meshes back to back (1).
+   Position of an output sample, on a doubled grid so that luma and chroma share one rule: a luma sample ox has
+   u = 2 ox, a chroma sample cx has u = 4 cx + 1 (the centre of its 2 x 2); v likewise from the row. The cell is
+   (u >> (grid_log2 + 1), v >> (grid_log2 + 1)), its points A (the cell's own), B (the next across), C (the next down),
+   D (both); the fractions are fx = u & (2G - 1), fy = v & (2G - 1). Per coordinate
+     P = (2G - fx)(2G - fy) A + fx (2G - fy) B + (2G - fx) fy C + fx fy D        |P| <= 4 G^2 2^18 = 2^30
+     luma    L = floor((P + 2 G^2) / (4 G^2))
+     chroma  L = floor((P - 28 G^2) / (8 G^2))        (the luma position - 1/2) / 2, rounded the same way
+     i = L >> 4 (arithmetic), f = L & 15
+   Sample. Per axis the taps i - 1 .. i + 2, each clamped to the source plane (0 .. p - 1), under the weights of
+   phase f of h264mi_i420_upscale_dev for the call's filter (H264MI_FILTER_BILINEAR / _BICUBIC). Horizontal first,
+   H = (sum Wx p + 16) >> 5, then out = clamp((sum Wy H + 2^20) >> 21, 0, 255): the upscaler's arithmetic unchanged.
+   edge H264MI_WARP_CLAMP uses that as it stands; with H264MI_WARP_FILL a sample whose L is below 0 or above
+   16 (p - 1) in either axis, p the plane's source side, takes the plane's fill value (fill_y, fill_u, fill_v).
+   Nothing outside the source planes is read, whatever the mesh holds; nothing outside the destination frames is
+   written. The same bytes from run to run, equal to a restatement on any host (h264mi_i420_warp_host).
+   Consequences: the identity mesh (x = 16 i G, y = 16 j G, sw x sh = dw x dh) copies the frame; a mesh of whole even
+   sample shifts copies a shifted frame (edge samples repeat, or the fill); a mesh whose points are an affine map is
+   that map at every sample without error, so the eight meshes of the orientations' index maps (x = 16 (sw - 1 - ox)
+   for MIRROR, ...) give h264mi_i420_orient_dev's bytes, the transposing ones with dw x dh = sh x sw included.
+   Minification is not antialiased: a mesh that shrinks reads four taps per axis whatever the step; shrink with
+   h264mi_i420_scale_dev first. */
+#define H264MI_WARP_CLAMP 0
+#define H264MI_WARP_FILL 1
+typedef struct { int32_t filter, edge, fill_y, fill_u, fill_v, grid_log2; } h264mi_warp; /* 24 bytes */
+/* host only: 0 when filter is one of the two, edge is one of the two, the fills are in 0..255 and grid_log2 in 3..5;
+   else -1 (a null pointer included) */
+int h264mi_warp_ok(const h264mi_warp *p);
+/* host only: the control points *mw x *mh of a mesh for a dw x dh destination. Returns 0, or -1 with nothing written
+   on a null pointer, a side that is odd or outside 2..8192, or grid_log2 outside 3..5 */
+int h264mi_warp_mesh_size(int dw, int dh, int grid_log2, int *mw, int *mh);
+/* host only, integers only: builders that fill the caller's mesh (2 mw mh int32_t) for a dw x dh destination. With
+   X = i G, Y = j G the point's destination position in luma samples; every result clamped to -2^18 .. 2^18. Each
+   returns the number of points mw mh, or -1 with nothing written on a null pointer, a bad side or grid_log2, or what
+   its own rule refuses.
+     _affine: six coefficients in Q16 (m2, m5 in samples), sums in 64 bits:
+         x = (m0 X + m1 Y + m2 + 2^11) >> 12,  y = (m3 X + m4 Y + m5 + 2^11) >> 12
+     _homography: nine coefficients in Q16: den = h6 X + h7 Y + h8, x = floor((32 (h0 X + h1 Y + h2) + den) / (2 den)),
+         the rounded quotient 16 num / den, y likewise from h3, h4, h5; 64 bits. -1 if den <= 0 at any control point.
+     _radial: removes lens distortion. (cx, cy) the centre in sixteenths, r2 a reference radius squared in sixteenths
+         squared, k1 and k2 signed Q16. With dx = 16 X - cx, dy = 16 Y - cy:
+           q = floor(((dx^2 + dy^2) << 16) / r2)
+           s = 65536 + ((k1 q) >> 16) + ((k2 ((q q) >> 16)) >> 16)
+           x = cx + ((dx s + 2^15) >> 16),  y = cy + ((dy s + 2^15) >> 16)
+         Limits, beyond each of which the call returns -1: |cx|, |cy| <= 2^18, 1 <= r2 <= 2^40, |k1|, |k2| <= 2^20, and
+         q <= 2^24 at every control point (none further than 16 reference radii from the centre). With them
+         dx^2 + dy^2 < 2^39, its shift < 2^55, |k1 q| <= 2^44, q q <= 2^48, |k2 (q q >> 16)| <= 2^52, |s| < 2^37 and
+         |dx s| < 2^56: every product stays inside 64 bits. Other fisheye models are not provided. */
+int h264mi_warp_mesh_affine(int32_t *mesh, int dw, int dh, int grid_log2, const int32_t m[6]);
+int h264mi_warp_mesh_homography(int32_t *mesh, int dw, int dh, int grid_log2, const int32_t h[9]);
+int h264mi_warp_mesh_radial(int32_t *mesh, int dw, int dh, int grid_log2, int cx, int cy, int64_t r2, int k1, int k2);
+/* host only: how the kernel reads the source for tile (tx, ty) -- the samples of mesh cell (tx, ty) -- of plane 0..2
+   under a host copy of the mesh: 0 when the tile's source footprint (the bounding box of its four corner samples'
+   positions plus the tap margin, clamped to the plane) has at most 2048 samples and is staged in LDS, 1 when it is
+   sampled from global memory. The bytes are the same either way. -1 on a bad argument. */
+int h264mi_warp_tile_class(const int32_t *mesh, int dw, int dh, int sw, int sh, int grid_log2, int plane, int tx, int ty);
+/* async on hip_stream: n tight sw x sh I420 frames back to back at d_src (any alignment) warped to n tight dw x dh
+   frames at d_dst under the mesh(es) at d_mesh (device; mesh_per_frame 0: one for all, 1: n back to back), one launch
+   per 2^30 tiles. Returns 0, or -1 before anything is enqueued on a null pointer, a side that is odd or outside
+   2..8192, n < 1, a setting h264mi_warp_ok refuses, mesh_per_frame neither 0 nor 1, a mesh address that is no multiple
+   of 4, or a destination byte range that overlaps the source or the mesh. Antialiased minification, Lanczos, warps
+   inside compose cells, warped sprites and RGBA frames are not provided. */
+int h264mi_i420_warp_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, const void *d_mesh, int mesh_per_frame,
+                         const h264mi_warp *p, void *hip_stream);
+/* host only: the rule above as plain loops on one frame in host memory, what the device call is compared against.
+   Returns 0, or -1 on what h264mi_i420_warp_dev refuses of one frame */
+int h264mi_i420_warp_host(void *dst, int dw, int dh, const void *src, int sw, int sh, const int32_t *mesh, const h264mi_warp *p);
+/* async, as h264mi_enc_encode_oriented, from nstreams tight src_w x src_h I420 frames back to back (device, any
+   alignment): one launch of h264mi_i420_warp_dev on the encoder's stream warps them into the input area under the mesh
+   at d_mesh (mesh_per_stream 0: one for all streams, 1: one each), then the stages in force and the frame step run
+   as in h264mi_enc_encode; the quality records compare the warped source with the reconstruction. Frames and mesh
+   are read by that launch only. Returns -1 and enqueues nothing -- the encoder's next step is as if the call had not
+   happened -- on whatever h264mi_i420_warp_dev refuses for the encoder's width x height, on frames or a mesh that
+   overlap the input area, and while the deinterlacer is on. */
+int h264mi_enc_encode_warped(h264mi_encoder *e, const void *d_frames, int src_w, int src_h, const void *d_mesh, int mesh_per_stream,
+                             const h264mi_warp *p);
+
 /* library self-description */
 const char *h264mi_version(void);
 

@@ -4,7 +4,7 @@ import os, subprocess, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 # one code object each: the codec, then the picture units (see the files)
 UNITS = ('h264mi_kernels', 'quality', 'scale', 'compose', 'overlay', 'upscale', 'orient', 'pixfmt', 'pixdeep', 'colorspace', 'denoise',
-         'scenecut', 'deinterlace', 'spatial', 'levels')
+         'scenecut', 'deinterlace', 'spatial', 'levels', 'warp')
 OUT = os.path.join(HERE, 'lib', 'libh264mi.so')
 
 

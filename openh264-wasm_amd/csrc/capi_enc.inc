@@ -404,6 +404,56 @@ int h264mi_enc_encode_oriented(h264mi_encoder *e, const void *d_frames, int orie
     if (launch_orient_i420(c->d_src, (const uint8_t *)d_frames, sw, sh, c->S, orient, c->stream) != 0) return -1;
     return enc_code_input(c);
 }
+// The mesh warp (DESIGN.md §5.20; warp.hip; the checks: picture_host.h): n frames, one launch up to 2^30 tiles
+int h264mi_warp_ok(const h264mi_warp *p) { return warp_ok(p) ? 0 : -1; }
+int h264mi_warp_mesh_size(int dw, int dh, int grid_log2, int *mw, int *mh) {
+    if (!mw || !mh || !canvas_ok(dw, dh) || !warp_grid_ok(grid_log2)) return -1;
+    *mw = warp_mesh_side(dw, grid_log2); *mh = warp_mesh_side(dh, grid_log2);
+    return 0;
+}
+int h264mi_warp_mesh_affine(int32_t *mesh, int dw, int dh, int grid_log2, const int32_t m[6]) { return warp_mesh_affine(mesh, dw, dh, grid_log2, m); }
+int h264mi_warp_mesh_homography(int32_t *mesh, int dw, int dh, int grid_log2, const int32_t h[9]) {
+    return warp_mesh_homography(mesh, dw, dh, grid_log2, h);
+}
+int h264mi_warp_mesh_radial(int32_t *mesh, int dw, int dh, int grid_log2, int cx, int cy, int64_t r2, int k1, int k2) {
+    return warp_mesh_radial(mesh, dw, dh, grid_log2, cx, cy, r2, k1, k2);
+}
+int h264mi_warp_tile_class(const int32_t *mesh, int dw, int dh, int sw, int sh, int grid_log2, int plane, int tx, int ty) {
+    return warp_tile_class(mesh, dw, dh, sw, sh, grid_log2, plane, tx, ty);
+}
+int h264mi_i420_warp_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, const void *d_mesh, int mesh_per_frame,
+                         const h264mi_warp *p, void *hip_stream) {
+    if (!warp_args_ok(d_dst, dw, dh, d_src, sw, sh, n, d_mesh, mesh_per_frame, p)) return -1;
+    return launch_warp_i420((uint8_t *)d_dst, dw, dh, (const uint8_t *)d_src, sw, sh, n, (const int32_t *)d_mesh, mesh_per_frame, *p, 0,
+                            (hipStream_t)hip_stream);
+}
+int h264mi_i420_warp_host(void *dst, int dw, int dh, const void *src, int sw, int sh, const int32_t *mesh, const h264mi_warp *p) {
+    if (!warp_args_ok(dst, dw, dh, src, sw, sh, 1, mesh, 0, p)) return -1;
+    warp_frame_host((uint8_t *)dst, dw, dh, (const uint8_t *)src, sw, sh, mesh, *p);
+    return 0;
+}
+// nstreams tight src_w x src_h I420 frames back to back: one batched warp into the encoder's own input area on its
+// stream, then the frame step as h264mi_enc_encode runs it. Every refusal comes before the first launch
+int h264mi_enc_encode_warped(h264mi_encoder *e, const void *d_frames, int src_w, int src_h, const void *d_mesh, int mesh_per_stream,
+                             const h264mi_warp *p) {
+    if (!e || enc_resampling_refused(e->c)) return -1;
+    EncCtx *c = e->c;
+    if (!warp_args_ok(c->d_src, c->w, c->h, d_frames, src_w, src_h, c->S, d_mesh, mesh_per_stream, p)) return -1;
+    if (launch_warp_i420(c->d_src, c->w, c->h, (const uint8_t *)d_frames, src_w, src_h, c->S, (const int32_t *)d_mesh, mesh_per_stream, *p, 0,
+                         c->stream) != 0)
+        return -1;
+    return enc_code_input(c);
+}
+// measurement only (tools/warp_ab.py), not declared in the header: h264mi_i420_warp_dev with the path of this one
+// call given -- 0 as the call chooses, 1 every tile from global memory. No state is kept
+int h264mi_i420_warp_path_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, const void *d_mesh, int mesh_per_frame,
+                              const h264mi_warp *p, int path, void *hip_stream);
+int h264mi_i420_warp_path_dev(void *d_dst, int dw, int dh, const void *d_src, int sw, int sh, int n, const void *d_mesh, int mesh_per_frame,
+                              const h264mi_warp *p, int path, void *hip_stream) {
+    if (!warp_args_ok(d_dst, dw, dh, d_src, sw, sh, n, d_mesh, mesh_per_frame, p) || (path != 0 && path != 1)) return -1;
+    return launch_warp_i420((uint8_t *)d_dst, dw, dh, (const uint8_t *)d_src, sw, sh, n, (const int32_t *)d_mesh, mesh_per_frame, *p, path,
+                            (hipStream_t)hip_stream);
+}
 // Pixel formats and pitched layouts (DESIGN.md §5.10; pixfmt.hip; the rules: picture_host.h): n frames, one launch
 int h264mi_pix_layout_tight(h264mi_pix_layout *out, int pix, int w, int h) { return pix_layout_tight(out, pix, w, h); }
 int64_t h264mi_pix_span(const h264mi_pix_layout *layout, int w, int h) { return pix_span(layout, w, h); }

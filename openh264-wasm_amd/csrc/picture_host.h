@@ -1,5 +1,5 @@
 // picture_host.h -- the host half that the picture code objects (scale.hip, compose.hip, overlay.hip, upscale.hip, orient.hip,
-// pixfmt.hip, pixdeep.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip, levels.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
+// pixfmt.hip, pixdeep.hip, colorspace.hip, denoise.hip, scenecut.hip, deinterlace.hip, spatial.hip, levels.hip, warp.hip) and the runtime (runtime_enc.inc, enc_input.inc, runtime_dec.inc, capi_enc.inc, capi_dec.inc) share: byte counts, the limits of a call, the checks of a cell
 // list, the cell table of a launch, the layouts' fit, and the declaration of every function a code object exports to
 // the runtime. Host only: nothing here is compiled for the device but the plain 24-byte PictureCell, which the compose
 // and upscale launch structs hold, and the plain 60-byte CsCoef, which the colour launches hold. DESIGN.md §5.8.
@@ -397,6 +397,47 @@ static inline bool levels_args_ok(const void *dst, const void *src, int w, int h
     return true;
 }
 
+// ---- the sixteen-phase interpolation weights (upscale.hip, warp.hip; include/h264mi.h)
+// the four weights of phase f (0..15), sum 8192
+__host__ __device__ static inline void up_weights(int f, bool cubic, int *w) {
+    if (cubic) {
+        const int f2 = f * f, f3 = f2 * f;
+        w[0] = -f3 + 32 * f2 - 256 * f;
+        w[1] = 3 * f3 - 80 * f2 + 8192;
+        w[2] = -3 * f3 + 64 * f2 + 256 * f;
+        w[3] = f3 - 16 * f2;
+    } else {
+        w[0] = 0; w[1] = (16 - f) * 512; w[2] = f * 512; w[3] = 0;
+    }
+}
+
+// ---- the mesh warp (include/h264mi.h)
+constexpr int WARP_MIN_GRID = 3, WARP_MAX_GRID = 5;
+constexpr int WARP_POINT_MAX = 1 << 18;  // a control point's coordinates are clamped to +-this, in sixteenths of a sample
+// the radial builder's limits: with them every product of its rule stays inside 64 bits (warp.hip has the sums)
+constexpr int WARP_RADIAL_MAX_CENTRE = 1 << 18, WARP_RADIAL_MAX_K = 1 << 20;
+constexpr int64_t WARP_RADIAL_MAX_R2 = (int64_t)1 << 40, WARP_RADIAL_MAX_Q = (int64_t)1 << 24;
+static inline bool warp_grid_ok(int grid_log2) { return grid_log2 >= WARP_MIN_GRID && grid_log2 <= WARP_MAX_GRID; }
+static inline bool warp_ok(const h264mi_warp *p) {
+    return p && filter_ok(p->filter) && (p->edge == H264MI_WARP_CLAMP || p->edge == H264MI_WARP_FILL) && (uint32_t)p->fill_y <= 255 &&
+           (uint32_t)p->fill_u <= 255 && (uint32_t)p->fill_v <= 255 && warp_grid_ok(p->grid_log2);
+}
+// control points across or down a destination side
+static inline int warp_mesh_side(int d, int grid_log2) { return ((d + (1 << grid_log2) - 1) >> grid_log2) + 1; }
+static inline size_t warp_mesh_bytes(int dw, int dh, int grid_log2) {
+    return (size_t)warp_mesh_side(dw, grid_log2) * warp_mesh_side(dh, grid_log2) * 2 * sizeof(int32_t);
+}
+// arguments of a warp call, the pointers' values included. Both pictures are canvases (sides_ok would hold the source
+// to PIC_MAX_SRC, the limit of the resamplers whose arithmetic grows with the source side; the warp's does not)
+static inline bool warp_args_ok(const void *dst, int dw, int dh, const void *src, int sw, int sh, int n, const void *mesh, int mesh_per_frame,
+                                const h264mi_warp *p) {
+    if (!dst || !src || !mesh || n < 1 || !canvas_ok(dw, dh) || !canvas_ok(sw, sh) || !warp_ok(p)) return false;
+    if (((uintptr_t)mesh & 3) || (mesh_per_frame != 0 && mesh_per_frame != 1)) return false;
+    const size_t db = (size_t)n * i420_bytes(dw, dh);
+    return !byte_ranges_overlap(dst, db, src, (size_t)n * i420_bytes(sw, sh)) &&
+           !byte_ranges_overlap(dst, db, mesh, (mesh_per_frame ? (size_t)n : 1) * warp_mesh_bytes(dw, dh, p->grid_log2));
+}
+
 // ---- cell lists
 // the kind of a cell: 0 shrinking (equal sizes included), 1 enlarging, -1 one axis each way
 static inline int cell_kind(const h264mi_cell &c) {
@@ -532,6 +573,17 @@ int launch_levels_i420(uint8_t *dst, const uint8_t *src, int w, int h, int n, co
 void hist_frame_host(uint32_t *hist, const uint8_t *frame, int w, int h);
 void lut_frame_host(uint8_t *dst, const uint8_t *src, int w, int h, const uint8_t *lut768);
 void levels_lut_host(uint8_t *lut768, const uint32_t *hist_y, int w, int h, const h264mi_levels &p, int32_t *state4, int32_t *record8);
+// warp.hip: arguments as warp_args_ok accepts them; mesh on the device. warp_frame_host: one frame sample by sample,
+// mesh on the host. The builders fill a host mesh and return its number of points, or -1. warp_tile_class: 0 when the
+// kernel stages the source footprint of tile (tx, ty) of plane 0..2 in LDS, 1 when it samples global memory, -1 on a
+// bad argument. path: 0, or 1 (measurement only) for the global path in every tile
+int launch_warp_i420(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, int n, const int32_t *mesh, int mesh_per_frame,
+                     const h264mi_warp &p, int path, hipStream_t s);
+void warp_frame_host(uint8_t *dst, int dw, int dh, const uint8_t *src, int sw, int sh, const int32_t *mesh, const h264mi_warp &p);
+int warp_mesh_affine(int32_t *mesh, int dw, int dh, int grid_log2, const int32_t *m6);
+int warp_mesh_homography(int32_t *mesh, int dw, int dh, int grid_log2, const int32_t *h9);
+int warp_mesh_radial(int32_t *mesh, int dw, int dh, int grid_log2, int cx, int cy, int64_t r2, int k1, int k2);
+int warp_tile_class(const int32_t *mesh, int dw, int dh, int sw, int sh, int grid_log2, int plane, int tx, int ty);
 // pixfmt.hip, pixdeep.hip
 int launch_pix_to_i420(uint8_t *d_i420, const uint8_t *d_src, const h264mi_pix_layout &L, int w, int h, int n, hipStream_t s);
 int launch_i420_to_pix(uint8_t *d_dst, const h264mi_pix_layout &L, const uint8_t *d_i420, int w, int h, int n, hipStream_t s);

@@ -47,18 +47,7 @@ struct UpscaleLaunch {
 };
 static_assert(sizeof(UpscaleLaunch) < 2048, "the argument block stays well below 4 KB");
 
-// the four weights of phase f (0..15), sum 8192
-__host__ __device__ static inline void up_weights(int f, bool cubic, int *w) {
-    if (cubic) {
-        const int f2 = f * f, f3 = f2 * f;
-        w[0] = -f3 + 32 * f2 - 256 * f;
-        w[1] = 3 * f3 - 80 * f2 + 8192;
-        w[2] = -3 * f3 + 64 * f2 + 256 * f;
-        w[3] = f3 - 16 * f2;
-    } else {
-        w[0] = 0; w[1] = (16 - f) * 512; w[2] = f * 512; w[3] = 0;
-    }
-}
+// the four weights of phase f: up_weights, picture_host.h (warp.hip samples under the same ones)
 // P of output index o: floor((16 ((2 o + 1) p - q) + q) / (2 q)). The numerator is above -15 q, so 32 q added makes it
 // positive (and leaves it below 2^31 for p <= 4096, q <= 8192); the quotient is then 16 too large
 __host__ __device__ static inline int up_phase(int o, int p, int q) {

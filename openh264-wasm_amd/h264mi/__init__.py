@@ -214,6 +214,15 @@ def lib():
             'h264mi_enc_set_levels': (i, [vp, vp]),
             'h264mi_enc_levels': (i, [vp, vp]),
             'h264mi_enc_levels_record': (i, [vp, vp, i]),
+            'h264mi_warp_ok': (i, [vp]),
+            'h264mi_warp_mesh_size': (i, [i, i, i, vp, vp]),
+            'h264mi_warp_mesh_affine': (i, [vp, i, i, i, vp]),
+            'h264mi_warp_mesh_homography': (i, [vp, i, i, i, vp]),
+            'h264mi_warp_mesh_radial': (i, [vp, i, i, i, i, i, ctypes.c_int64, i, i]),
+            'h264mi_warp_tile_class': (i, [vp, i, i, i, i, i, i, i, i]),
+            'h264mi_i420_warp_dev': (i, [vp, i, i, vp, i, i, i, vp, i, vp, vp]),
+            'h264mi_i420_warp_host': (i, [vp, i, i, vp, i, i, vp, vp]),
+            'h264mi_enc_encode_warped': (i, [vp, vp, i, i, vp, i, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -474,6 +483,19 @@ class BatchEncoder:
         assert frames.is_cuda and frames.numel() >= self.S * _i420_bytes(self.w, self.h)
         if self._L.h264mi_enc_encode_oriented(self._e, ctypes.c_void_p(frames.data_ptr()), int(orient)) != 0:
             raise ValueError(f'h264mi_enc_encode_oriented refused orientation {orient} -> {self.w}x{self.h}')
+
+    def encode_warped(self, frames, src_w, src_h, mesh, params, mesh_per_stream=False):
+        """frames: uint8 CUDA tensor holding S tight I420 frames of src_w x src_h back to back, any alignment; mesh: int32
+        CUDA tensor holding one mesh for the encoder's size, or S of them with mesh_per_stream; params: a Warp or
+        (filter, edge, fill_y, fill_u, fill_v, grid_log2) (async): one batched warp (i420_warp) into the encoder's input
+        area on its stream, then the stages in force and the frame step of encode(). ValueError, with nothing enqueued,
+        for what i420_warp refuses, frames or a mesh inside the input area, or while the deinterlacer is on."""
+        assert frames.is_cuda and frames.numel() >= self.S * _i420_bytes(src_w, src_h)
+        d = Warp._of(params)
+        _assert_dev_mesh(mesh, self.w, self.h, d, self.S if mesh_per_stream else 1)
+        if self._L.h264mi_enc_encode_warped(self._e, _ptr(frames), int(src_w), int(src_h), _ptr(mesh), int(bool(mesh_per_stream)),
+                                            _byref(d)) != 0:
+            raise ValueError(f'h264mi_enc_encode_warped refused {src_w}x{src_h} -> {self.w}x{self.h}, {d!r}')
 
     def encode_pix(self, frames, layout):
         """frames: uint8 CUDA tensor holding S frames of the encoder's size in `layout` (a PixLayout: NV12, NV21, YUY2,
@@ -1524,6 +1546,116 @@ def i420_levels(dst, src, w, h, n, params, work, state=None, record=None, stream
 
 PRIVACY_PIXELATE = 0  # H264MI_PRIVACY_PIXELATE: cells of block x block become their mean
 PRIVACY_FILL = 1      # H264MI_PRIVACY_FILL: the rectangle becomes (fill_y, fill_cb, fill_cr)
+
+
+WARP_CLAMP = 0  # H264MI_WARP_CLAMP: positions outside the source repeat its edge samples
+WARP_FILL = 1   # H264MI_WARP_FILL: they take the fill values
+
+
+class Warp(_Record):
+    """h264mi_warp (include/h264mi.h): filter FILTER_BILINEAR or FILTER_BICUBIC, edge WARP_CLAMP or WARP_FILL, fill_y,
+    fill_u, fill_v 0..255 (FILL), grid_log2 3..5 (the mesh pitch is 1 << grid_log2 destination luma samples). 24 bytes"""
+    _fields_ = [(k, ctypes.c_int32) for k in ('filter', 'edge', 'fill_y', 'fill_u', 'fill_v', 'grid_log2')]
+
+
+def warp_ok(params):
+    """0 when every field of params (a Warp or six integers) is in its range, else -1 (None included); h264mi_warp_ok"""
+    return lib().h264mi_warp_ok(_byref(Warp._of(params)))
+
+
+def warp_mesh_size(dw, dh, grid_log2):
+    """(mw, mh): the control points of a mesh for a dw x dh destination (h264mi_warp_mesh_size; host only). ValueError on a
+    side that is odd or outside 2..8192 or grid_log2 outside 3..5."""
+    mw, mh = ctypes.c_int(), ctypes.c_int()
+    if lib().h264mi_warp_mesh_size(int(dw), int(dh), int(grid_log2), ctypes.byref(mw), ctypes.byref(mh)) != 0:
+        raise ValueError(f'bad arguments: a mesh of pitch 1 << {grid_log2} for {dw}x{dh}')
+    return mw.value, mh.value
+
+
+def _warp_mesh(dw, dh, grid_log2, fill):
+    """a (mh, mw, 2) int32 array filled by fill(pointer); ValueError when the builder refuses"""
+    import numpy as np
+    mw, mh = warp_mesh_size(dw, dh, grid_log2)
+    mesh = np.zeros((mh, mw, 2), np.int32)
+    if fill(mesh.ctypes.data_as(ctypes.c_void_p)) != mw * mh:
+        raise ValueError(f'the builder refused its arguments for {dw}x{dh}, pitch 1 << {grid_log2}')
+    return mesh
+
+
+def warp_mesh_affine(dw, dh, grid_log2, m):
+    """the mesh of the affine map m (six Q16 integers: x = m0 X + m1 Y + m2, y = m3 X + m4 Y + m5, in samples) as a
+    (mh, mw, 2) numpy int32 array of (x, y) in sixteenths; h264mi_warp_mesh_affine, host only"""
+    c = (ctypes.c_int32 * 6)(*(int(v) for v in m))
+    return _warp_mesh(dw, dh, grid_log2, lambda p: lib().h264mi_warp_mesh_affine(p, int(dw), int(dh), int(grid_log2), c))
+
+
+def warp_mesh_homography(dw, dh, grid_log2, h):
+    """the mesh of the homography h (nine Q16 integers, row-major); ValueError where the denominator is not positive at a
+    control point; h264mi_warp_mesh_homography, host only"""
+    c = (ctypes.c_int32 * 9)(*(int(v) for v in h))
+    return _warp_mesh(dw, dh, grid_log2, lambda p: lib().h264mi_warp_mesh_homography(p, int(dw), int(dh), int(grid_log2), c))
+
+
+def warp_mesh_radial(dw, dh, grid_log2, cx, cy, r2, k1, k2):
+    """the mesh that removes a two-coefficient radial lens distortion: (cx, cy) the centre in sixteenths, r2 the
+    reference radius squared in sixteenths squared, k1, k2 signed Q16; ValueError beyond the limits the header states;
+    h264mi_warp_mesh_radial, host only"""
+    return _warp_mesh(dw, dh, grid_log2, lambda p: lib().h264mi_warp_mesh_radial(p, int(dw), int(dh), int(grid_log2), int(cx), int(cy),
+                                                                                  int(r2), int(k1), int(k2)))
+
+
+def warp_tile_class(mesh, dw, dh, sw, sh, grid_log2, plane, tx, ty):
+    """0 when the kernel stages the source footprint of tile (tx, ty) of plane 0..2 in LDS, 1 when it samples global
+    memory; mesh: a host (mh, mw, 2) int32 array; h264mi_warp_tile_class, host only"""
+    import numpy as np
+    m = np.ascontiguousarray(mesh, np.int32)
+    assert m.size == 2 * int(np.prod(warp_mesh_size(dw, dh, grid_log2)))
+    r = lib().h264mi_warp_tile_class(m.ctypes.data_as(ctypes.c_void_p), int(dw), int(dh), int(sw), int(sh), int(grid_log2), int(plane),
+                                     int(tx), int(ty))
+    if r < 0:
+        raise ValueError(f'bad arguments: tile ({tx}, {ty}) of plane {plane}, {sw}x{sh} -> {dw}x{dh}')
+    return r
+
+
+def _assert_dev_mesh(mesh, dw, dh, d, count):
+    """mesh is a contiguous int32 device tensor that holds count meshes (when the geometry is good enough to tell)"""
+    import torch
+    assert mesh.is_cuda and mesh.dtype == torch.int32 and mesh.is_contiguous()
+    if d is not None and 3 <= d.grid_log2 <= 5 and min(dw, dh) > 0:
+        G = 1 << d.grid_log2
+        assert mesh.numel() >= count * 2 * ((dw + G - 1) // G + 1) * ((dh + G - 1) // G + 1)
+
+
+def i420_warp(dst, src, sw, sh, dw, dh, n, mesh, params, mesh_per_frame=False, stream=None):
+    """n tight sw x sh I420 frames (uint8 CUDA tensor src, any alignment) warped to n tight dw x dh frames (dst) under the
+    mesh (int32 CUDA tensor: one mesh, or n back to back with mesh_per_frame), async on stream (default: the current
+    one); h264mi_i420_warp_dev. params: a Warp or (filter, edge, fill_y, fill_u, fill_v, grid_log2). The bytes equal
+    tests/warpref.py's. Minification is not antialiased. ValueError on a bad argument (a parameter out of range, a side
+    that is odd or outside 2..8192, n < 1, a destination that shares a byte with the source or the mesh)."""
+    _assert_dev_u8(dst, src)
+    ok = n > 0 and min(sw, sh, dw, dh) > 0
+    assert dst.numel() >= (n * _i420_bytes(dw, dh) if ok else 0) and src.numel() >= (n * _i420_bytes(sw, sh) if ok else 0)
+    d = Warp._of(params)
+    if ok:
+        _assert_dev_mesh(mesh, dw, dh, d, n if mesh_per_frame else 1)
+    if lib().h264mi_i420_warp_dev(_ptr(dst), int(dw), int(dh), _ptr(src), int(sw), int(sh), int(n), _ptr(mesh), int(bool(mesh_per_frame)),
+                                  _byref(d), _hip_stream(stream)) != 0:
+        raise ValueError(f'bad arguments: {n} frames {sw}x{sh} -> {dw}x{dh}, {d!r}')
+
+
+def i420_warp_host(src, sw, sh, dw, dh, mesh, params):
+    """one frame (a numpy uint8 array) warped on the host by the library's own loops (h264mi_i420_warp_host): the dw x dh
+    frame as a numpy array. mesh: a host (mh, mw, 2) int32 array"""
+    import numpy as np
+    s = np.ascontiguousarray(src, np.uint8).ravel()
+    m = np.ascontiguousarray(mesh, np.int32)
+    d = Warp._of(params)
+    assert s.size >= _i420_bytes(sw, sh) and m.size == 2 * int(np.prod(warp_mesh_size(dw, dh, d.grid_log2)))
+    out = np.zeros(_i420_bytes(dw, dh), np.uint8)
+    if lib().h264mi_i420_warp_host(out.ctypes.data_as(ctypes.c_void_p), int(dw), int(dh), s.ctypes.data_as(ctypes.c_void_p), int(sw), int(sh),
+                                   m.ctypes.data_as(ctypes.c_void_p), _byref(d)) != 0:
+        raise ValueError(f'bad arguments: {sw}x{sh} -> {dw}x{dh}, {d!r}')
+    return out
 
 
 class Privacy(_Record):

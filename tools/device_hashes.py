@@ -8,7 +8,7 @@ import subprocess
 import sys
 import tempfile
 
-UNITS = ('h264mi_kernels', 'quality', 'scale', 'compose', 'overlay', 'upscale', 'orient', 'pixfmt', 'pixdeep', 'colorspace', 'denoise', 'scenecut', 'deinterlace', 'spatial', 'levels')
+UNITS = ('h264mi_kernels', 'quality', 'scale', 'compose', 'overlay', 'upscale', 'orient', 'pixfmt', 'pixdeep', 'colorspace', 'denoise', 'scenecut', 'deinterlace', 'spatial', 'levels', 'warp')
 HIPCC = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '--no-gpu-bundle-output', '-c']
 OBJCOPY = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'llvm', 'bin', 'llvm-objcopy')
 
